@@ -1,7 +1,7 @@
 """Headline benchmark: graph-steps/s of the spatial block on the synthetic drainage network
 |V|=10k, |E|=12k, d=64 (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one batch: the L-layer spatial block
@@ -9,6 +9,13 @@ A "step" = one pass of the hot path over one batch: the L-layer spatial block
 (graph-step = one spatial layer on one snapshot).  With N > 1 every rank
 runs its own S snapshots of the same network (snapshots are independent inside a forward,
 `emulator.py:217-218`): weak scaling, no data-path collective.  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the K steps and prints the headline line.  `--full` adds the
+other legs of that line: the 200k-node partitioned case (`c4_partitioned`), the whole-Emulator forward
+(`rollout`), the dense-trained-bias block (`trained_bias`) and the CPU oracle with the parity check
+(`cpu_baseline`, `roofline.parity_err_vs_fp64`).  `--dump-outputs DIR` writes what the last timed step
+returned (rank 0's x' and e') as DIR/nodes.npy and DIR/links.npy, float32; inputs and weights are seeded,
+so two builds run with the same arguments can be compared output for output.
 
 `--workload c4` switches to BASELINE.json's 200k-node mega-catchment: ONE network node-cut partitioned
 over the N ranks, boundary rows exchanged once per layer over RCCL (gnn_uds_amd/dist.py): strong scaling.
@@ -26,6 +33,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0       # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 achievable
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: all files together stay under 64 MB
 
 
 def algorithmic_bytes_per_graph_step(g, f_in, d):
@@ -47,6 +55,37 @@ def recorded_traffic(args):
     same = (cfg.get('nodes') == args.nodes and cfg.get('links') == args.links and cfg.get('embed') == args.embed and
             cfg.get('snapshots') == args.snapshots and cfg.get('precision') == args.precision)
     return rec.get('traffic_bytes_per_launch') if same else None
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: each (..., d) output as `path/<name>.npy`, float32, rows flattened to (rows, d).  When all of them
+    together exceed DUMP_BUDGET_BYTES, every output keeps the same fraction of its rows: a sorted sample drawn with a fixed
+    seed, so the rows depend only on the shapes (the headline's 338 MB of x', e' keep ~18 % of their rows)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() for t in outputs.values()) * 4
+    frac = min(1.0, DUMP_BUDGET_BYTES / total)
+    for name, t in outputs.items():
+        a = t.detach().reshape(-1, t.shape[-1])
+        if frac < 1.0:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], int(a.shape[0] * frac), replace=False))
+            a = a[torch.from_numpy(rows).to(a.device)]
+        np.save(os.path.join(path, name + '.npy'), a.float().cpu().numpy())
+    return frac
+
+
+def headline_setup(U, args, dev, rank=0):
+    """The headline workload's network, block and inputs: all seeded, so the same arguments give the same inputs and
+    weights in every run (what makes --dump-outputs comparable between builds).  Returns (graph, block, x, e)."""
+    g = U.DrainageGraph.from_edges(U.synthetic_drainage_network(args.nodes, args.links, seed=0))
+    d, L, S = args.embed, args.layers, args.snapshots
+    # random-init weights of the reference architecture (Keras initialisers: glorot_uniform kernels, zero
+    # biases, N(0, 0.05^2) NodeEdge weights; SURVEY.md Appendix C), seed 1
+    block = U.SpatialBlock(g, d, L, 'relu', sparse_params=True, generator=torch.Generator().manual_seed(1),
+                           precision=args.precision).to(dev)
+    gen = torch.Generator().manual_seed(2 + rank)
+    x = torch.rand(S, g.n_node, d, generator=gen).to(dev)
+    e = torch.rand(S, g.n_edge, d, generator=gen).to(dev)
+    return g, block, x, e
 
 
 def rollout_forward(U, g, args, dev, reps=30):
@@ -486,14 +525,24 @@ def main():
     ap.add_argument('--workload', default='headline', choices=['headline', 'c4', 'c5', 'small'],
                     help='c4: 200k-node / 240k-link network partitioned over the ranks with per-layer halo exchange')
     ap.add_argument('--graph', action='store_true', help='replay the L layer launches of a step from one captured HIP graph')
+    ap.add_argument('--full', action='store_true',
+                    help='headline workload: also run the legs beyond the headline figure (c4_partitioned, rollout, trained_bias, '
+                         'cpu_baseline with the fp64 parity check); the --no-* switches below drop single legs of a --full run')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='headline workload: write what the last timed step returned as DIR/nodes.npy and DIR/links.npy (float32, '
+                         'a fixed seeded sample of rows when the outputs exceed 64 MB)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-trained-bias', action='store_true', help='skip the dense-trained-bias NodeEdge leg')
     ap.add_argument('--autoregressive', action='store_true',
-                    help='also time the C2 autoregressive rollout (100 fed-back steps, eager and HIP graph); off by default so that '
-                         'the rocprofv3 averages of the default command are those of the timed headline launches')
+                    help='with --full: also time the C2 autoregressive rollout (100 fed-back steps, eager and HIP graph); off by default '
+                         'so that the rocprofv3 averages of a --full command are those of the timed headline launches')
     ap.add_argument('--no-rollout', action='store_true', help='skip the whole-Emulator forward legs (profiling runs: only the timed headline launches)')
     ap.add_argument('--no-c4', action='store_true', help='skip the 200k-node partitioned leg of the headline line')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if args.dump_outputs and args.workload != 'headline':
+        ap.error('--dump-outputs writes the outputs of the headline workload only')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` (how the driver calls it): start the N ranks here, as a CHILD process and before
@@ -549,16 +598,8 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
-    g = U.DrainageGraph.from_edges(U.synthetic_drainage_network(args.nodes, args.links, seed=0))
+    g, block, x, e = headline_setup(U, args, dev, rank)
     d, L, S = args.embed, args.layers, args.snapshots
-    # random-init weights of the reference architecture (Keras initialisers: glorot_uniform kernels, zero
-    # biases, N(0, 0.05^2) NodeEdge weights), seed 1
-    block = U.SpatialBlock(g, d, L, 'relu', sparse_params=True, generator=torch.Generator().manual_seed(1),
-                           precision=args.precision).to(dev)
-    params = [layer.export_params() for layer in block.layers]
-    gen = torch.Generator().manual_seed(2 + rank)
-    x = torch.rand(S, g.n_node, d, generator=gen).to(dev)
-    e = torch.rand(S, g.n_edge, d, generator=gen).to(dev)
 
     # one step = the L layer launches from Python; `--graph` replays them from ONE captured HIP graph instead (SpatialBlock.graphed).
     # At the headline size the two are equal within noise (231-232 k vs 233-235 k graph-steps/s: the host runs ahead of 250-us kernels)
@@ -574,9 +615,11 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for a, b in ev:
+        last = None         # release the previous step's result before the next step allocates, as a discarded result would be
         a.record()          # events on torch's current stream = the stream the kernels are launched on
-        step()
+        last = step()
         b.record()
     torch.cuda.synchronize()
     if dist is not None:
@@ -587,11 +630,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
     dev_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))      # device time of one step
+    if args.dump_outputs and rank == 0:
+        frac = dump_outputs(args.dump_outputs, {'nodes': last[0], 'links': last[1]})
+        print('bench.py: last timed step written to %s (%.1f %% of the rows)' % (args.dump_outputs, 100 * frac), file=sys.stderr)
+    last = None
 
     # BASELINE.json's partitioned case beside the headline (every N, so that the N = 1 line is the base of the strong-scaling
     # ratio): the 200k-node network node-cut over the ranks, boundary rows exchanged after every layer
     c4 = None
-    if not args.no_c4 and args.embed == 64 and args.precision == 'bf16x3' and (args.nodes, args.links) == (10000, 12000):
+    if args.full and not args.no_c4 and args.embed == 64 and args.precision == 'bf16x3' and (args.nodes, args.links) == (10000, 12000):
         c4 = bench_c4(argparse.Namespace(**dict(vars(args), steps=min(args.steps, 50), warmup=min(args.warmup, 10), snapshots=60)),
                       U, dist, world, rank, dev)
 
@@ -626,14 +673,15 @@ def main():
         }
         if c4 is not None:
             out['c4_partitioned'] = {k: c4[k] for k in ('metric', 'value', 'unit', 'n_gpus', 'ms_per_step', 'scaling', 'config', 'halo', 'roofline')}
-        if world == 1 and args.embed == 64 and not args.no_rollout:
+        if args.full and world == 1 and args.embed == 64 and not args.no_rollout:
             out['rollout'] = rollout_forward(U, g, args, dev)
             if args.autoregressive:
                 out['rollout']['autoregressive'] = rollout_autoregressive(U, dev)
-        if world == 1 and args.embed in (64, 128) and args.precision == 'bf16x3' and not args.no_trained_bias \
+        if args.full and world == 1 and args.embed in (64, 128) and args.precision == 'bf16x3' and not args.no_trained_bias \
                 and g.n_node * g.n_edge <= (1 << 28):
             out['trained_bias'] = trained_bias_leg(U, g, args, dev, x, e)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
+            params = [layer.export_params() for layer in block.layers]
             cb = cpu_baseline(U, g, params, d, gpu_out=step(), gpu_in=(x, e))
             # max |GPU - fp64 oracle| / max(1, max|oracle|) over all rows of the first snapshot after the whole L-layer block
             out['roofline']['parity_err_vs_fp64'] = cb.pop('parity_err_vs_fp64', None)
