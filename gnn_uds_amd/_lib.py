@@ -53,6 +53,10 @@ SYMBOLS = {
     'uds_diffusion_forward': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
     'uds_halo_pack': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr]),
     'uds_halo_unpack': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr]),
+    'uds_halo_pack_all': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_i64,
+                                   _c_ptr, _c_ptr]),
+    'uds_halo_unpack_all': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr,
+                                     _c_i64, _c_ptr]),
     'uds_remainder_packed_bytes': (_c_i64, [_c_i64, _c_i64]),
     'uds_remainder_pack': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr]),
     'uds_remainder_workspace_bytes': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
@@ -533,6 +537,44 @@ def halo_unpack(buf, x, e, idx_x, idx_e):
         _check(lib.uds_halo_unpack(_dev(buf, 'buf'), S, F, _dev_i32(idx_x, 'idx_x') if nx else None, nx,
                                    _dev_i32(idx_e, 'idx_e') if ne else None, ne, _dev(x, 'x'), n_x, _dev(e, 'e'), e.shape[1], _stream()),
                'uds_halo_unpack')
+
+
+def _halo_all_args(x, e, idx_x, idx_e, off_x, off_e, what):
+    if x.dim() != 3 or e.dim() != 3 or x.shape[0] != e.shape[0] or x.shape[2] != e.shape[2]:
+        raise UdsError('%s: x %r and e %r must be (S, rows, F) with the same S and F' % (what, tuple(x.shape), tuple(e.shape)))
+    P = int(off_x.numel()) - 1
+    if P < 1 or int(off_e.numel()) != P + 1:
+        raise UdsError('%s: off_x / off_e need P + 1 >= 2 entries each, got %d / %d' % (what, off_x.numel(), off_e.numel()))
+    return P, int(idx_x.numel()), int(idx_e.numel())
+
+
+def halo_pack_all(x, e, idx_x, idx_e, off_x, off_e):
+    """The messages of all P peers, ONE launch (uds_halo_pack_all): a flat buffer in which peer q's message is the (S, nx_q + ne_q, F)
+    block [x[:, idx_x[off_x[q]:off_x[q+1]]] | e[:, idx_e[off_e[q]:off_e[q+1]]]] at element offset S F (off_x[q] + off_e[q]).
+    idx_* / off_* are int32 device tensors (off_*: P + 1 offsets); any F >= 1."""
+    lib = load()
+    P, nx, ne = _halo_all_args(x, e, idx_x, idx_e, off_x, off_e, 'halo_pack_all')
+    S, n_x, F = x.shape
+    buf = torch.empty(S * (nx + ne) * F, device=x.device, dtype=torch.float32)
+    if buf.numel():
+        _check(lib.uds_halo_pack_all(_dev(x, 'x') if nx else None, n_x, _dev(e, 'e') if ne else None, e.shape[1], S, F,
+                                     _dev_i32(idx_x, 'idx_x') if nx else None, nx, _dev_i32(idx_e, 'idx_e') if ne else None, ne,
+                                     _dev_i32(off_x, 'off_x'), _dev_i32(off_e, 'off_e'), P, _dev(buf, 'buf'), _stream()), 'uds_halo_pack_all')
+    return buf
+
+
+def halo_unpack_all(buf, x, e, idx_x, idx_e, off_x, off_e):
+    """The inverse of halo_pack_all: every peer's block of `buf` scattered into its rows of x / e (in place), ONE launch."""
+    lib = load()
+    P, nx, ne = _halo_all_args(x, e, idx_x, idx_e, off_x, off_e, 'halo_unpack_all')
+    S, n_x, F = x.shape
+    if buf.numel() != S * (nx + ne) * F:
+        raise UdsError('halo_unpack_all: buffer of %d floats for %d + %d rows of %r' % (buf.numel(), nx, ne, tuple(x.shape)))
+    if buf.numel():
+        _check(lib.uds_halo_unpack_all(_dev(buf, 'buf'), S, F, _dev_i32(idx_x, 'idx_x') if nx else None, nx,
+                                       _dev_i32(idx_e, 'idx_e') if ne else None, ne, _dev_i32(off_x, 'off_x'), _dev_i32(off_e, 'off_e'), P,
+                                       _dev(x, 'x') if nx else None, n_x, _dev(e, 'e') if ne else None, e.shape[1], _stream()),
+               'uds_halo_unpack_all')
 
 
 def remainder_pack(rest):

@@ -583,6 +583,54 @@ inline hipError_t launch_halo_rows(const HaloArgs &a, bool pack, hipStream_t st)
   return hipGetLastError();
 }
 
+// The messages of ALL peers in one launch (dist.HaloExchangeAll).  Message rows are numbered across peers: peer q owns
+// rows [r_q, r_{q+1}), r_q = off_x[q] + off_e[q], node rows first; its block of the buffer is (S, n_q, F) at float offset
+// S * F * r_q, so each peer's message stays one contiguous slice.
+//   PACK:   buf[S F r_q + (s n_q + j) F + f] = j < nx_q ? x[s, idx_x[off_x[q] + j], f] : e[s, idx_e[off_e[q] + j - nx_q], f]
+//   UNPACK: the inverse scatter.
+// Grid (ceil(n_rows * W / 256), S); thread = (message row, W-th of a row): W = F / 4 float4 (VEC) or F floats.
+struct HaloAllArgs {
+  float *x, *e, *buf;
+  const int32_t *idx_x, *idx_e, *off_x, *off_e;      // off_* (P + 1), device
+  int64_t n_x, n_e;
+  int n_rows, P, F, W;
+};
+
+template <bool PACK, bool VEC>
+__global__ __launch_bounds__(256) void k_halo_rows_all(HaloAllArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)a.n_rows * a.W) return;
+  const int r = (int)(i / a.W), c = (int)(i % a.W);
+  const int64_t s = blockIdx.y, S = gridDim.y;
+  int lo = 0, hi = a.P;                                  // peer q: r_q <= r < r_{q+1} (peers with no rows are skipped over)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (a.off_x[mid] + a.off_e[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  const int q = lo, r0 = a.off_x[q] + a.off_e[q], nx = a.off_x[q + 1] - a.off_x[q];
+  const int n = a.off_x[q + 1] + a.off_e[q + 1] - r0, j = r - r0;
+  float *row = j < nx ? a.x + (s * a.n_x + a.idx_x[a.off_x[q] + j]) * a.F : a.e + (s * a.n_e + a.idx_e[a.off_e[q] + j - nx]) * a.F;
+  float *slot = a.buf + S * a.F * r0 + (s * n + j) * a.F;
+  if (VEC) {
+    float4 *rv = reinterpret_cast<float4 *>(row) + c, *sv = reinterpret_cast<float4 *>(slot) + c;
+    if (PACK) *sv = *rv;
+    else *rv = *sv;
+  } else {
+    if (PACK) slot[c] = row[c];
+    else row[c] = slot[c];
+  }
+}
+
+inline hipError_t launch_halo_rows_all(const HaloAllArgs &a, int S, bool pack, bool vec, hipStream_t st) {
+  const dim3 grid((unsigned)(((int64_t)a.n_rows * a.W + 255) / 256), (unsigned)S);
+  if (pack && vec) hipLaunchKernelGGL((k_halo_rows_all<true, true>), grid, dim3(256), 0, st, a);
+  else if (pack) hipLaunchKernelGGL((k_halo_rows_all<true, false>), grid, dim3(256), 0, st, a);
+  else if (vec) hipLaunchKernelGGL((k_halo_rows_all<false, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((k_halo_rows_all<false, false>), grid, dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 // spektral DiffusionConv in the reference's dense "mixed" mode (emulator.py:135-138,229): each of the C output channels
 // is ONE DiffuseFeatures filter, H_q = reduce_sum(polyval(theta_q, a_hat) @ x, -1), where tf.math.polyval runs Horner's
 // rule on the ENTRIES of a_hat.  A zero entry therefore gets the constant coefficient c0_q = theta_q[K], and with

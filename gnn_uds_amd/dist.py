@@ -24,7 +24,9 @@ from typing import Dict, List
 import numpy as np
 import torch
 import torch.distributed as dist
+from torch import nn
 
+from .emulator import Emulator
 from .graph import CSR, DrainageGraph
 
 I32 = np.int32
@@ -411,3 +413,342 @@ def allreduce_gradients(params, group=None, bucket_bytes=64 << 20):
         n_calls += 1
         i = j
     return n_calls
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The whole Emulator on a graph-sharded network ("whole-forward schedule")
+# ---------------------------------------------------------------------------------------------------------------------
+def flow_rows(prob):
+    """The `rows=` subset of the post-processing's flow exchange: the halo LINKS incident to own nodes (the only flows the
+    link -> node balance of an own node reads that the rank does not own), no node rows.  Both ends agree without talking:
+    a link belongs to its from-node's part, so the receiver keeps the halo links whose to-node it owns and the sender keeps
+    the own links whose to-node the receiver owns -- in the plan's order, which the two lists share."""
+    edges = np.asarray(prob.graph.edges, dtype=np.int64)
+    n_own = len(prob.own_nodes)
+    recv_links = {q: idx[(edges[idx, 1] >= 0) & (edges[idx, 1] < n_own)] for q, idx in prob.recv_links.items()}
+    send_links = {}
+    for q, idx in prob.send_links.items():
+        theirs = prob.recv_nodes.get(q, np.zeros(0, np.int64))
+        send_links[q] = idx[np.isin(edges[idx, 1], theirs)]
+    return dict(send_links=send_links, recv_links=recv_links)
+
+
+class HaloExchangeAll:
+    """`HaloExchange` with ONE pack launch and ONE unpack launch per exchange, whatever the number of peers
+    (uds_halo_pack_all / uds_halo_unpack_all): the per-peer row lists are concatenated (int32, with P + 1 offsets) and all
+    messages live in one send buffer and one receive buffer, peer q's message the contiguous (S, nx_q + ne_q, F) block at
+    S F (off_x[q] + off_e[q]) -- a plain slice for `batch_isend_irecv`.  Any row width F >= 1.
+
+    rows: a subset of the plan's lists, a dict with any of 'send_nodes', 'send_links', 'recv_nodes', 'recv_links' (peer ->
+    LOCAL indices, as in LocalProblem); a list the dict does not name is empty (`flow_rows`).  None: the plan's lists."""
+
+    def __init__(self, prob, device, group=None, rows=None):
+        self.prob, self.group = prob, group
+        if rows is None:
+            rows = dict(send_nodes=prob.send_nodes, send_links=prob.send_links, recv_nodes=prob.recv_nodes, recv_links=prob.recv_links)
+        get = lambda key, q: np.asarray(rows.get(key, {}).get(q, np.zeros(0, np.int64)), dtype=np.int64)
+        peers = sorted(set(prob.send_nodes) | set(prob.recv_nodes))
+        lists = {k: [get(k, q) for q in peers] for k in ('send_nodes', 'send_links', 'recv_nodes', 'recv_links')}
+        n_n, n_e = len(prob.nodes), len(prob.links)
+        for k, bound in (('send_nodes', len(prob.own_nodes)), ('send_links', len(prob.own_links)), ('recv_nodes', n_n), ('recv_links', n_e)):
+            lo = len(prob.own_nodes) if k == 'recv_nodes' else len(prob.own_links) if k == 'recv_links' else 0
+            for a in lists[k]:        # the kernels do not check rows on the device: every row is checked here, once
+                if len(a) and (a.min() < lo or a.max() >= bound):
+                    raise ValueError('HaloExchangeAll: %s rows outside [%d, %d)' % (k, lo, bound))
+        keep = [i for i in range(len(peers)) if sum(len(lists[k][i]) for k in lists)]
+        self.peers = [peers[i] for i in keep]
+        t = lambda a, dt: torch.as_tensor(a, dtype=dt, device=device)
+        self.dev = {}
+        self.n_send, self.n_recv = {}, {}             # peer -> message rows
+        for side in ('send', 'recv'):
+            xs = [lists[side + '_nodes'][i] for i in keep]
+            es = [lists[side + '_links'][i] for i in keep]
+            off_x = np.concatenate([[0], np.cumsum([len(a) for a in xs])]).astype(np.int64)
+            off_e = np.concatenate([[0], np.cumsum([len(a) for a in es])]).astype(np.int64)
+            cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.int64)
+            self.dev[side] = dict(idx_x=t(cat(xs), torch.int64), idx_e=t(cat(es), torch.int64), off_x=off_x, off_e=off_e,
+                                  idx_x32=t(cat(xs), torch.int32), idx_e32=t(cat(es), torch.int32),
+                                  off_x32=t(off_x, torch.int32), off_e32=t(off_e, torch.int32))
+            for k, q in enumerate(self.peers):
+                (self.n_send if side == 'send' else self.n_recv)[q] = (int(off_x[k] + off_e[k]), int(off_x[k + 1] + off_e[k + 1]))
+
+    def rows(self, side):
+        """(node rows, link rows) of all messages of `side` ('send' / 'recv'), int64 on the device, peers concatenated."""
+        d = self.dev[side]
+        return d['idx_x'], d['idx_e']
+
+    def pack(self, x, e):
+        """All outgoing messages in one flat buffer (one launch on the GPU)."""
+        d = self.dev['send']
+        if x.is_cuda:
+            from . import _lib
+            return _lib.halo_pack_all(x, e, d['idx_x32'], d['idx_e32'], d['off_x32'], d['off_e32'])
+        S, F = e.shape[0], e.shape[-1]        # CPU tensors (gloo): the same layout with index ops
+        parts = []
+        for k in range(len(self.peers)):
+            sx = d['idx_x'][int(d['off_x'][k]):int(d['off_x'][k + 1])]
+            se = d['idx_e'][int(d['off_e'][k]):int(d['off_e'][k + 1])]
+            parts.append(torch.cat([x.index_select(1, sx), e.index_select(1, se)], dim=1).reshape(-1))
+        return torch.cat(parts) if parts else e.new_empty(0)
+
+    def unpack(self, buf, x, e):
+        """Scatter every received message into the halo rows (in place; one launch on the GPU)."""
+        d = self.dev['recv']
+        if x.is_cuda:
+            from . import _lib
+            _lib.halo_unpack_all(buf, x, e, d['idx_x32'], d['idx_e32'], d['off_x32'], d['off_e32'])
+            return
+        S, F = e.shape[0], e.shape[-1]
+        for k in range(len(self.peers)):
+            r0, r1 = int(d['off_x'][k] + d['off_e'][k]), int(d['off_x'][k + 1] + d['off_e'][k + 1])
+            nx_ = int(d['off_x'][k + 1] - d['off_x'][k])
+            msg = buf[S * F * r0:S * F * r1].reshape(S, r1 - r0, F)
+            x.index_copy_(1, d['idx_x'][int(d['off_x'][k]):int(d['off_x'][k + 1])], msg[:, :nx_])
+            e.index_copy_(1, d['idx_e'][int(d['off_e'][k]):int(d['off_e'][k + 1])], msg[:, nx_:])
+
+    def message(self, buf, q, side, S, F):
+        """Peer q's slice of a send / receive buffer."""
+        r0, r1 = (self.n_send if side == 'send' else self.n_recv)[q]
+        return buf[S * F * r0:S * F * r1]
+
+    def __call__(self, x, e):
+        """x (S, n_local_nodes, F) or None (a link-only exchange), e (S, n_local_links, F): overwrite the halo rows with the
+        owners' exact rows; enqueued on the current stream, as `HaloExchange`."""
+        if x is None:
+            x = e.new_empty((e.shape[0], 0, e.shape[-1]))
+        if not self.peers:
+            return x, e
+        S, F = e.shape[0], e.shape[-1]
+        sbuf = self.pack(x, e)
+        n_recv = self.n_recv[self.peers[-1]][1]
+        rbuf = torch.empty(S * n_recv * F, device=e.device, dtype=e.dtype)
+        ops = []
+        for q in self.peers:
+            if self.n_recv[q][1] > self.n_recv[q][0]:
+                ops.append(dist.P2POp(dist.irecv, self.message(rbuf, q, 'recv', S, F), q, self.group))
+            if self.n_send[q][1] > self.n_send[q][0]:
+                ops.append(dist.P2POp(dist.isend, self.message(sbuf, q, 'send', S, F), q, self.group))
+        if ops:
+            for w in dist.batch_isend_irecv(ops):
+                w.wait()
+        self.unpack(rbuf, x, e)
+        return x, e
+
+
+def _refuse_unsharded_configuration(emul):
+    """Why `shard_emulator` cannot shard this model, or None."""
+    if not emul.conv:
+        return NotImplementedError, 'conv=False (the non-graph baseline flattens the whole network into one row per step)'
+    if emul.conv_kind != 'GAT':
+        return NotImplementedError, 'conv=%s: the sharded forward is built for GAT' % emul.conv_kind
+    if emul.graph_base:
+        return NotImplementedError, 'graph_base=%r: one graph over nodes and links has no node cut here' % emul.graph_base
+    if emul.use_adj:
+        return NotImplementedError, 'use_adj: the per-step adjacency of block 2 is not sharded'
+    if emul.dropout:
+        return NotImplementedError, 'dropout=%r: the sharded forward is inference only' % emul.dropout
+    for bi, block in enumerate((emul.block1, emul.block2)):
+        for li, ly in enumerate(block.layers):
+            for name in ('node_edge_n', 'node_edge_e'):
+                ne = getattr(ly, name)
+                if not ne.sparse and ne.support_values()[1] is not None:
+                    return ValueError, ('block %d layer %d %s: the NodeEdge bias is non-zero off the incidence support -- every node then '
+                                        'depends on every link and no halo of bounded radius exists' % (bi + 1, li, name))
+    return None
+
+
+class _ExchangedBlock(nn.Module):
+    """A SpatialBlock run layer by layer on a rank's sub-network with a halo exchange after every layer but the last (and,
+    for block 2, one exchange of its input first): exact on own rows, as `ShardedSpatialBlock`, same layers and kernels."""
+
+    def __init__(self, block, exchange, exchange_input):
+        super().__init__()
+        self.block, self.exchange_input = block, exchange_input
+        self._exchange = exchange
+
+    def forward(self, x, e, xb=None, eb=None, adj_mask=None, dropout=None, attn_dropout=None):
+        if adj_mask is not None or dropout is not None or attn_dropout is not None:
+            raise NotImplementedError('the sharded forward runs without use_adj and dropout')
+        ex = self._exchange
+        if self.exchange_input:
+            x, e = ex(x.contiguous(), e.contiguous())
+        layers = self.block.layers
+        net = layers[0].network()
+        for i, layer in enumerate(layers):
+            layer._net = net
+            x, e = layer(x, e, xb if i == 0 else None, eb if i == 0 else None)
+            if i + 1 < len(layers):
+                x, e = ex(x.contiguous(), e.contiguous())
+        return x, e
+
+
+class _LocalEmulator(Emulator):
+    """The Emulator of one rank: `Emulator` on the rank's sub-network whose action tables keep the GLOBAL columns and whose
+    flow balance first receives the owners' gated flows of the halo links incident to own nodes."""
+
+    def get_edge_action(self, a, g=True):
+        table = torch.cat([torch.ones_like(a[..., :1]), a], dim=-1)
+        return table[..., self._dev_index('edge_action', self._edge_act_cols, a.device)].unsqueeze(-1)
+
+    def get_action(self, a, g=True):
+        table = torch.cat([torch.ones_like(a[..., :1]), a], dim=-1)
+        return (table[..., self._dev_index('act_out', self._node_act_cols[0], a.device)],
+                table[..., self._dev_index('act_in', self._node_act_cols[1], a.device)])
+
+    def _flow_balance(self, flow):
+        f = flow.reshape(-1, self.n_edge, 1).contiguous()
+        self._flow_exchange(None, f)
+        return super()._flow_balance(f.reshape(flow.shape))
+
+
+def global_action_columns(emul):
+    """Column (1-based, 0 = no actuator) of the action vector that drives every link, and every node as the from / to end of
+    an actuated link -- the maps `Emulator.get_edge_action` / `get_action` build, over the WHOLE network."""
+    n_act = len(emul._act_edge_index())
+    link = np.zeros(emul.n_edge, dtype=np.int64)
+    link[emul._act_edge_index()] = np.arange(1, n_act + 1)
+    out_o, out_i = np.zeros(emul.n_node, dtype=np.int64), np.zeros(emul.n_node, dtype=np.int64)
+    out_o[emul.act_edges[:, 0]] = np.arange(1, len(emul.act_edges) + 1)
+    out_i[emul.act_edges[:, 1]] = np.arange(1, len(emul.act_edges) + 1)
+    return link, out_o, out_i
+
+
+def shard_emulator(emul, prob, device, group=None):
+    """The `ShardedEmulator` of one rank: an `Emulator` on `prob.graph` (the `args.graph` CSR path, local rows own first)
+    carrying the global model's state -- row-local parameters copied, NodeEdge parameters gathered onto the local support,
+    per-row constants and norms sliced to the local rows, the `_has_*` flags and the action columns of the GLOBAL model.
+    Inference only.  Refuses (NotImplementedError / ValueError) what has no bounded halo or is not built: conv=False, a conv
+    other than GAT, graph_base, use_adj, dropout, and a NodeEdge bias that is non-zero off the incidence support."""
+    why = _refuse_unsharded_configuration(emul)
+    if why is not None:
+        raise why[0]('shard_emulator: ' + why[1])
+    from types import SimpleNamespace
+    nodes, links = np.asarray(prob.nodes, dtype=np.int64), np.asarray(prob.links, dtype=np.int64)
+    args = dict(vars(emul._args))
+    nmap = np.full(emul.n_node, -1, dtype=np.int64)
+    nmap[nodes] = np.arange(len(nodes))
+    act_edges = None
+    if emul.act:
+        ae = nmap[np.asarray(emul.act_edges, dtype=np.int64)]
+        act_edges = ae[(ae >= 0).all(1)]           # documentation only: the action maps below carry the global columns
+    const = lambda name, idx: getattr(emul, name).detach().cpu().numpy()[idx].astype(np.float64)
+    ly0 = emul.block1.layers[0]
+    args.update(state_shape=(len(nodes), emul._args.state_shape[1]), edge_state_shape=(len(links), emul.e_in),
+                edges=np.asarray(prob.graph.edges), graph=prob.graph, adj=None, edge_adj=None, node_edge=None,
+                act_edges=act_edges, dropout=0.0, graph_base=0, use_adj=False, sparse_params=ly0.node_edge_n.sparse,
+                **{k: const(k, nodes) for k in ('is_outfall', 'area', 'pump_in', 'pump_out', 'hmax', 'hmin')},
+                **{k: const(k, links) for k in ('ehmax', 'pump', 'offset')})
+    local = _LocalEmulator(emul.conv, emul.resnet, emul.recurrent, SimpleNamespace(**args), precision=ly0.precision)
+    # parameters: row-local ones copied; NodeEdge gathered onto the local support (sparse) or sliced (dense (R, M))
+    dev = torch.device(device)
+    ti = lambda a: torch.as_tensor(a, dtype=torch.int64)
+    gp = dict(emul.named_parameters())
+    with torch.no_grad():
+        for name, p in local.named_parameters():
+            src = gp[name].detach().cpu()
+            if '.node_edge_n.' in name or '.node_edge_e.' in name:
+                rows_n = name.split('.')[-2] == 'node_edge_n'
+                if src.dim() == 1:
+                    src = src[ti(prob.inc_n_pos if rows_n else prob.inc_e_pos)]
+                else:
+                    src = src[ti(nodes)][:, ti(links)] if rows_n else src[ti(links)][:, ti(nodes)]
+            if tuple(src.shape) != tuple(p.shape):
+                raise ValueError('shard_emulator: parameter %s %r does not map onto the local %r' % (name, tuple(src.shape), tuple(p.shape)))
+            p.copy_(src)
+    local.requires_grad_(False)
+    local.to(dev)
+    # host-side facts of the WHOLE network (a part whose links are all pumped must not take the pump override on its own)
+    for flag in ('_has_offset', '_has_pump', '_has_link_pump', '_has_any_pump'):
+        setattr(local, flag, getattr(emul, flag))
+    if emul.act:
+        link, out_o, out_i = global_action_columns(emul)
+        local._edge_act_cols, local._node_act_cols = link[links], (out_o[nodes], out_i[nodes])
+    norms = {}
+    for k, t in emul._norms.items():
+        t = t.detach().cpu()
+        norms[k] = (t[:, ti(links)] if k == 'e' else t[:, ti(nodes)]).numpy()
+    local.set_norm(*(norms.get(k) for k in 'xbyre'))
+    return ShardedEmulator(local, prob, dev, group)
+
+
+class ShardedEmulator:
+    """One rank's share of a graph-sharded `Emulator` forward / `predict_tf` / `predict` (built by `shard_emulator`).
+
+    Inputs are the rank's LOCAL rows (own rows first, then halo rows) of the replicated global tensors (`scatter_inputs`);
+    actions `a` are the global (B, T, n_act) settings.  Schedule, L = n_sp_layer:
+      embeddings on all local rows (inputs are exact on halo rows: no exchange);
+      block 1 with an exchange after each layer but the last (L - 1, width d, S = B seq_in);
+      temporal stack 1, the last seq_out steps, ONE exchange of them (width H, S = B seq_out);
+      block 2 with L - 1 exchanges (its first layer reads the exact b / ae pieces); temporal stack 2 and heads (row-local);
+      post-processing: link gates (exact on own links: a link's from-node has the link's owner), ONE link-only exchange of
+      the gated flow column (`flow_rows`, edge_fusion only), the flow balance on the local incidence, node gates / pumped-
+      storage depth / constrain_tf (row-local);
+      predict_tf / predict: ONE exchange of the final (y, ey), so the returned local tensors are exact on ALL local rows
+      and can be fed back as the next chunk's input without another scatter (mpc.predict_horizon).
+    `forward` returns local tensors exact on OWN rows (`own`).  `exchange` / `flow_exchange` are attributes (defaults:
+    `HaloExchangeAll` over the plan's lists / over `flow_rows`); anything with the same `__call__(x, e)` may replace them."""
+
+    def __init__(self, local, prob, device, group=None):
+        self.local, self.prob, self.device = local, prob, torch.device(device)
+        self.exchange = HaloExchangeAll(prob, device, group)
+        self.flow_exchange = HaloExchangeAll(prob, device, group, rows=flow_rows(prob))
+        local.block1 = _ExchangedBlock(local.block1, lambda x, e: self.exchange(x, e), False)
+        local.block2 = _ExchangedBlock(local.block2, lambda x, e: self.exchange(x, e), True)
+        local._flow_exchange = lambda x, e: self.flow_exchange(x, e)
+        self.n_own_nodes, self.n_own_links = len(prob.own_nodes), len(prob.own_links)
+
+    # model facts read by callers such as mpc.predict_horizon
+    seq_in = property(lambda self: self.local.seq_in)
+    seq_out = property(lambda self: self.local.seq_out)
+    if_flood = property(lambda self: self.local.if_flood)
+    act = property(lambda self: self.local.act)
+
+    def get_edge_action(self, a, g=True):
+        """(B, T, n_local_links, 1): the global settings spread over the local links (global action columns)."""
+        return self.local.get_edge_action(a, g)
+
+    def scatter_inputs(self, X, B, E, AE=None):
+        """The local rows of replicated global inputs: X (B, T, N, C), B (B, T, N, b) node tensors, E (B, T, E, C), AE
+        (B, T, E, 1) link tensors (None passes through); own + halo rows are simply read."""
+        dev = X.device
+        ni = self.local._dev_index('scatter_nodes', self.prob.nodes, dev)
+        li = self.local._dev_index('scatter_links', self.prob.links, dev)
+        pick = lambda t, idx: None if t is None else t.index_select(2, idx).contiguous()
+        return pick(X, ni), pick(B, ni), pick(E, li), pick(AE, li)
+
+    def own(self, y, ey=None):
+        """The own rows of local node (..., n_local_nodes, C) / link tensors; one tensor in, one out."""
+        oy = y[..., :self.n_own_nodes, :]
+        return oy if ey is None else (oy, ey[..., :self.n_own_links, :])
+
+    @staticmethod
+    def _inference_only(*tensors):
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+            raise NotImplementedError('ShardedEmulator is inference only: no gradients across the cut')
+
+    def forward(self, X, B, E, AE=None):
+        """`Emulator.forward` on local rows: (B, T, n_local_nodes, n_out), (B, T, n_local_links, e_out), exact on own rows."""
+        self._inference_only(X, B, E, AE)
+        return self.local.forward(X, B, E, AE)
+
+    __call__ = forward
+
+    def predict_tf(self, states, b, a=None, edge_state=None):
+        """`Emulator.predict_tf` on local rows; the result is exact on ALL local rows."""
+        return self._predict(states, b, a, edge_state, False)
+
+    def predict(self, states, b, a=None, edge_state=None):
+        """`Emulator.predict` (NumPy-mode post-processing) on local rows; exact on ALL local rows."""
+        return self._predict(states, b, a, edge_state, True)
+
+    def _predict(self, states, b, a, edge_state, np_form):
+        self._inference_only(states, b, a, edge_state)
+        y, ey = self.local._predict(states, b, a, edge_state, np_form)
+        # one exchange of the final outputs, both pieces padded to one width
+        nb, T, cy, ce = y.shape[0], y.shape[1], y.shape[-1], ey.shape[-1]
+        F = max(cy, ce)
+        pad = lambda t, c: t if c == F else torch.cat([t, t.new_zeros(t.shape[:-1] + (F - c,))], dim=-1)
+        xs = pad(y, cy).reshape(nb * T, y.shape[2], F).contiguous()
+        es = pad(ey, ce).reshape(nb * T, ey.shape[2], F).contiguous()
+        xs, es = self.exchange(xs, es)
+        return xs.reshape(nb, T, -1, F)[..., :cy], es.reshape(nb, T, -1, F)[..., :ce]

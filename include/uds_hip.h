@@ -177,6 +177,23 @@ int uds_halo_pack(const float *x, int64_t n_x, const float *e, int64_t n_e, int6
 int uds_halo_unpack(const float *buf, int64_t S, int64_t F, const int32_t *idx_x, int64_t nx, const int32_t *idx_e,
                     int64_t ne, float *x, int64_t n_x, float *e, int64_t n_e, uds_stream_t stream);
 
+/* The messages of ALL P peers of one exchange in one launch each way (the whole-Emulator graph-sharded forward).
+ * idx_x (nx) / idx_e (ne) are the peers' row lists concatenated; peer q's rows are idx_x[off_x[q] .. off_x[q+1]) and
+ * idx_e[off_e[q] .. off_e[q+1]) (off_* int32 device arrays of P + 1 non-decreasing offsets, off_*[0] = 0, off_x[P] = nx,
+ * off_e[P] = ne; a peer may have no rows).  One buffer: peer q's message is the contiguous (S, nx_q + ne_q, F) block at
+ * float offset S * F * (off_x[q] + off_e[q]), node rows then link rows, as uds_halo_pack lays out one message.
+ *   pack_all:   every block filled from x (S, n_x, F) / e (S, n_e, F)
+ *   unpack_all: the inverse scatter (in place)
+ * Any F >= 1 (16-byte vector path when F % 4 == 0 and x, e, buf are 16-byte aligned, per-float otherwise); S <= 65535;
+ * idx_* are LOCAL row numbers < n_x / n_e (not checked on the device).  UDS_EINVAL on bad sizes or NULL arguments,
+ * UDS_EHIP when the launch fails. */
+int uds_halo_pack_all(const float *x, int64_t n_x, const float *e, int64_t n_e, int64_t S, int64_t F, const int32_t *idx_x,
+                      int64_t nx, const int32_t *idx_e, int64_t ne, const int32_t *off_x, const int32_t *off_e, int64_t P,
+                      float *buf, uds_stream_t stream);
+int uds_halo_unpack_all(const float *buf, int64_t S, int64_t F, const int32_t *idx_x, int64_t nx, const int32_t *idx_e,
+                        int64_t ne, const int32_t *off_x, const int32_t *off_e, int64_t P, float *x, int64_t n_x, float *e,
+                        int64_t n_e, uds_stream_t stream);
+
 /* Dense remainder of a TRAINED NodeEdge layer.  The reference's layer is `(w * inci + b) @ x` with w, b dense trainable
  * (R, M) matrices (emulator.py:34-45); on the incidence support that is the CSR aggregation of the fused kernel, off the
  * support it is `rest @ x`, rest = b with the support entries zeroed -- a true (R x M) x (M x S*h) GEMM.  Matrix cores,
