@@ -57,6 +57,10 @@ SYMBOLS = {
                                    _c_ptr, _c_ptr]),
     'uds_halo_unpack_all': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr,
                                      _c_i64, _c_ptr]),
+    'uds_halo_pack_clear_all': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr,
+                                         _c_i64, _c_ptr, _c_ptr]),
+    'uds_halo_accumulate_all': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr,
+                                         _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr]),
     'uds_remainder_packed_bytes': (_c_i64, [_c_i64, _c_i64]),
     'uds_remainder_pack': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr]),
     'uds_remainder_workspace_bytes': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
@@ -575,6 +579,39 @@ def halo_unpack_all(buf, x, e, idx_x, idx_e, off_x, off_e):
                                        _dev_i32(idx_e, 'idx_e') if ne else None, ne, _dev_i32(off_x, 'off_x'), _dev_i32(off_e, 'off_e'), P,
                                        _dev(x, 'x') if nx else None, n_x, _dev(e, 'e') if ne else None, e.shape[1], _stream()),
                'uds_halo_unpack_all')
+
+
+def halo_pack_clear_all(x, e, idx_x, idx_e, off_x, off_e):
+    """halo_pack_all, and every row it reads is then zeroed in x / e (in place), ONE launch (uds_halo_pack_clear_all): the
+    first half of the exchange's adjoint.  The rows listed across all peers must be distinct."""
+    lib = load()
+    P, nx, ne = _halo_all_args(x, e, idx_x, idx_e, off_x, off_e, 'halo_pack_clear_all')
+    S, n_x, F = x.shape
+    buf = torch.empty(S * (nx + ne) * F, device=x.device, dtype=torch.float32)
+    if buf.numel():
+        _check(lib.uds_halo_pack_clear_all(_dev(x, 'x') if nx else None, n_x, _dev(e, 'e') if ne else None, e.shape[1], S, F,
+                                           _dev_i32(idx_x, 'idx_x') if nx else None, nx, _dev_i32(idx_e, 'idx_e') if ne else None, ne,
+                                           _dev_i32(off_x, 'off_x'), _dev_i32(off_e, 'off_e'), P, _dev(buf, 'buf'), _stream()),
+               'uds_halo_pack_clear_all')
+    return buf
+
+
+def halo_accumulate_all(buf, x, e, off_x, off_e, tgt_x, tgt_e, ptr, src):
+    """x[:, tgt_x[t]] (then e[:, tgt_e[t - tx]]) += the message rows src[ptr[t]:ptr[t+1]] of `buf` (laid out by off_x / off_e
+    as halo_pack_all lays it out; rows numbered across peers), added in the listed order after the current value; in place,
+    ONE launch, no atomics (uds_halo_accumulate_all).  int32 device index tensors; any F >= 1."""
+    lib = load()
+    P, tx, te = _halo_all_args(x, e, tgt_x, tgt_e, off_x, off_e, 'halo_accumulate_all')
+    S, n_x, F = x.shape
+    n_src = int(src.numel())
+    if int(ptr.numel()) != tx + te + 1:
+        raise UdsError('halo_accumulate_all: ptr has %d entries for %d + %d targets' % (ptr.numel(), tx, te))
+    if S and tx + te:
+        _check(lib.uds_halo_accumulate_all(_dev(buf, 'buf') if n_src else None, S, F, _dev_i32(off_x, 'off_x'), _dev_i32(off_e, 'off_e'), P,
+                                           _dev_i32(tgt_x, 'tgt_x') if tx else None, tx, _dev_i32(tgt_e, 'tgt_e') if te else None, te,
+                                           _dev_i32(ptr, 'ptr'), _dev_i32(src, 'src') if n_src else None, n_src,
+                                           _dev(x, 'x') if tx else None, n_x, _dev(e, 'e') if te else None, e.shape[1], _stream()),
+               'uds_halo_accumulate_all')
 
 
 def remainder_pack(rest):

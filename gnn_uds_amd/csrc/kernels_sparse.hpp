@@ -588,6 +588,8 @@ inline hipError_t launch_halo_rows(const HaloArgs &a, bool pack, hipStream_t st)
 // S * F * r_q, so each peer's message stays one contiguous slice.
 //   PACK:   buf[S F r_q + (s n_q + j) F + f] = j < nx_q ? x[s, idx_x[off_x[q] + j], f] : e[s, idx_e[off_e[q] + j - nx_q], f]
 //   UNPACK: the inverse scatter.
+//   CLEAR (with PACK): every source element is zeroed after it is read -- the first half of the exchange's adjoint
+//   (the rows must be distinct across peers: each element is read and zeroed by one thread).
 // Grid (ceil(n_rows * W / 256), S); thread = (message row, W-th of a row): W = F / 4 float4 (VEC) or F floats.
 struct HaloAllArgs {
   float *x, *e, *buf;
@@ -596,7 +598,7 @@ struct HaloAllArgs {
   int n_rows, P, F, W;
 };
 
-template <bool PACK, bool VEC>
+template <bool PACK, bool VEC, bool CLEAR = false>
 __global__ __launch_bounds__(256) void k_halo_rows_all(HaloAllArgs a) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= (int64_t)a.n_rows * a.W) return;
@@ -614,11 +616,19 @@ __global__ __launch_bounds__(256) void k_halo_rows_all(HaloAllArgs a) {
   float *slot = a.buf + S * a.F * r0 + (s * n + j) * a.F;
   if (VEC) {
     float4 *rv = reinterpret_cast<float4 *>(row) + c, *sv = reinterpret_cast<float4 *>(slot) + c;
-    if (PACK) *sv = *rv;
-    else *rv = *sv;
+    if (PACK) {
+      *sv = *rv;
+      if (CLEAR) *rv = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      *rv = *sv;
+    }
   } else {
-    if (PACK) slot[c] = row[c];
-    else row[c] = slot[c];
+    if (PACK) {
+      slot[c] = row[c];
+      if (CLEAR) row[c] = 0.f;
+    } else {
+      row[c] = slot[c];
+    }
   }
 }
 
@@ -628,6 +638,67 @@ inline hipError_t launch_halo_rows_all(const HaloAllArgs &a, int S, bool pack, b
   else if (pack) hipLaunchKernelGGL((k_halo_rows_all<true, false>), grid, dim3(256), 0, st, a);
   else if (vec) hipLaunchKernelGGL((k_halo_rows_all<false, true>), grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL((k_halo_rows_all<false, false>), grid, dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+inline hipError_t launch_halo_pack_clear_all(const HaloAllArgs &a, int S, bool vec, hipStream_t st) {
+  const dim3 grid((unsigned)(((int64_t)a.n_rows * a.W + 255) / 256), (unsigned)S);
+  if (vec) hipLaunchKernelGGL((k_halo_rows_all<true, true, true>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((k_halo_rows_all<true, false, true>), grid, dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// The second half of the exchange's adjoint: every owner ADDS the gradients its peers return for its rows.  Targets are
+// numbered node rows first (t < tx: x row tgt_x[t], else e row tgt_e[t - tx]); target t sums the message rows
+// src[ptr[t] .. ptr[t+1]) -- numbered across peers as in HaloAllArgs, so row r lies in peer q's block with
+// r_q <= r < r_{q+1} -- in the order listed (ascending peer):
+//   row[s, :] = ((row[s, :] + m_0[s, :]) + m_1[s, :]) + ...
+// One thread per (target, W-th of a row) and snapshot: no two threads touch one element, no atomics -- the sum is the same
+// bits whatever the arrival order of the messages.  Grid (ceil(n_tgt * W / 256), S).
+struct HaloAccArgs {
+  const float *buf;
+  float *x, *e;
+  const int32_t *off_x, *off_e, *tgt_x, *tgt_e, *ptr, *src;
+  int64_t n_x, n_e;
+  int tx, n_tgt, P, F, W;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_halo_accumulate_all(HaloAccArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)a.n_tgt * a.W) return;
+  const int t = (int)(i / a.W), c = (int)(i % a.W);
+  const int64_t s = blockIdx.y, S = gridDim.y;
+  float *row = t < a.tx ? a.x + (s * a.n_x + a.tgt_x[t]) * a.F : a.e + (s * a.n_e + a.tgt_e[t - a.tx]) * a.F;
+  float4 acc4 = VEC ? reinterpret_cast<const float4 *>(row)[c] : make_float4(row[c], 0.f, 0.f, 0.f);
+  for (int k = a.ptr[t]; k < a.ptr[t + 1]; ++k) {
+    const int r = a.src[k];
+    int lo = 0, hi = a.P;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (a.off_x[mid] + a.off_e[mid] <= r) lo = mid;
+      else hi = mid;
+    }
+    const int r0 = a.off_x[lo] + a.off_e[lo], n = a.off_x[lo + 1] + a.off_e[lo + 1] - r0;
+    const float *slot = a.buf + S * a.F * r0 + (s * n + (r - r0)) * a.F;
+    if (VEC) {
+      const float4 m = reinterpret_cast<const float4 *>(slot)[c];
+      acc4.x += m.x;
+      acc4.y += m.y;
+      acc4.z += m.z;
+      acc4.w += m.w;
+    } else {
+      acc4.x += slot[c];
+    }
+  }
+  if (VEC) reinterpret_cast<float4 *>(row)[c] = acc4;
+  else row[c] = acc4.x;
+}
+
+inline hipError_t launch_halo_accumulate_all(const HaloAccArgs &a, int S, bool vec, hipStream_t st) {
+  const dim3 grid((unsigned)(((int64_t)a.n_tgt * a.W + 255) / 256), (unsigned)S);
+  if (vec) hipLaunchKernelGGL(k_halo_accumulate_all<true>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_halo_accumulate_all<false>, grid, dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

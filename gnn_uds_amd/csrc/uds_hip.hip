@@ -796,6 +796,42 @@ int uds_halo_unpack_all(const float *buf, int64_t S, int64_t F, const int32_t *i
                        stream);
 }
 
+int uds_halo_pack_clear_all(float *x, int64_t n_x, float *e, int64_t n_e, int64_t S, int64_t F, const int32_t *idx_x, int64_t nx,
+                            const int32_t *idx_e, int64_t ne, const int32_t *off_x, const int32_t *off_e, int64_t P, float *buf,
+                            uds_stream_t stream) {
+  const char *what = "uds_halo_pack_clear_all";
+  UDS_REQUIRE(S >= 0 && S <= 65535 && nx >= 0 && ne >= 0 && n_x >= 0 && n_e >= 0 && F >= 1 && P >= 1,
+              "%s: bad sizes (S=%lld nx=%lld ne=%lld F=%lld P=%lld; needs S <= 65535, F >= 1, P >= 1)", what, (long long)S, (long long)nx,
+              (long long)ne, (long long)F, (long long)P);
+  if (S == 0 || nx + ne == 0) return UDS_OK;
+  UDS_REQUIRE(buf && off_x && off_e && (nx == 0 || (x && idx_x)) && (ne == 0 || (e && idx_e)), "%s: NULL argument", what);
+  UDS_REQUIRE(nx + ne < INT32_MAX && P < INT32_MAX && F < INT32_MAX && (nx + ne) * F < (int64_t)INT32_MAX * 256, "%s: messages too large", what);
+  const bool vec = F % 4 == 0 && aligned16(buf) && aligned16(x) && aligned16(e);
+  uds::HaloAllArgs a{x, e, buf, idx_x, idx_e, off_x, off_e, n_x, n_e, (int)(nx + ne), (int)P, (int)F, (int)(vec ? F / 4 : F)};
+  hipError_t err = uds::launch_halo_pack_clear_all(a, (int)S, vec, static_cast<hipStream_t>(stream));
+  if (err != hipSuccess) return fail(UDS_EHIP, "%s: launch -> %s", what, hipGetErrorString(err));
+  return UDS_OK;
+}
+
+int uds_halo_accumulate_all(const float *buf, int64_t S, int64_t F, const int32_t *off_x, const int32_t *off_e, int64_t P,
+                            const int32_t *tgt_x, int64_t tx, const int32_t *tgt_e, int64_t te, const int32_t *ptr, const int32_t *src,
+                            int64_t n_src, float *x, int64_t n_x, float *e, int64_t n_e, uds_stream_t stream) {
+  const char *what = "uds_halo_accumulate_all";
+  UDS_REQUIRE(S >= 0 && S <= 65535 && tx >= 0 && te >= 0 && n_src >= 0 && n_x >= 0 && n_e >= 0 && F >= 1 && P >= 1,
+              "%s: bad sizes (S=%lld tx=%lld te=%lld n_src=%lld F=%lld P=%lld; needs S <= 65535, F >= 1, P >= 1)", what, (long long)S,
+              (long long)tx, (long long)te, (long long)n_src, (long long)F, (long long)P);
+  if (S == 0 || tx + te == 0) return UDS_OK;
+  UDS_REQUIRE(off_x && off_e && ptr && (n_src == 0 || (buf && src)) && (tx == 0 || (x && tgt_x)) && (te == 0 || (e && tgt_e)),
+              "%s: NULL argument", what);
+  UDS_REQUIRE(tx + te < INT32_MAX && n_src < INT32_MAX && P < INT32_MAX && F < INT32_MAX && (tx + te) * F < (int64_t)INT32_MAX * 256,
+              "%s: too many rows", what);
+  const bool vec = F % 4 == 0 && aligned16(buf) && aligned16(x) && aligned16(e);
+  uds::HaloAccArgs a{buf, x, e, off_x, off_e, tgt_x, tgt_e, ptr, src, n_x, n_e, (int)tx, (int)(tx + te), (int)P, (int)F, (int)(vec ? F / 4 : F)};
+  hipError_t err = uds::launch_halo_accumulate_all(a, (int)S, vec, static_cast<hipStream_t>(stream));
+  if (err != hipSuccess) return fail(UDS_EHIP, "%s: launch -> %s", what, hipGetErrorString(err));
+  return UDS_OK;
+}
+
 int uds_roll_update(const uds_csr_t *inc_n, const float *sign, const float *span_e, const float *mini_e, const float *scale_in,
                     const float *scale_out, const float *y, int64_t cy, const float *ey, int64_t ce, const float *b, int64_t B, int64_t so,
                     int64_t T, int flood, float *x, float *ex, float *preds, uds_stream_t stream) {

@@ -440,7 +440,12 @@ class HaloExchangeAll:
     S F (off_x[q] + off_e[q]) -- a plain slice for `batch_isend_irecv`.  Any row width F >= 1.
 
     rows: a subset of the plan's lists, a dict with any of 'send_nodes', 'send_links', 'recv_nodes', 'recv_links' (peer ->
-    LOCAL indices, as in LocalProblem); a list the dict does not name is empty (`flow_rows`).  None: the plan's lists."""
+    LOCAL indices, as in LocalProblem); a list the dict does not name is empty (`flow_rows`).  None: the plan's lists.
+
+    `adjoint` is the transpose of `__call__` (graph-sharded training): the roles of the lists swap, halo rows return their
+    gradient to the owner and keep none (uds_halo_pack_clear_all over the receive lists), owners add what comes back
+    (uds_halo_accumulate_all over the send lists, in ascending peer order, no atomics).  Both directions post their messages
+    through `transport`, the one method an in-process test transport overrides."""
 
     def __init__(self, prob, device, group=None, rows=None):
         self.prob, self.group = prob, group
@@ -471,6 +476,39 @@ class HaloExchangeAll:
                                   off_x32=t(off_x, torch.int32), off_e32=t(off_e, torch.int32))
             for k, q in enumerate(self.peers):
                 (self.n_send if side == 'send' else self.n_recv)[q] = (int(off_x[k] + off_e[k]), int(off_x[k + 1] + off_e[k + 1]))
+        # the adjoint zeroes the received rows after packing them and adds the returned messages into the sent rows: the
+        # received rows must be distinct across peers, the sent rows distinct within a peer (checked once, here)
+        for k in ('recv_nodes', 'recv_links'):
+            allrows = np.concatenate([lists[k][i] for i in keep]) if keep else np.zeros(0, np.int64)
+            if len(np.unique(allrows)) != len(allrows):
+                raise ValueError('HaloExchangeAll: %s rows repeat across peers' % k)
+        for k in ('send_nodes', 'send_links'):
+            if any(len(np.unique(lists[k][i])) != len(lists[k][i]) for i in keep):
+                raise ValueError('HaloExchangeAll: %s rows repeat within a peer' % k)
+        self.dev['acc'] = self._accumulate_plan(t)
+        self.adjoint_calls = 0
+
+    def _accumulate_plan(self, t):
+        """Targets of the adjoint's accumulation -- the distinct own rows in the send lists, node rows first -- and the CSR of
+        the message rows (numbered across peers, as the buffer) that each one adds, in ascending peer order."""
+        d = self.dev['send']
+        off_x, off_e = d['off_x'], d['off_e']
+        P = len(self.peers)
+        sx, se = d['idx_x'].cpu().numpy(), d['idx_e'].cpu().numpy()
+        peer_x = np.repeat(np.arange(P), np.diff(off_x)).astype(np.int64)
+        peer_e = np.repeat(np.arange(P), np.diff(off_e)).astype(np.int64)
+        msg_x = np.arange(len(sx), dtype=np.int64) + off_e[peer_x]          # message row of send-list entry k: r_q + j
+        msg_e = np.arange(len(se), dtype=np.int64) + off_x[peer_e + 1]
+        tgts, ptr, src = [], [0], []
+        for rows, msg in ((sx, msg_x), (se, msg_e)):
+            o = np.argsort(rows, kind='stable')                              # entries are in peer order: stable keeps it
+            tgt, cnt = np.unique(rows[o], return_counts=True)
+            tgts.append(tgt)
+            ptr.extend((ptr[-1] + np.cumsum(cnt)).tolist())
+            src.append(msg[o])
+        tgt_x, tgt_e, ptr, src = tgts[0], tgts[1], np.asarray(ptr, np.int64), np.concatenate(src)
+        return dict(tgt_x=t(tgt_x, torch.int64), tgt_e=t(tgt_e, torch.int64), ptr=ptr, src=src,
+                    tgt_x32=t(tgt_x, torch.int32), tgt_e32=t(tgt_e, torch.int32), ptr32=t(ptr, torch.int32), src32=t(src, torch.int32))
 
     def rows(self, side):
         """(node rows, link rows) of all messages of `side` ('send' / 'recv'), int64 on the device, peers concatenated."""
@@ -506,10 +544,55 @@ class HaloExchangeAll:
             x.index_copy_(1, d['idx_x'][int(d['off_x'][k]):int(d['off_x'][k + 1])], msg[:, :nx_])
             e.index_copy_(1, d['idx_e'][int(d['off_e'][k]):int(d['off_e'][k + 1])], msg[:, nx_:])
 
+    def pack_clear(self, gx, ge):
+        """The adjoint's outgoing messages: the RECEIVE lists' rows packed as `unpack` reads them, each row then zeroed (in
+        place; one launch on the GPU)."""
+        d = self.dev['recv']
+        if gx.is_cuda:
+            from . import _lib
+            return _lib.halo_pack_clear_all(gx, ge, d['idx_x32'], d['idx_e32'], d['off_x32'], d['off_e32'])
+        parts = []
+        for k in range(len(self.peers)):
+            sx = d['idx_x'][int(d['off_x'][k]):int(d['off_x'][k + 1])]
+            se = d['idx_e'][int(d['off_e'][k]):int(d['off_e'][k + 1])]
+            parts.append(torch.cat([gx.index_select(1, sx), ge.index_select(1, se)], dim=1).reshape(-1))
+        gx.index_fill_(1, d['idx_x'], 0)
+        ge.index_fill_(1, d['idx_e'], 0)
+        return torch.cat(parts) if parts else ge.new_empty(0)
+
+    def accumulate(self, buf, gx, ge):
+        """Add every returned message (laid out as the forward SEND buffer) into the sent rows, in place: the current value
+        first, then the peers in ascending order (one launch on the GPU, no atomics)."""
+        d, a = self.dev['send'], self.dev['acc']
+        if gx.is_cuda:
+            from . import _lib
+            _lib.halo_accumulate_all(buf, gx, ge, d['off_x32'], d['off_e32'], a['tgt_x32'], a['tgt_e32'], a['ptr32'], a['src32'])
+            return
+        S, F = ge.shape[0], ge.shape[-1]        # CPU tensors (gloo): one index_add_ per peer and kind, each row added once
+        for k in range(len(self.peers)):
+            r0, r1 = int(d['off_x'][k] + d['off_e'][k]), int(d['off_x'][k + 1] + d['off_e'][k + 1])
+            nx_ = int(d['off_x'][k + 1] - d['off_x'][k])
+            msg = buf[S * F * r0:S * F * r1].reshape(S, r1 - r0, F)
+            gx.index_add_(1, d['idx_x'][int(d['off_x'][k]):int(d['off_x'][k + 1])], msg[:, :nx_])
+            ge.index_add_(1, d['idx_e'][int(d['off_e'][k]):int(d['off_e'][k + 1])], msg[:, nx_:])
+
     def message(self, buf, q, side, S, F):
         """Peer q's slice of a send / receive buffer."""
         r0, r1 = (self.n_send if side == 'send' else self.n_recv)[q]
         return buf[S * F * r0:S * F * r1]
+
+    def transport(self, msgs):
+        """Move one exchange's messages: msgs lists (peer, outgoing slice or None, incoming slice or None) in ascending peer
+        order; grouped isend / irecv (ncclSend / ncclRecv on RCCL), waited for on the current stream."""
+        ops = []
+        for q, out, inc in msgs:
+            if inc is not None:
+                ops.append(dist.P2POp(dist.irecv, inc, q, self.group))
+            if out is not None:
+                ops.append(dist.P2POp(dist.isend, out, q, self.group))
+        if ops:
+            for w in dist.batch_isend_irecv(ops):
+                w.wait()
 
     def __call__(self, x, e):
         """x (S, n_local_nodes, F) or None (a link-only exchange), e (S, n_local_links, F): overwrite the halo rows with the
@@ -522,17 +605,29 @@ class HaloExchangeAll:
         sbuf = self.pack(x, e)
         n_recv = self.n_recv[self.peers[-1]][1]
         rbuf = torch.empty(S * n_recv * F, device=e.device, dtype=e.dtype)
-        ops = []
-        for q in self.peers:
-            if self.n_recv[q][1] > self.n_recv[q][0]:
-                ops.append(dist.P2POp(dist.irecv, self.message(rbuf, q, 'recv', S, F), q, self.group))
-            if self.n_send[q][1] > self.n_send[q][0]:
-                ops.append(dist.P2POp(dist.isend, self.message(sbuf, q, 'send', S, F), q, self.group))
-        if ops:
-            for w in dist.batch_isend_irecv(ops):
-                w.wait()
+        some = lambda n, buf, q, side: self.message(buf, q, side, S, F) if n[q][1] > n[q][0] else None
+        self.transport([(q, some(self.n_send, sbuf, q, 'send'), some(self.n_recv, rbuf, q, 'recv')) for q in self.peers])
         self.unpack(rbuf, x, e)
         return x, e
+
+    def adjoint(self, gx, ge):
+        """The transpose of `__call__`, in place on gradients shaped like its x (or None, link-only) and e: the gradient of
+        every halo row the exchange overwrote goes to its owner and is zeroed here; every own row a peer holds as halo adds
+        that peer's message.  The message to peer q is this rank's receive block from q; it lands in a buffer laid out as
+        the forward send buffer.  Summed over ranks, <E(x), g> = <x, E^T(g)>."""
+        if gx is None:
+            gx = ge.new_empty((ge.shape[0], 0, ge.shape[-1]))
+        self.adjoint_calls += 1
+        if not self.peers:
+            return gx, ge
+        S, F = ge.shape[0], ge.shape[-1]
+        sbuf = self.pack_clear(gx, ge)
+        n_back = self.n_send[self.peers[-1]][1]
+        rbuf = torch.empty(S * n_back * F, device=ge.device, dtype=ge.dtype)
+        some = lambda n, buf, q, side: self.message(buf, q, side, S, F) if n[q][1] > n[q][0] else None
+        self.transport([(q, some(self.n_recv, sbuf, q, 'recv'), some(self.n_send, rbuf, q, 'send')) for q in self.peers])
+        self.accumulate(rbuf, gx, ge)
+        return gx, ge
 
 
 def _refuse_unsharded_configuration(emul):
@@ -597,7 +692,7 @@ class _LocalEmulator(Emulator):
 
     def _flow_balance(self, flow):
         f = flow.reshape(-1, self.n_edge, 1).contiguous()
-        self._flow_exchange(None, f)
+        _, f = self._flow_exchange(None, f)        # in place; out of place (a new leaf) while a training step records its tape
         return super()._flow_balance(f.reshape(flow.shape))
 
 
@@ -617,8 +712,9 @@ def shard_emulator(emul, prob, device, group=None):
     """The `ShardedEmulator` of one rank: an `Emulator` on `prob.graph` (the `args.graph` CSR path, local rows own first)
     carrying the global model's state -- row-local parameters copied, NodeEdge parameters gathered onto the local support,
     per-row constants and norms sliced to the local rows, the `_has_*` flags and the action columns of the GLOBAL model.
-    Inference only.  Refuses (NotImplementedError / ValueError) what has no bounded halo or is not built: conv=False, a conv
-    other than GAT, graph_base, use_adj, dropout, and a NodeEdge bias that is non-zero off the incidence support."""
+    `emul` stays the rank's global replica (training: `ShardedEmulator.loss_and_grad` / `fit_eval`).  Refuses
+    (NotImplementedError / ValueError) what has no bounded halo or is not built: conv=False, a conv other than GAT,
+    graph_base, use_adj, dropout, and a NodeEdge bias that is non-zero off the incidence support."""
     why = _refuse_unsharded_configuration(emul)
     if why is not None:
         raise why[0]('shard_emulator: ' + why[1])
@@ -668,7 +764,7 @@ def shard_emulator(emul, prob, device, group=None):
         t = t.detach().cpu()
         norms[k] = (t[:, ti(links)] if k == 'e' else t[:, ti(nodes)]).numpy()
     local.set_norm(*(norms.get(k) for k in 'xbyre'))
-    return ShardedEmulator(local, prob, dev, group)
+    return ShardedEmulator(local, prob, dev, group, global_model=emul)
 
 
 class ShardedEmulator:
@@ -686,15 +782,24 @@ class ShardedEmulator:
       predict_tf / predict: ONE exchange of the final (y, ey), so the returned local tensors are exact on ALL local rows
       and can be fed back as the next chunk's input without another scatter (mpc.predict_horizon).
     `forward` returns local tensors exact on OWN rows (`own`).  `exchange` / `flow_exchange` are attributes (defaults:
-    `HaloExchangeAll` over the plan's lists / over `flow_rows`); anything with the same `__call__(x, e)` may replace them."""
+    `HaloExchangeAll` over the plan's lists / over `flow_rows`); anything with the same `__call__(x, e)` may replace them
+    (training also needs their `adjoint(gx, ge)`).
 
-    def __init__(self, local, prob, device, group=None):
+    Training (`loss_and_grad`, `fit_eval`; DESIGN.md section 8, "training across the cut"): `global_model` is this rank's
+    replica of the whole Emulator, which holds the authoritative parameters and the Adam state.  The forward records every
+    exchange on a tape, out of place; the reverse schedule runs the adjoint exchanges on the calling thread; the loss is
+    summed over own rows and divided by the global sample counts; the gradients go into the global layout and are summed over
+    the ranks by `reduce` -- the one hook every cross-rank reduction goes through."""
+
+    def __init__(self, local, prob, device, group=None, global_model=None):
         self.local, self.prob, self.device = local, prob, torch.device(device)
+        self.group, self.global_model = group, global_model
         self.exchange = HaloExchangeAll(prob, device, group)
         self.flow_exchange = HaloExchangeAll(prob, device, group, rows=flow_rows(prob))
-        local.block1 = _ExchangedBlock(local.block1, lambda x, e: self.exchange(x, e), False)
-        local.block2 = _ExchangedBlock(local.block2, lambda x, e: self.exchange(x, e), True)
-        local._flow_exchange = lambda x, e: self.flow_exchange(x, e)
+        self._tape = None                     # a list while a training forward runs: (exchange, pre, post) per exchange
+        local.block1 = _ExchangedBlock(local.block1, lambda x, e: self._exchanged(self.exchange, x, e), False)
+        local.block2 = _ExchangedBlock(local.block2, lambda x, e: self._exchanged(self.exchange, x, e), True)
+        local._flow_exchange = lambda x, e: self._exchanged(self.flow_exchange, x, e)
         self.n_own_nodes, self.n_own_links = len(prob.own_nodes), len(prob.own_links)
 
     # model facts read by callers such as mpc.predict_horizon
@@ -752,3 +857,225 @@ class ShardedEmulator:
         es = pad(ey, ce).reshape(nb * T, ey.shape[2], F).contiguous()
         xs, es = self.exchange(xs, es)
         return xs.reshape(nb, T, -1, F)[..., :cy], es.reshape(nb, T, -1, F)[..., :ce]
+
+    # ------------------------------------------------------------------ training across the cut
+    def _exchanged(self, ex, x, e):
+        """An exchange of the forward.  Inference: in place, `ex(x, e)`.  While a training step records its tape: out of place
+        -- the segment outputs `pre` stay in the autograd graph, the exchange writes into detached copies `post` that become
+        new leaves, and (ex, pre, post) goes on the tape for the reverse schedule."""
+        if self._tape is None:
+            return ex(x, e)
+        px = None if x is None else x.detach().clone()
+        pe = e.detach().clone()
+        ex(px, pe)
+        post = tuple(None if t is None else t.requires_grad_() for t in (px, pe))
+        self._tape.append((ex, (x, e), post))
+        return post
+
+    def _reverse(self, loss):
+        """The reverse schedule, on the calling thread (never inside the autograd engine, whose one worker thread per device
+        would wait on a peer's message while holding every rank's backward): the loss first, then every tape entry from the
+        last to the first -- adjoint exchange of the gradient that reached `post`, then on through `pre`.  In reverse order
+        `post_k` has received all of its gradient (from the loss and from the later `pre_j`) when its turn comes; the graph is
+        retained until the last call because the residual links the first segment straight to the heads."""
+        tape, self._tape = self._tape, None
+        loss.backward(retain_graph=bool(tape))
+        for k in range(len(tape) - 1, -1, -1):
+            ex, pre, post = tape[k]
+            g = [None if t is None else (t.grad if t.grad is not None else torch.zeros_like(t)).contiguous() for t in post]
+            ex.adjoint(g[0], g[1])
+            outs = [(p, gp) for p, gp in zip(pre, g) if p is not None and p.requires_grad]
+            if outs:
+                torch.autograd.backward([p for p, _ in outs], [gp for _, gp in outs], retain_graph=k > 0)
+        del tape
+
+    def reduce(self, t):
+        """Sum `t` over the ranks (in place where the backend allows; returns the summed tensor): `dist.all_reduce` SUM over
+        `group` when torch.distributed is initialised with more than one rank, else `t`.  Every cross-rank reduction of a
+        training step goes through here -- the loss parts with the non-finite flag, then the gradient buffer -- so an
+        in-process test may replace it with a fixed-rank-order sum."""
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            if dist.get_backend(self.group) == 'gloo' and t.is_cuda:
+                c = t.cpu()
+                dist.all_reduce(c, op=dist.ReduceOp.SUM, group=self.group)
+                return c.to(t.device)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t
+
+    def _check_trainable(self):
+        g = self.global_model
+        if g is None:
+            raise ValueError('ShardedEmulator training needs the global model replica (build it with shard_emulator)')
+        if g.gradnorm:
+            raise NotImplementedError('sharded training without GradNorm: its task weights need per-task gradient norms at a '
+                                      'shared layer, not built across the cut')
+        if g.roll:
+            raise NotImplementedError('sharded training with roll=%d: fed-back chunks would need the output exchange on the tape' % g.roll)
+        if g.if_flood and g.balance:
+            raise NotImplementedError('if_flood with balance: the reference leaves fl_loss undefined here (emulator.py:466,473)')
+        for name, p in g.named_parameters():
+            if ('.node_edge_n.' in name or '.node_edge_e.' in name) and p.dim() != 1:
+                raise ValueError('sharded training needs sparse NodeEdge parameters (sparse_params=True): %s is a dense %r -- the '
+                                 "reference's dense bias trains OFF the incidence support, every node then depends on every link and "
+                                 'no halo of bounded radius exists' % (name, tuple(p.shape)))
+
+    def own_loss_weights(self, device):
+        """nwei / ewei / poswei of the OWN rows, sliced from the GLOBAL model's `_loss_setup` (its head-range reweighting uses
+        statistics of all nodes, which a part cannot recompute)."""
+        hit = getattr(self, '_lw_own', None)
+        if hit is None or hit[0] != device:
+            lw = self.global_model._loss_setup(device)
+            ni = torch.as_tensor(self.prob.own_nodes, dtype=torch.int64, device=device)
+            li = torch.as_tensor(self.prob.own_links, dtype=torch.int64, device=device)
+            hit = self._lw_own = (device, dict(nwei=lw['nwei'].index_select(0, ni), ewei=lw['ewei'].index_select(0, li),
+                                               poswei=lw['poswei'].index_select(0, ni)))
+        return hit[1]
+
+    def loss_parts(self, y, b, preds, ey, edge_preds):
+        """This rank's share of [node_loss, (flood_loss,) edge_loss] of `Emulator.fit_eval`: the per-sample terms of the OWN
+        rows summed and divided by the GLOBAL sample count (B T N for the node terms, B T E for the link term), so that the sum
+        over ranks is the whole-network loss.  Local tensors (own rows first)."""
+        g, lc = self.global_model, self.local
+        lw = self.own_loss_weights(preds.device)
+        no, lo = self.n_own_nodes, self.n_own_links
+        nb, T = preds.shape[0], preds.shape[1]
+        cn, ce = float(nb * T * g.n_node), float(nb * T * g.n_edge)
+        mse = lambda t, p, w=None: (((p - t) ** 2).mean(dim=-1) * (1.0 if w is None else w)).sum()
+        if g.balance:
+            q_w, pr = lc.constrain_tf(lc.normalize(preds, 'y', True), lc.normalize(b, 'b', True)[..., :1])
+            q_w = (q_w / lc._norm('y', preds.device)[0, :, -1]).unsqueeze(-1)
+            pr = lc.normalize(pr, 'y').clamp(0, 1)
+            true = torch.cat([y[..., :3], y[..., -1:]], dim=-1)[..., :no, :]
+            node = mse(true * lw['nwei'], torch.cat([pr[..., :3], q_w], dim=-1)[..., :no, :] * lw['nwei']) / cn
+        else:
+            node = mse(y[..., :no, :3] * lw['nwei'], preds[..., :no, :3] * lw['nwei']) / cn
+        parts = [node]
+        if g.if_flood and not g.balance:
+            yo = y[..., :no, :]
+            weight = lw['poswei'] * yo[..., -2] + lw['nwei'][:, -1] * (1 - yo[..., -2])
+            p = preds[..., :no, -1:].clamp(1e-7, 1 - 1e-7)
+            t = yo[..., -2:-1]
+            per = -(t * torch.log(p) + (1 - t) * torch.log(1 - p)).mean(dim=-1)
+            parts.append((per * weight).sum() / cn)
+        parts.append(mse(ey[..., :lo, :], edge_preds[..., :lo, :], lw['ewei']) / ce)
+        return parts
+
+    def _reduced_losses(self, parts, flag=None):
+        vec = torch.stack([p.detach().float() for p in parts] + ([] if flag is None else [flag]))
+        vec = self.reduce(vec)
+        return [vec[i] for i in range(len(parts))], (None if flag is None else float(vec[-1]))
+
+    def _global_layout(self):
+        if getattr(self, '_layout', None) is None:
+            lay, off = {}, 0
+            for name, p in self.global_model.named_parameters():
+                lay[name] = (off, tuple(p.shape))
+                off += p.numel()
+            pos = {True: torch.as_tensor(self.prob.inc_n_pos, dtype=torch.int64, device=self.device),
+                   False: torch.as_tensor(self.prob.inc_e_pos, dtype=torch.int64, device=self.device)}
+            self._layout = (lay, off, pos)
+        return self._layout
+
+    @staticmethod
+    def _global_name(name):
+        """The global model's name of a local parameter (the local spatial blocks are wrapped in `_ExchangedBlock`)."""
+        for b in ('block1', 'block2'):
+            if name.startswith(b + '.block.'):
+                return b + name[len(b) + 6:]
+        return name
+
+    @staticmethod
+    def _support_rows(name):
+        """None for a row-local parameter, else True / False: a sparse NodeEdge parameter on the node / link rows."""
+        if '.node_edge_n.' in name or '.node_edge_e.' in name:
+            return name.split('.')[-2] == 'node_edge_n'
+        return None
+
+    def loss_and_grad(self, x, a, b, y, ex, ey):
+        """The whole-network loss and gradient of one `fit_eval` step, computed on this rank's part.  Local rows of NORMALISED
+        tensors: x, b, ex as `scatter_inputs` gives them, y (B, T, n_local_nodes, C), ey (B, T, n_local_links, C) picked the
+        same way; a the global (B, T, n_act) settings.  Returns (losses, grads): `fit_eval`'s list of 0-d tensors with the
+        GLOBAL values, and {global parameter name: gradient summed over the ranks}; every rank returns the same."""
+        self._check_trainable()
+        lc = self.local
+        params = [(self._global_name(n), p) for n, p in lc.named_parameters()]
+        for _, p in params:
+            p.grad = None
+            p.requires_grad_(True)
+        self._tape = []
+        try:
+            with torch.enable_grad():
+                ae = lc.get_edge_action(a, True) if lc.act else None
+                preds, edge_preds = lc._model(x, a, b, ex, ae, None, True)
+                parts = self.loss_parts(y, b, preds, ey, edge_preds)
+                loss = sum(parts[1:], parts[0])
+                losses, bad = self._reduced_losses(parts, (~torch.isfinite(loss.detach())).float())
+                if bad > 0:                        # decided on all ranks together: all raise, none waits in an exchange
+                    raise FloatingPointError('Loss contains NaN or Inf values.')
+                self._reverse(loss)
+        finally:
+            self._tape = None
+            for _, p in params:
+                p.requires_grad_(False)
+        lay, total, pos = self._global_layout()
+        flat = torch.zeros(total, dtype=torch.float32, device=self.device)
+        for name, p in params:
+            if p.grad is None:
+                continue
+            off, shape = lay[name]
+            n = 1
+            for v in shape:
+                n *= v
+            rows = self._support_rows(name)
+            g = p.grad.reshape(-1).float()
+            if rows is None:
+                flat[off:off + n] = g
+            else:                               # local support entries map to distinct global entries
+                flat[off:off + n].index_copy_(0, pos[rows], g)
+            p.grad = None
+        flat = self.reduce(flat)
+        grads = {}
+        for name, (off, shape) in lay.items():
+            n = 1
+            for v in shape:
+                n *= v
+            grads[name] = flat[off:off + n].view(shape)
+        return losses, grads
+
+    def fit_eval(self, x, a, b, y, ex, ey, fit=True):
+        """`Emulator.fit_eval` on a graph-sharded network (same tensors as `loss_and_grad`).  fit=True: the summed gradient
+        steps the global replica's KerasAdam (per-variable clipnorm = 1 needs the whole gradient), then the local parameters
+        are refreshed in place from it; the replicas stay the same bits on every rank.  fit=False: evaluation only.
+        Returns the global [node_loss, (flood_loss,) edge_loss] as 0-d tensors."""
+        self._check_trainable()
+        if not fit:
+            with torch.no_grad():
+                lc = self.local
+                ae = lc.get_edge_action(a, True) if lc.act else None
+                preds, edge_preds = lc._model(x, a, b, ex, ae, None, False)
+                return self._reduced_losses(self.loss_parts(y, b, preds, ey, edge_preds))[0]
+        losses, grads = self.loss_and_grad(x, a, b, y, ex, ey)
+        g = self.global_model
+        gparams = list(g.named_parameters())
+        for name, p in gparams:
+            p.grad = grads[name].to(p.device)
+        if g._optimizer is None:
+            from .emulator import KerasAdam
+            g._optimizer = KerasAdam([p for _, p in gparams], g.learning_rate, clipnorm=1.0)
+        g._optimizer.step()
+        for _, p in gparams:
+            p.grad = None
+        self.refresh()
+        return losses
+
+    @torch.no_grad()
+    def refresh(self):
+        """Copy the global replica's parameters into the local ones, in place (`copy_`: the versioned caches of packed
+        weights and support values see the change)."""
+        gp = dict(self.global_model.named_parameters())
+        _, _, pos = self._global_layout()
+        for name, p in self.local.named_parameters():
+            name = self._global_name(name)
+            src = gp[name].detach().to(p.device)
+            rows = self._support_rows(name)
+            p.copy_(src if rows is None else src.index_select(0, pos[rows].to(p.device)))

@@ -194,6 +194,28 @@ int uds_halo_unpack_all(const float *buf, int64_t S, int64_t F, const int32_t *i
                         int64_t ne, const int32_t *off_x, const int32_t *off_e, int64_t P, float *x, int64_t n_x, float *e,
                         int64_t n_e, uds_stream_t stream);
 
+/* The adjoint of uds_halo_unpack_all (gradients across the node cut, graph-sharded training), in two launches.
+ *   pack_clear_all:  as uds_halo_pack_all (same arguments, same buffer layout), and every source element is set to 0
+ *                    after it is read -- a halo row whose value the exchange overwrote returns its gradient to the owner
+ *                    and keeps none.  The rows listed across all peers must be distinct (not checked on the device).
+ *   accumulate_all:  the owner ADDS what its peers returned.  buf is laid out by off_x / off_e (P + 1 offsets) as
+ *                    uds_halo_pack_all lays it out; message rows are numbered across peers, peer q's rows
+ *                    off_x[q] + off_e[q] + j, node rows first.  Targets: tx rows tgt_x of x then te rows tgt_e of e,
+ *                    distinct; target t (node targets numbered first) adds the message rows src[ptr[t] .. ptr[t+1])
+ *                    (ptr: tx + te + 1 offsets, n_src = ptr[tx + te]) in the listed order, ascending peer:
+ *                      row[s, :] = ((row[s, :] + m_0[s, :]) + m_1[s, :]) + ...
+ *                    No atomics: the result is bitwise reproducible and independent of message arrival order.
+ * x (S, n_x, F), e (S, n_e, F); any F >= 1 (16-byte vector path when F % 4 == 0 and x, e, buf are 16-byte aligned,
+ * per-float otherwise); S <= 65535; all int32 arrays are on the device and their rows are not checked there.
+ * UDS_EINVAL on bad sizes or NULL arguments, UDS_EHIP when the launch fails. */
+int uds_halo_pack_clear_all(float *x, int64_t n_x, float *e, int64_t n_e, int64_t S, int64_t F, const int32_t *idx_x, int64_t nx,
+                            const int32_t *idx_e, int64_t ne, const int32_t *off_x, const int32_t *off_e, int64_t P, float *buf,
+                            uds_stream_t stream);
+int uds_halo_accumulate_all(const float *buf, int64_t S, int64_t F, const int32_t *off_x, const int32_t *off_e, int64_t P,
+                            const int32_t *tgt_x, int64_t tx, const int32_t *tgt_e, int64_t te, const int32_t *ptr,
+                            const int32_t *src, int64_t n_src, float *x, int64_t n_x, float *e, int64_t n_e,
+                            uds_stream_t stream);
+
 /* Dense remainder of a TRAINED NodeEdge layer.  The reference's layer is `(w * inci + b) @ x` with w, b dense trainable
  * (R, M) matrices (emulator.py:34-45); on the incidence support that is the CSR aggregation of the fused kernel, off the
  * support it is `rest @ x`, rest = b with the support entries zeroed -- a true (R x M) x (M x S*h) GEMM.  Matrix cores,
