@@ -51,6 +51,9 @@ SYMBOLS = {
     'uds_gat_aggregate_masked': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
     'uds_gat_aggregate_coef': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
     'uds_diffusion_forward': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
+    'uds_diffusion_backward_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    'uds_diffusion_backward': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
+                                        _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     'uds_halo_pack': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr]),
     'uds_halo_unpack': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr]),
     'uds_halo_pack_all': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_i64,
@@ -515,6 +518,29 @@ def diffusion_forward(csr, vals, c0, r, tot, act='tanh'):
         _check(lib.uds_diffusion_forward(csr.ptr, _dev(vals, 'vals'), _dev(c0, 'c0'), _dev(r, 'r'), _dev(tot, 'tot'), S, C, ACT[act],
                                          _dev(out, 'out'), _stream()), 'uds_diffusion_forward')
     return out
+
+
+def diffusion_backward(csr, a, vals, c0, r, tot, y, gy, K1, act='tanh'):
+    """(dr (S, n_cols), dtheta (C, K1)) of diffusion_forward's out = y given dL/dout = gy: dr folds in the tot term, dtheta is
+    the gradient of the (C, K1) coefficient kernel; `a` (nnz,) = the filter's values on the support (uds_diffusion_backward)."""
+    lib = load()
+    S, C = r.shape[0], vals.shape[1]
+    if (tuple(vals.shape) != (csr.nnz, C) or tuple(a.shape) != (csr.nnz,) or tuple(c0.shape) != (C,) or tuple(r.shape) != (S, csr.n_cols)
+            or tuple(tot.shape) != (S,) or tuple(y.shape) != (S, csr.n_rows, C) or tuple(gy.shape) != (S, csr.n_rows, C)):
+        raise UdsError('diffusion_backward: a %r vals %r c0 %r r %r tot %r y %r gy %r for a %d x %d pattern with %d entries'
+                       % (tuple(a.shape), tuple(vals.shape), tuple(c0.shape), tuple(r.shape), tuple(tot.shape), tuple(y.shape),
+                          tuple(gy.shape), csr.n_rows, csr.n_cols, csr.nnz))
+    nws = lib.uds_diffusion_backward_workspace_floats(csr.n_rows, S, C, K1)
+    if nws < 0:
+        raise UdsError('diffusion_backward: C=%d K1=%d not taken (C %% 4 == 0, C <= 256, 1 <= K1 <= 16)' % (C, K1))
+    ht, perm = csr.transposed(r.device)
+    ws = torch.empty(max(int(nws), 4), device=r.device, dtype=torch.float32)
+    dr = torch.empty((S, csr.n_cols), device=r.device, dtype=torch.float32)
+    dtheta = torch.empty((C, K1), device=r.device, dtype=torch.float32)
+    _check(lib.uds_diffusion_backward(csr.ptr, ht.ptr, _dev_i32(perm, 'perm_t'), _dev(a, 'a'), _dev(vals, 'vals'), _dev(c0, 'c0'),
+                                      _dev(r, 'r'), _dev(tot, 'tot'), _dev(y, 'y'), _dev(gy, 'gy'), S, C, K1, ACT[act], ws.data_ptr(),
+                                      _dev(dr, 'dr'), _dev(dtheta, 'dtheta'), _stream()), 'uds_diffusion_backward')
+    return dr, dtheta
 
 
 def halo_pack(x, e, idx_x, idx_e):

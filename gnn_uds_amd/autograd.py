@@ -7,6 +7,7 @@ operator of the forward carries its own backward, so `loss.backward()` on an `Em
     Conv1DFn       causal dilated Conv1D           dX = the same kernels looking AHEAD (dilation < 0) with transposed taps
     SpmmFn         NodeEdge on its support / GCN   dX = spmm on the transposed pattern, dval = uds_csr_sddmm
     GatFn          MixedGAT(GATConv)               uds_gat_backward (softmax / leaky-relu / aggregation), then Dense rules
+    DiffusionFn    DiffusionConv on its support    uds_diffusion_backward: d r (transposed pattern) and d kernel, 3 launches
     CumsumActFn    relu(cumsum_T(x) + res)         reverse cumulative sum
     FlowBalanceFn  post_proc_tf incidence sums     gather along the link end nodes
     SpatialLayerFn the fused spatial layer forward, backward through the unfused chain above (intermediates recomputed)
@@ -289,6 +290,31 @@ class GatFn(torch.autograd.Function):
         if ctx.has_bias and ctx.needs_input_grad[5]:
             db = g.reshape(-1, d).sum(0)
         return dxa, dxb, dk, das, dan, db, None, None, None, None
+
+
+class DiffusionFn(torch.autograd.Function):
+    """DiffusionConv from the feature sums r = x.sum(-1) (S, n_cols): out = act(c0 tot + sum_p vals[p] r[col p]) on the CSR
+    support (uds_diffusion_forward, the inference kernel).  `kernel` (C, K1) is an input only for its gradient: vals / c0 are
+    its values prepared by the layer, `a` the filter's support values.  Backward: uds_diffusion_backward from the saved output
+    -- d r (the tot term folded in) and d kernel, three launches, no host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, r, kernel, handle, a, vals, c0, act):
+        r = r.contiguous()
+        tot = r.sum(dim=-1).contiguous()
+        out = _lib.diffusion_forward(handle, vals, c0, r, tot, act)
+        ctx.save_for_backward(r, tot, a, vals, c0, out)
+        ctx.handle, ctx.act, ctx.K1 = handle, act, kernel.shape[1]
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        r, tot, a, vals, c0, out = ctx.saved_tensors
+        gy = gy.contiguous()
+        if gy.data_ptr() % 16:                   # a view at an odd offset: the kernel reads 16-byte vectors
+            gy = gy.clone()
+        dr, dk = _lib.diffusion_backward(ctx.handle, a, vals, c0, r, tot, out, gy, ctx.K1, ctx.act)
+        return (dr if ctx.needs_input_grad[0] else None), (dk if ctx.needs_input_grad[1] else None), None, None, None, None, None
 
 
 class CumsumActFn(torch.autograd.Function):

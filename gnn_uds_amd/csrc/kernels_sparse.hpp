@@ -739,6 +739,206 @@ inline hipError_t launch_diffusion(const DiffusionArgs &a, int S, hipStream_t st
   return hipGetLastError();
 }
 
+// Reverse of k_diffusion.  With gz = act'(y) gy (act' from the output y), K = K1 - 1, M_0[s, i] = tot[s] and
+// M_m[s, i] = sum_{p in row i} a_p^m r[s, col p] (m = 1..K):
+//     dtheta[q, k] = sum_{s, i} gz[s, i, q] M_{K-k}[s, i]
+//     dr[s, j]     = g0[s] + sum_{p : col p = j} sum_q vals[p, q] gz[s, row p, q],     g0[s] = sum_{i, q} c0[q] gz[s, i, q]
+// (the c0 tot[s] term reaches every r[s, j]; zero entries of a_hat are off the support in both directions).  Three launches:
+//   rows    grid (gx, sy): block (bx, by) owns snapshots [8 by, 8 by + 8) and row slots bx, bx + gx, ...; lr lanes per row
+//           (lr = c4 rounded up to a power of two), lane q = channels 4q..4q+3.  Writes gz, the block's partial of the
+//           (K1, C) moment products and, per snapshot, of g0.
+//   reduce  one block per dtheta element and per g0[s]: strided partial sums and a fixed LDS tree.
+//   input   grid (ceil(n_cols / (256 / lr)), S): row j of the TRANSPOSED pattern, vals read through perm_t, lanes summed by a
+//           fixed xor tree.
+// Every partial has one writer and every sum a fixed order: no atomics, bitwise repeatable.  The block partition depends only
+// on (n_rows, S, C), not on the device.
+constexpr int DIFF_SCH = 8;        // snapshots per row-pass block
+constexpr int DIFF_KMAX = 16;      // largest K1 the row pass takes
+
+struct DiffusionBwdArgs {
+  const int32_t *rowptr, *col, *t_rowptr, *t_col, *perm_t;
+  const float *a, *vals, *c0, *r, *tot, *y, *gy;
+  float *gz, *pth, *pg, *g0, *dr, *dtheta;
+  int n_rows, n_cols, S, c4, lr, K1, act, gx, sy;
+};
+
+struct DiffusionBwdPlan {
+  int lr, gx, sy;
+  int64_t off_pth, off_pg, off_g0, total;     // workspace carve (floats, 16-byte aligned sections); gz at offset 0
+};
+
+inline DiffusionBwdPlan diffusion_bwd_plan(int64_t n_rows, int64_t S, int64_t C, int64_t K1) {
+  DiffusionBwdPlan p;
+  p.lr = 1;
+  while (p.lr < C / 4) p.lr <<= 1;
+  const int64_t rpb = 256 / p.lr, ng = (n_rows + rpb - 1) / rpb;
+  p.sy = (int)((S + DIFF_SCH - 1) / DIFF_SCH);
+  const int64_t cap = p.sy > 0 && 2048 / p.sy > 256 ? 2048 / p.sy : 256;      // ~2048 blocks: the whole GPU, few partials
+  p.gx = (int)(ng < 1 ? 1 : ng < cap ? ng : cap);
+  auto up4 = [](int64_t f) { return (f + 3) & ~int64_t(3); };
+  p.off_pth = up4(S * n_rows * C);
+  p.off_pg = p.off_pth + up4((int64_t)p.gx * p.sy * K1 * C);
+  p.off_g0 = p.off_pg + up4(S * p.gx);
+  p.total = p.off_g0 + up4(S);
+  return p;
+}
+
+__device__ __forceinline__ float act_grad_from_out(float y, float g, int act) {     // autograd.act_grad, element-wise
+  switch (act) {
+    case UDS_ACT_RELU: return y > 0.f ? g : 0.f;
+    case UDS_ACT_TANH: return g * (1.f - y * y);
+    case UDS_ACT_SIGMOID: return g * y * (1.f - y);
+    case UDS_ACT_HARD_SIGMOID: return y > 0.f && y < 1.f ? g * 0.2f : 0.f;
+    default: return g;
+  }
+}
+
+template <int KMAX>
+__global__ __launch_bounds__(256) void k_diffusion_bwd_rows(DiffusionBwdArgs a) {
+  __shared__ float4 s_red[256];
+  __shared__ float s_g0[4][DIFF_SCH];
+  const int tid = threadIdx.x, q = tid % a.lr, rpb = 256 / a.lr, wave = tid >> 6, wl = tid & 63;
+  const bool qok = q < a.c4;
+  const int s0 = blockIdx.y * DIFF_SCH;
+  const float4 c = qok ? reinterpret_cast<const float4 *>(a.c0)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 acc[KMAX];
+#pragma unroll
+  for (int m = 0; m < KMAX; ++m) acc[m] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float g0p[DIFF_SCH];
+#pragma unroll
+  for (int sl = 0; sl < DIFF_SCH; ++sl) g0p[sl] = 0.f;
+  for (int i = blockIdx.x * rpb + tid / a.lr; i < a.n_rows; i += gridDim.x * rpb) {
+    const int beg = a.rowptr[i], end = a.rowptr[i + 1];
+#pragma unroll
+    for (int sl = 0; sl < DIFF_SCH; ++sl) {
+      const int s = s0 + sl;
+      if (s < a.S) {
+        float M[KMAX];
+        M[0] = a.tot[s];
+#pragma unroll
+        for (int m = 1; m < KMAX; ++m) M[m] = 0.f;
+        const float *rs = a.r + (int64_t)s * a.n_cols;
+        for (int p = beg; p < end; ++p) {
+          const float av = a.a[p];
+          float pw = rs[a.col[p]];
+#pragma unroll
+          for (int m = 1; m < KMAX; ++m)
+            if (m < a.K1) {
+              pw *= av;
+              M[m] += pw;
+            }
+        }
+        if (qok) {
+          const int64_t idx = ((int64_t)s * a.n_rows + i) * a.c4 + q;
+          const float4 yv = reinterpret_cast<const float4 *>(a.y)[idx], gv = reinterpret_cast<const float4 *>(a.gy)[idx];
+          const float4 z = make_float4(act_grad_from_out(yv.x, gv.x, a.act), act_grad_from_out(yv.y, gv.y, a.act),
+                                       act_grad_from_out(yv.z, gv.z, a.act), act_grad_from_out(yv.w, gv.w, a.act));
+          reinterpret_cast<float4 *>(a.gz)[idx] = z;
+#pragma unroll
+          for (int m = 0; m < KMAX; ++m)
+            if (m < a.K1) {
+              acc[m].x = fmaf(z.x, M[m], acc[m].x);
+              acc[m].y = fmaf(z.y, M[m], acc[m].y);
+              acc[m].z = fmaf(z.z, M[m], acc[m].z);
+              acc[m].w = fmaf(z.w, M[m], acc[m].w);
+            }
+          g0p[sl] += c.x * z.x + c.y * z.y + c.z * z.z + c.w * z.w;
+        }
+      }
+    }
+  }
+  // g0 partial per snapshot: wave xor tree, then the 4 waves in order
+#pragma unroll
+  for (int sl = 0; sl < DIFF_SCH; ++sl) {
+    float v = g0p[sl];
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (wl == 0) s_g0[wave][sl] = v;
+  }
+  __syncthreads();
+  if (tid < DIFF_SCH && s0 + tid < a.S)
+    a.pg[(int64_t)(s0 + tid) * a.gx + blockIdx.x] = ((s_g0[0][tid] + s_g0[1][tid]) + s_g0[2][tid]) + s_g0[3][tid];
+  // moment products: lanes of one channel group are lr apart in a wave (xor tree over the row slots), then the 4 waves in order
+  const int64_t blk = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+#pragma unroll
+  for (int m = 0; m < KMAX; ++m) {
+    if (m >= a.K1) break;
+    float4 v = acc[m];
+    for (int o = a.lr; o < 64; o <<= 1) {
+      v.x += __shfl_xor(v.x, o);
+      v.y += __shfl_xor(v.y, o);
+      v.z += __shfl_xor(v.z, o);
+      v.w += __shfl_xor(v.w, o);
+    }
+    if (wl < a.lr) s_red[wave * 64 + wl] = v;
+    __syncthreads();
+    if (tid < a.lr && qok) {
+      float4 t = s_red[tid];
+      for (int w = 1; w < 4; ++w) {
+        const float4 u = s_red[w * 64 + tid];
+        t.x += u.x, t.y += u.y, t.z += u.z, t.w += u.w;
+      }
+      reinterpret_cast<float4 *>(a.pth)[(blk * a.K1 + m) * a.c4 + q] = t;
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void k_diffusion_bwd_reduce(DiffusionBwdArgs a) {
+  __shared__ float sh[256];
+  const int tid = threadIdx.x, C = a.c4 * 4, nt = a.K1 * C;
+  const int o = blockIdx.x;
+  float v = 0.f;
+  if (o < nt) {
+    const int64_t nb = (int64_t)a.gx * a.sy;
+    for (int64_t b = tid; b < nb; b += 256) v += a.pth[b * nt + o];
+  } else {
+    const int64_t s = o - nt;
+    for (int b = tid; b < a.gx; b += 256) v += a.pg[s * a.gx + b];
+  }
+  sh[tid] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) sh[tid] += sh[tid + w];
+    __syncthreads();
+  }
+  if (tid == 0) {
+    if (o < nt) a.dtheta[(o % C) * a.K1 + (a.K1 - 1 - o / C)] = sh[0];     // moment m = K - k
+    else a.g0[o - nt] = sh[0];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_diffusion_bwd_input(DiffusionBwdArgs a) {
+  const int tid = threadIdx.x, q = tid % a.lr;
+  const int j = blockIdx.x * (256 / a.lr) + tid / a.lr, s = blockIdx.y;
+  const bool live = j < a.n_cols;
+  float acc = 0.f;
+  if (live && q < a.c4) {
+    const float4 *gz = reinterpret_cast<const float4 *>(a.gz) + (int64_t)s * a.n_rows * a.c4 + q;
+    const float4 *vals = reinterpret_cast<const float4 *>(a.vals) + q;
+    for (int p = a.t_rowptr[j]; p < a.t_rowptr[j + 1]; ++p) {
+      const float4 v = vals[(int64_t)a.perm_t[p] * a.c4], z = gz[(int64_t)a.t_col[p] * a.c4];
+      acc = fmaf(v.x, z.x, acc);
+      acc = fmaf(v.y, z.y, acc);
+      acc = fmaf(v.z, z.z, acc);
+      acc = fmaf(v.w, z.w, acc);
+    }
+  }
+  for (int o = a.lr >> 1; o > 0; o >>= 1) acc += __shfl_xor(acc, o);      // every lane takes part (no early return above)
+  if (live && q == 0) a.dr[(int64_t)s * a.n_cols + j] = a.g0[s] + acc;
+}
+
+inline hipError_t launch_diffusion_backward(const DiffusionBwdArgs &a, hipStream_t st) {
+  if (a.K1 <= 8) hipLaunchKernelGGL(k_diffusion_bwd_rows<8>, dim3((unsigned)a.gx, (unsigned)a.sy), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_diffusion_bwd_rows<DIFF_KMAX>, dim3((unsigned)a.gx, (unsigned)a.sy), dim3(256), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_diffusion_bwd_reduce, dim3((unsigned)(a.K1 * a.c4 * 4 + a.S)), dim3(256), 0, st, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const int rpb = 256 / a.lr;
+  hipLaunchKernelGGL(k_diffusion_bwd_input, dim3((unsigned)((a.n_cols + rpb - 1) / rpb), (unsigned)a.S), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 // spektral GlobalAttnSumPool in batch mode (agent.py:93-94: the head of the RL agents' ConvNet): per sample b,
 //     alpha = softmax_r(<x[b, r, :], k>),  out[b, :] = sum_r alpha_r x[b, r, :]
 // One 256-thread workgroup per sample, one pass over its rows with an online (running-max) softmax: thread (c, part) owns float4

@@ -293,7 +293,9 @@ class DiffusionConv(nn.Module):
         out[..., q] = act( reduce_sum( polyval(theta_q, a_hat) @ x, -1 ) ),     no bias,
     where tf.math.polyval is Horner's rule on the ENTRIES of a_hat (element-wise powers).  A zero entry of a_hat therefore
     takes the constant coefficient theta_q[K]; with r = x.sum(-1) the dense (N, N) product collapses to the support of a_hat
-    plus a rank-one term (uds_diffusion_forward).  a_hat = DiffusionConv.preprocess(adj).  Inference only."""
+    plus a rank-one term (uds_diffusion_forward).  a_hat = DiffusionConv.preprocess(adj): a dense array, or a `graph.CSR`
+    carrying its values (no N x N array on the host).  Training: `autograd.DiffusionFn` (uds_diffusion_backward gives d r and
+    d kernel; the feature sum r = x.sum(-1) stays a torch op in front, its backward broadcasts d r over the features)."""
 
     def __init__(self, channels, K=6, activation='tanh', in_channels=None, generator=None):
         super().__init__()
@@ -306,7 +308,16 @@ class DiffusionConv(nn.Module):
 
     @staticmethod
     def preprocess(adj):
-        """normalized_adjacency: D^-1/2 A D^-1/2 (no self loops added), row-sum degrees, inf -> 0 (`emulator.py:137-138`)."""
+        """normalized_adjacency: D^-1/2 A D^-1/2 (no self loops added), row-sum degrees, inf -> 0 (`emulator.py:137-138`).
+        A square `graph.CSR` (values, or ones when it has none) gives a `graph.CSR` with the normalised values."""
+        if isinstance(adj, CSR):
+            val = np.ones(adj.nnz) if adj.val is None else np.asarray(adj.val, dtype=np.float64)
+            rows, cols = adj.rows(), adj.col.astype(np.int64)
+            deg = np.bincount(rows, weights=val, minlength=adj.n_rows)
+            with np.errstate(divide='ignore'):
+                dinv = np.power(deg, -0.5)
+            dinv[np.isinf(dinv)] = 0.0
+            return CSR(adj.rowptr, adj.col, adj.n_rows, adj.n_cols, dinv[rows] * val * dinv[cols])
         a = np.asarray(adj, dtype=np.float64)
         deg = a.sum(axis=1)
         with np.errstate(divide='ignore'):
@@ -317,8 +328,13 @@ class DiffusionConv(nn.Module):
     def _filter(self, a, device):
         hit = self._cache.get(id(a))
         if hit is None or hit[0] is not a:
-            dense = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-            csr = csr_from_dense(dense, keep_values=True)
+            if isinstance(a, CSR):
+                if a.val is None:
+                    raise ValueError('DiffusionConv: a CSR filter must carry its values (DiffusionConv.preprocess(csr))')
+                csr = a
+            else:
+                dense = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+                csr = csr_from_dense(dense, keep_values=True)
             hit = self._cache[id(a)] = (a, _lib.CsrHandle(csr), torch.as_tensor(csr.val, dtype=torch.float32, device=device))
             self._vals = None
         key = (self.kernel._version, self.kernel.data_ptr(), id(a))
@@ -329,15 +345,16 @@ class DiffusionConv(nn.Module):
             for k in range(1, self.K):                       # Horner, as tf.math.polyval
                 v = v * av + th[:, k]
             self._vals = (key, (v - th[:, -1]).float().contiguous(), th[:, -1].float().contiguous())
-        return hit[1], self._vals[1], self._vals[2]
+        return hit[1], self._vals[1], self._vals[2], hit[2]
 
     def forward(self, inputs):
         x, a = inputs
-        if _ag.grad_on(x, self.kernel):
-            raise NotImplementedError('DiffusionConv is built for inference (no backward kernels)')
-        h, vals, c0 = self._filter(a, x.device)
+        h, vals, c0, a_sup = self._filter(a, x.device)
         xs, lead = _flatten_snapshots(x)
         r = xs.sum(dim=-1)
+        if _ag.grad_on(x, self.kernel):
+            out = _ag.DiffusionFn.apply(r, self.kernel, h, a_sup, vals, c0, self.activation)
+            return out.reshape(lead + out.shape[-2:])
         out = _lib.diffusion_forward(h, vals, c0, r.contiguous(), r.sum(dim=-1).contiguous(), self.activation)
         return out.reshape(lead + out.shape[-2:])
 

@@ -167,6 +167,23 @@ int uds_rowgemm_forward_cat(const float *x, int64_t F1, const float *x2, int64_t
 int uds_diffusion_forward(const uds_csr_t *csr, const float *vals, const float *c0, const float *r, const float *tot,
                           int64_t S, int64_t C, int act, float *out, uds_stream_t stream);
 
+/* The reverse of uds_diffusion_forward (training a DiffusionConv), exact fp32, in three launches; no atomics, so two calls on
+ * the same inputs give the same bits.  With gz = act'(y) * gy (act' from the forward's output y, as autograd.act_grad),
+ * K1 = K + 1 coefficients per channel (highest power first), M_0[s, i] = tot[s], M_m[s, i] = sum_{p in row i} a[p]^m r[s, col[p]]:
+ *   dtheta[q, k] = sum_{s, i} gz[s, i, q] * M_{K-k}[s, i]                                   (C, K1), overwritten
+ *   dr[s, j]     = sum_{i, q} c0[q] gz[s, i, q] + sum_{p : col[p] = j} sum_q vals[p, q] gz[s, row(p), q]    (S, n_cols)
+ * dr is the gradient of r (tot = sum_j r[s, j] is folded in: its term reaches every j); dx[s, j, f] = dr[s, j] for every f.
+ * csr: the pattern of the forward; csr_t: its transpose (n_cols rows); perm_t (int32, nnz): perm_t[p] = position in csr's
+ * row-major order of entry p of csr_t (CsrHandle.transposed), entries < nnz (not checked on the device).  a (nnz): the values
+ * a_hat takes on the support, in csr's order.  vals (nnz, C), c0 (C), r (S, n_cols), tot (S) as uds_diffusion_forward;
+ * y, gy (S, n_rows, C).  C % 4 == 0, C <= 256, 1 <= K1 <= 16, S <= 65535; vals, c0, y, gy and workspace 16-byte aligned.
+ * workspace: uds_diffusion_backward_workspace_floats(n_rows, S, C, K1) floats (gz and per-block partials; -1 for sizes the
+ * kernels do not take). */
+int64_t uds_diffusion_backward_workspace_floats(int64_t n_rows, int64_t S, int64_t C, int64_t K1);
+int uds_diffusion_backward(const uds_csr_t *csr, const uds_csr_t *csr_t, const int32_t *perm_t, const float *a, const float *vals,
+                           const float *c0, const float *r, const float *tot, const float *y, const float *gy, int64_t S, int64_t C,
+                           int64_t K1, int act, float *workspace, float *dr, float *dtheta, uds_stream_t stream);
+
 /* Message buffers of the graph-sharded spatial block (one 200k-node network node-cut over the GPUs; the reference holds
  * whole graphs on one device, SURVEY.md F5 / 8e -- the exchange itself is torch.distributed isend / irecv over RCCL).
  *   pack:   buf[s, i, :] = i < nx ? x[s, idx_x[i], :] : e[s, idx_e[i - nx], :]     one buffer per peer, node rows then link rows
