@@ -85,6 +85,9 @@ SYMBOLS = {
                                   _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     'uds_gat_backward_coef': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr,
                                        _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_gat_aggregate_ex': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
+    'uds_gat_backward_ex': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
+                                     _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     'uds_csr_sddmm': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr]),
     'uds_wgrad_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_int]),
     'uds_wgrad': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
@@ -949,6 +952,56 @@ def gat_backward(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nb
                                      _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(a_self, 'a_self'), _dev(a_nbr, 'a_nbr'),
                                      _dev(coef, 'coef', True), S, d, _dev(ws[0], 'alpha_ws'), _dev(ws[1], 'de_ws'), _dev(d_hx, 'd_hx'),
                                      _dev(ds_self, 'ds_self'), _dev(ds_nbr, 'ds_nbr'), _stream()), 'uds_gat_backward_coef')
+    return d_hx, ds_self, ds_nbr
+
+
+def _check_entry_operand(name, t, S, handle):
+    if t is not None and tuple(t.shape) != (S, handle.nnz):
+        raise UdsError('%s %r for %d snapshots of a %d-entry pattern' % (name, tuple(t.shape), S, handle.nnz))
+
+
+def gat_aggregate_ex(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask=None, coef=None):
+    """gat_aggregate with an optional per-snapshot edge_mask (S, nnz) AND an optional attention-dropout coef (S, nnz) on the
+    grouped kernels (uds_gat_aggregate_ex): the training path of `use_adj` GAT layers.  A masked entry leaves the softmax; the
+    diagonal always takes part.  With edge_mask = all ones and coef None the result is bitwise that of gat_aggregate."""
+    lib = load()
+    S, n, d = hx.shape
+    if n != handle.n_rows or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
+        raise UdsError('gat_aggregate_ex: hx %r, s_self %r, s_nbr %r do not match a %d-row pattern' %
+                       (tuple(hx.shape), tuple(s_self.shape), tuple(s_nbr.shape), handle.n_rows))
+    _check_entry_operand('gat_aggregate_ex: edge_mask', edge_mask, S, handle)
+    _check_entry_operand('gat_aggregate_ex: coef', coef, S, handle)
+    out = torch.empty_like(hx)
+    if out.numel() == 0:
+        _dev(hx, 'hx')
+        return out
+    _check(lib.uds_gat_aggregate_ex(handle.ptr, _dev(hx, 'hx'), _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(bias, 'bias', True),
+                                    _dev(edge_mask, 'edge_mask', True), _dev(coef, 'coef', True), S, d, ACT[act], _dev(out, 'out'),
+                                    _stream()), 'uds_gat_aggregate_ex')
+    return out
+
+
+def gat_backward_ex(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, edge_mask=None, coef=None):
+    """Reverse mode of gat_aggregate_ex (uds_gat_backward_ex): outputs as gat_backward.  A masked entry contributes nothing."""
+    lib = load()
+    S, n, d = grad.shape
+    if n != handle.n_rows or tuple(hx.shape) != (S, n, d) or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
+        raise UdsError('gat_backward_ex: grad %r, hx %r, s_self %r, s_nbr %r do not match a %d-row pattern' %
+                       (tuple(grad.shape), tuple(hx.shape), tuple(s_self.shape), tuple(s_nbr.shape), handle.n_rows))
+    _check_entry_operand('gat_backward_ex: edge_mask', edge_mask, S, handle)
+    _check_entry_operand('gat_backward_ex: coef', coef, S, handle)
+    d_hx = torch.empty_like(grad)
+    ds_self = torch.empty((S, n), device=grad.device, dtype=torch.float32)
+    ds_nbr = torch.empty_like(ds_self)
+    if grad.numel() == 0:
+        _dev(grad, 'grad')
+        return d_hx, ds_self, ds_nbr
+    ws = torch.empty((2, S, max(handle.nnz, 1)), device=grad.device, dtype=torch.float32)
+    _check(lib.uds_gat_backward_ex(handle.ptr, handle_t.ptr, _dev_i32(perm_t, 'perm_t'), _dev(grad, 'grad'), _dev(hx, 'hx'),
+                                   _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(a_self, 'a_self'), _dev(a_nbr, 'a_nbr'),
+                                   _dev(edge_mask, 'edge_mask', True), _dev(coef, 'coef', True), S, d, _dev(ws[0], 'alpha_ws'),
+                                   _dev(ws[1], 'de_ws'), _dev(d_hx, 'd_hx'), _dev(ds_self, 'ds_self'), _dev(ds_nbr, 'ds_nbr'),
+                                   _stream()), 'uds_gat_backward_ex')
     return d_hx, ds_self, ds_nbr
 
 

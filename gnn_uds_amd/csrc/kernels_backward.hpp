@@ -28,6 +28,10 @@ struct GatBwdRowsArgs {
   // attention dropout (k_gat_aggregate_coef): pre_i = sum_j alpha_ij m_ij hx_j with m (S, nnz) = 0 or 1 / (1 - rate), else NULL.
   // Then q_ij = m_ij <g_i, hx_j> in the formulas above, and the alpha handed to the column pass is alpha_ij m_ij.
   const float *coef;
+  // per-snapshot edge mask (S, nnz) of uds_gat_backward_ex (use_adj), else NULL: entry p of snapshot s takes part iff
+  // mask != 0 or p is the row's diagonal.  The softmax runs over the surviving entries; a masked entry gets alpha = de = 0,
+  // so the column pass needs no change.
+  const float *mask;
 };
 
 __global__ __launch_bounds__(256) void k_gat_bwd_rows(GatBwdRowsArgs a) {
@@ -44,19 +48,24 @@ __global__ __launch_bounds__(256) void k_gat_bwd_rows(GatBwdRowsArgs a) {
   const float4 *hx4 = reinterpret_cast<const float4 *>(a.hx) + (int64_t)s * a.n * a.d4;
   float *al = a.alpha + (int64_t)s * a.nnz, *de = a.de + (int64_t)s * a.nnz;
   const float *cf = a.coef ? a.coef + (int64_t)s * a.nnz : nullptr;
+  const float *mk = a.mask ? a.mask + (int64_t)s * a.nnz : nullptr;
   float m = -INFINITY;
-  for (int p = beg; p < end; ++p) m = fmaxf(m, leaky02(ss + sn[a.col[p]]));
+  for (int p = beg; p < end; ++p) {
+    const int j = a.col[p];
+    if (!mk || mk[p] != 0.0f || j == i) m = fmaxf(m, leaky02(ss + sn[j]));
+  }
   float den = 0.f, cn = 0.f;
   if (end - beg <= a.G) {
     // the usual case (degree <= lanes per row): lane k of the row keeps entry k's (exp, q, logit sign) in registers, the
     // row sums are known to every lane after the loop, and the lanes write alpha / de of their entries side by side --
     // no second walk through memory by one lane.  Same operation order per value as the general path below.
     float wk = 0.f, qk = 0.f;
-    bool pos = false;
+    bool pos = false, onk = true;
     for (int p = beg; p < end; ++p) {
       const int j = a.col[p];
       const float lgt = ss + sn[j];
-      const float w = expf(leaky02(lgt) - m);
+      const bool on = !mk || mk[p] != 0.0f || j == i;
+      const float w = on ? expf(leaky02(lgt) - m) : 0.f;       // a masked entry: weight 0, alpha = de = 0 below
       float q = 0.f;
       for (int c = lg; c < a.d4; c += a.G) {
         const float4 gv = g4[c], hv = hx4[(int64_t)j * a.d4 + c];
@@ -70,14 +79,15 @@ __global__ __launch_bounds__(256) void k_gat_bwd_rows(GatBwdRowsArgs a) {
         wk = w;
         qk = q;
         pos = lgt > 0.0f;
+        onk = on;
       }
     }
-    const float inv = end > beg ? 1.0f / den : 0.0f;
+    const float inv = (mk ? den > 0.0f : end > beg) ? 1.0f / den : 0.0f;     // (a row with every entry masked: den = 0)
     const float cbar = cn * inv;
     const bool mine = lg < end - beg;
     const float w = wk * inv;
     const float dl = w * (qk - cbar);
-    const float dv = mine ? (pos ? dl : 0.2f * dl) : 0.f;
+    const float dv = mine && onk ? (pos ? dl : 0.2f * dl) : 0.f;
     if (mine && row_ok) {
       al[beg + lg] = cf ? w * cf[beg + lg] : w;
       de[beg + lg] = dv;
@@ -90,7 +100,7 @@ __global__ __launch_bounds__(256) void k_gat_bwd_rows(GatBwdRowsArgs a) {
   }
   for (int p = beg; p < end; ++p) {
     const int j = a.col[p];
-    const float w = expf(leaky02(ss + sn[j]) - m);
+    const float w = !mk || mk[p] != 0.0f || j == i ? expf(leaky02(ss + sn[j]) - m) : 0.f;
     float q = 0.f;
     for (int c = lg; c < a.d4; c += a.G) {
       const float4 gv = g4[c], hv = hx4[(int64_t)j * a.d4 + c];
@@ -106,13 +116,14 @@ __global__ __launch_bounds__(256) void k_gat_bwd_rows(GatBwdRowsArgs a) {
     }
   }
   if (lg != 0 || !row_ok) return;
-  const float inv = end > beg ? 1.0f / den : 0.0f;
+  const float inv = (mk ? den > 0.0f : end > beg) ? 1.0f / den : 0.0f;
   const float cbar = cn * inv;
   float dss = 0.f;
   for (int p = beg; p < end; ++p) {       // same lane wrote al / de above
     const float w = al[p] * inv;
     const float dl = w * (de[p] - cbar);
-    const float dv = ss + sn[a.col[p]] > 0.0f ? dl : 0.2f * dl;
+    const int j = a.col[p];
+    const float dv = mk && !(mk[p] != 0.0f || j == i) ? 0.f : (ss + sn[j] > 0.0f ? dl : 0.2f * dl);
     al[p] = cf ? w * cf[p] : w;
     de[p] = dv;
     dss += dv;
@@ -123,7 +134,10 @@ __global__ __launch_bounds__(256) void k_gat_bwd_rows(GatBwdRowsArgs a) {
 // Grouped variant (see kernels_sparse.hpp): the G lanes of a row load G entries' indices and scores side by side, each
 // lane ends up holding (exp, q, sign) of "its" entry, and alpha / de are written side by side.  Rows of more than G entries
 // park the raw (exp, q) pairs in alpha / de per chunk and finish them in a second walk (same lane wrote them).
-template <int G, int NC>
+// EX = true (uds_gat_backward_ex) honours a.mask and a.coef: a masked entry gets weight 0 but stays in every shuffle, the
+// row maximum runs over the surviving entries, and q of entry k is multiplied by its coef after the lane reduction (the
+// order of k_gat_bwd_rows).  EX = false ignores both (uds_gat_backward; its code is that of the unmasked kernel).
+template <int G, int NC, bool EX = false>
 __global__ __launch_bounds__(256) void k_gat_bwd_rows_g(GatBwdRowsArgs a) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int c = (int)(t % G);
@@ -137,43 +151,58 @@ __global__ __launch_bounds__(256) void k_gat_bwd_rows_g(GatBwdRowsArgs a) {
   const float4 *g4 = reinterpret_cast<const float4 *>(a.g) + ((int64_t)s * a.n + i) * a.d4 + c;
   const float4 *hx4 = reinterpret_cast<const float4 *>(a.hx) + (int64_t)s * a.n * a.d4 + c;
   float *al = a.alpha + (int64_t)s * a.nnz, *de = a.de + (int64_t)s * a.nnz;
+  const float *mk = EX && a.mask ? a.mask + (int64_t)s * a.nnz : nullptr;
+  const float *cf = EX && a.coef ? a.coef + (int64_t)s * a.nnz : nullptr;
   float4 gv[NC];
 #pragma unroll
   for (int q = 0; q < NC; ++q) gv[q] = g4[G * q];
-  float m = -INFINITY, l0 = 0.f;
+  float m = -INFINITY, l0 = 0.f, c0 = 1.f;
   int j0 = 0;
+  bool on0 = true;
   for (int b0 = beg; b0 < end; b0 += G) {
     const int p = b0 + c;
-    const int j = a.col[min(p, end - 1)];
+    const int pc = min(p, end - 1);
+    const int j = a.col[pc];
     const float lgt = ss + sn[j];
+    bool on = p < end;
+    if (EX && mk) on = on && (mk[pc] != 0.0f || j == i);
     if (b0 == beg) {
       j0 = j;
       l0 = lgt;
+      on0 = on;
+      if (EX && cf) c0 = cf[pc];
     }
-    m = fmaxf(m, p < end ? leaky02(lgt) : -INFINITY);
+    m = fmaxf(m, on ? leaky02(lgt) : -INFINITY);
   }
   m = group_max<G>(m);
   const bool single = end - beg <= G;
-  float den = 0.f, cn = 0.f, wk = 0.f, qk = 0.f, lk = 0.f;
+  float den = 0.f, cn = 0.f, wk = 0.f, qk = 0.f, lk = 0.f, ck = 1.f;
+  bool onk = true;
   for (int b0 = beg; b0 < end; b0 += G) {
     const int p = b0 + c;
     int j = j0;
-    float lgt = l0;
+    float lgt = l0, cv = c0;
+    bool on = on0;
     if (b0 != beg) {
-      j = a.col[min(p, end - 1)];
+      const int pc = min(p, end - 1);
+      j = a.col[pc];
       lgt = ss + sn[j];
+      on = p < end;
+      if (EX && mk) on = on && (mk[pc] != 0.0f || j == i);
+      if (EX && cf) cv = cf[pc];
     }
-    const float w = p < end ? expf(leaky02(lgt) - m) : 0.f;
+    const float w = (EX ? on : p < end) ? expf(leaky02(lgt) - m) : 0.f;
     const int nk = min(G, end - b0);
     float qm = 0.f;
     for (int k0 = 0; k0 < nk; k0 += GU) {
-      float ww[GU], qq[GU];
+      float ww[GU], qq[GU], cc[GU];
       float4 hv[GU][NC];
 #pragma unroll
       for (int u = 0; u < GU; ++u) {
         const int k = min(k0 + u, nk - 1);
         const int jj = __shfl(j, k, G);
         ww[u] = __shfl(w, k, G);
+        if (EX && cf) cc[u] = __shfl(cv, k, G);
 #pragma unroll
         for (int v = 0; v < NC; ++v) hv[u][v] = hx4[(int64_t)jj * a.d4 + G * v];
       }
@@ -189,6 +218,9 @@ __global__ __launch_bounds__(256) void k_gat_bwd_rows_g(GatBwdRowsArgs a) {
       for (int o = G >> 1; o > 0; o >>= 1)
 #pragma unroll
         for (int u = 0; u < GU; ++u) qq[u] += __shfl_xor(qq[u], o);
+      if (EX && cf)
+#pragma unroll
+        for (int u = 0; u < GU; ++u) qq[u] *= cc[u];
 #pragma unroll
       for (int u = 0; u < GU; ++u)
         if (k0 + u < nk) {
@@ -201,20 +233,22 @@ __global__ __launch_bounds__(256) void k_gat_bwd_rows_g(GatBwdRowsArgs a) {
       wk = w;
       qk = qm;
       lk = lgt;
+      ck = cv;
+      onk = on;
     } else if (p < end && row_ok) {
       al[p] = w;
       de[p] = qm;
     }
   }
-  const float inv = end > beg ? 1.0f / den : 0.0f;
+  const float inv = (EX ? den > 0.0f : end > beg) ? 1.0f / den : 0.0f;
   const float cbar = cn * inv;
   if (single) {
     const bool mine = c < end - beg;
     const float w = wk * inv;
     const float dl = w * (qk - cbar);
-    const float dv = mine ? (lk > 0.0f ? dl : 0.2f * dl) : 0.f;
+    const float dv = (EX ? mine && onk : mine) ? (lk > 0.0f ? dl : 0.2f * dl) : 0.f;
     if (mine && row_ok) {
-      al[beg + c] = w;
+      al[beg + c] = EX && cf ? w * ck : w;
       de[beg + c] = dv;
     }
     float dss = 0.f;
@@ -227,10 +261,11 @@ __global__ __launch_bounds__(256) void k_gat_bwd_rows_g(GatBwdRowsArgs a) {
     const int p = b0 + c;
     float dv = 0.f;
     if (p < end && row_ok) {
-      const float w = al[p] * inv;
+      const float w = al[p] * inv;        // EX: a masked entry parked exp = 0, so w = 0 and dl = +-0
       const float dl = w * (de[p] - cbar);
-      dv = ss + sn[a.col[p]] > 0.0f ? dl : 0.2f * dl;
-      al[p] = w;
+      const int j = a.col[p];
+      dv = EX && mk && !(mk[p] != 0.0f || j == i) ? 0.f : (ss + sn[j] > 0.0f ? dl : 0.2f * dl);
+      al[p] = EX && cf ? w * cf[p] : w;
       de[p] = dv;
     }
     dss += dv;
@@ -246,6 +281,19 @@ inline hipError_t launch_gat_bwd_rows(const GatBwdRowsArgs &a, hipStream_t st) {
   if (G && a.n > 0 && !a.coef)      // (attention dropout: the plain kernel below)
     return launch_grouped(a, a.n, a.S, a.d4, st, [&](auto g_, auto nc_, dim3 grid) {
       hipLaunchKernelGGL((k_gat_bwd_rows_g<decltype(g_)::value, decltype(nc_)::value>), grid, dim3(256), 0, st, a);
+    });
+  const int64_t total = (int64_t)a.n * a.G;
+  hipLaunchKernelGGL(k_gat_bwd_rows, dim3((unsigned)((total + 255) / 256), (unsigned)a.S), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// uds_gat_backward_ex: the grouped EX instantiations (mask and / or coef), the walking kernel for the other widths.
+inline hipError_t launch_gat_bwd_rows_ex(const GatBwdRowsArgs &a, hipStream_t st) {
+  int G, NC;
+  group_shape(a.d4, G, NC);
+  if (G && a.n > 0)
+    return launch_grouped(a, a.n, a.S, a.d4, st, [&](auto g_, auto nc_, dim3 grid) {
+      hipLaunchKernelGGL((k_gat_bwd_rows_g<decltype(g_)::value, decltype(nc_)::value, true>), grid, dim3(256), 0, st, a);
     });
   const int64_t total = (int64_t)a.n * a.G;
   hipLaunchKernelGGL(k_gat_bwd_rows, dim3((unsigned)((total + 255) / 256), (unsigned)a.S), dim3(256), 0, st, a);

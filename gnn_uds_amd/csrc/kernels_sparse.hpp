@@ -214,8 +214,20 @@ __global__ __launch_bounds__(256) void k_gat_aggregate(GatArgs a) {
   reinterpret_cast<float4 *>(a.out)[((int64_t)s * a.n + i) * a.d4 + c] = o;
 }
 
-template <int G, int NC>
-__global__ __launch_bounds__(256) void k_gat_aggregate_g(GatArgs a) {
+// Optional operands of the _ex aggregation / row pass (uds_gat_aggregate_ex, uds_gat_backward_ex): a per-snapshot edge
+// mask (S, nnz) -- entry p of snapshot s takes part iff mask[s, p] != 0 or p is the row's diagonal -- and the attention
+// dropout multiplier coef (S, nnz) on the normalised coefficients.  Either may be NULL.
+struct GatEx {
+  const float *mask, *coef;
+  int64_t nnz;
+};
+
+// EX = false: the unmasked instantiations (uds_gat_aggregate / uds_gat_forward), `x` unused.  EX = true: a masked entry
+// gets logit -inf exactly like the lanes past the row's end, so it stays in every shuffle with weight 0, and the row
+// maximum runs over the surviving entries only.  With an all-ones mask and no coef every value is computed by the same
+// operations in the same order as EX = false (a zero weight adds 0 to den and fmaf(0, h, acc) = acc): bitwise equal.
+template <int G, int NC, bool EX = false>
+__global__ __launch_bounds__(256) void k_gat_aggregate_g(GatArgs a, GatEx x) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t grp = t / G;
   const int c = (int)(t % G);
@@ -225,16 +237,22 @@ __global__ __launch_bounds__(256) void k_gat_aggregate_g(GatArgs a) {
   const int beg = a.rowptr[i], end = a.rowptr[i + 1];
   const float *sn = a.s_nbr + (int64_t)s * a.n;
   const float ss = a.s_self[(int64_t)s * a.n + i];
+  const float *mk = EX && x.mask ? x.mask + (int64_t)s * x.nnz : nullptr;
+  const float *cf = EX && x.coef ? x.coef + (int64_t)s * x.nnz : nullptr;
   // pass 1: row maximum of the logits; the single-chunk row (degree <= G, the usual case) keeps its logits for pass 2
-  float m = -INFINITY, l0 = -INFINITY;
+  float m = -INFINITY, l0 = -INFINITY, c0 = 1.0f;
   int j0 = 0;
   for (int b0 = beg; b0 < end; b0 += G) {
     const int p = b0 + c;
-    const int j = a.col[min(p, end - 1)];
-    const float l = p < end ? leaky02(ss + sn[j]) : -INFINITY;
+    const int pc = min(p, end - 1);
+    const int j = a.col[pc];
+    bool on = p < end;
+    if (EX && mk) on = on && (mk[pc] != 0.0f || j == i);
+    const float l = on ? leaky02(ss + sn[j]) : -INFINITY;
     if (b0 == beg) {
       j0 = j;
       l0 = l;
+      if (EX && cf) c0 = cf[pc];
     }
     m = fmaxf(m, l);
   }
@@ -247,21 +265,29 @@ __global__ __launch_bounds__(256) void k_gat_aggregate_g(GatArgs a) {
   for (int b0 = beg; b0 < end; b0 += G) {
     const int p = b0 + c;
     int j = j0;
-    float l = l0;
+    float l = l0, cv = c0;
     if (b0 != beg) {
-      j = a.col[min(p, end - 1)];
-      l = p < end ? leaky02(ss + sn[j]) : -INFINITY;
+      const int pc = min(p, end - 1);
+      j = a.col[pc];
+      bool on = p < end;
+      if (EX && mk) on = on && (mk[pc] != 0.0f || j == i);
+      l = on ? leaky02(ss + sn[j]) : -INFINITY;
+      if (EX && cf) cv = cf[pc];
     }
-    const float w = expf(l - m);                  // one exp per entry (lanes past the row's end hold exp(-inf) = 0, unused)
+    // one exp per entry (lanes past the row's end hold exp(-inf) = 0, unused); EX: a row whose every entry is masked has
+    // m = -inf, so the weight of an off lane is set to 0 instead of exp(-inf - -inf)
+    const float w = EX ? (l == -INFINITY ? 0.0f : expf(l - m)) : expf(l - m);
+    const float wc = EX && cf ? w * cv : w;      // attention dropout multiplies the numerator only, as k_gat_aggregate_coef
     const int nk = min(G, end - b0);
     for (int k0 = 0; k0 < nk; k0 += GU) {
-      float ww[GU];
+      float ww[GU], wm[GU];
       float4 hv[GU][NC];
 #pragma unroll
       for (int u = 0; u < GU; ++u) {
         const int k = min(k0 + u, nk - 1);
         const int jj = __shfl(j, k, G);
         ww[u] = __shfl(w, k, G);
+        wm[u] = EX && cf ? __shfl(wc, k, G) : ww[u];
 #pragma unroll
         for (int q = 0; q < NC; ++q) hv[u][q] = hx4[(int64_t)jj * a.d4 + G * q];
       }
@@ -271,16 +297,16 @@ __global__ __launch_bounds__(256) void k_gat_aggregate_g(GatArgs a) {
           den += ww[u];
 #pragma unroll
           for (int q = 0; q < NC; ++q) {
-            acc[q].x = fmaf(ww[u], hv[u][q].x, acc[q].x);
-            acc[q].y = fmaf(ww[u], hv[u][q].y, acc[q].y);
-            acc[q].z = fmaf(ww[u], hv[u][q].z, acc[q].z);
-            acc[q].w = fmaf(ww[u], hv[u][q].w, acc[q].w);
+            acc[q].x = fmaf(wm[u], hv[u][q].x, acc[q].x);
+            acc[q].y = fmaf(wm[u], hv[u][q].y, acc[q].y);
+            acc[q].z = fmaf(wm[u], hv[u][q].z, acc[q].z);
+            acc[q].w = fmaf(wm[u], hv[u][q].w, acc[q].w);
           }
         }
     }
   }
   if (!row_ok) return;
-  const float inv = end > beg ? 1.0f / den : 0.0f;
+  const float inv = (EX ? den > 0.0f : end > beg) ? 1.0f / den : 0.0f;
 #pragma unroll
   for (int q = 0; q < NC; ++q) {
     float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -401,10 +427,72 @@ inline hipError_t launch_gat_aggregate(const GatArgs &a, hipStream_t st) {
   group_shape(a.d4, G, NC);
   if (G && a.n > 0)
     return launch_grouped(a, a.n, a.S, a.d4, st, [&](auto g_, auto nc_, dim3 grid) {
-      hipLaunchKernelGGL((k_gat_aggregate_g<decltype(g_)::value, decltype(nc_)::value>), grid, dim3(256), 0, st, a);
+      hipLaunchKernelGGL((k_gat_aggregate_g<decltype(g_)::value, decltype(nc_)::value>), grid, dim3(256), 0, st, a, GatEx{});
     });
   const int64_t per_snap = (int64_t)a.n * a.d4;
   hipLaunchKernelGGL(k_gat_aggregate, dim3((unsigned)((per_snap + 255) / 256), (unsigned)a.S), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// One-lane-per-chunk form of k_gat_aggregate_g<.., EX = true> for widths group_shape does not cover (d / 4 not in
+// {2, 4, 8, 16, 32}).  No shuffles here, so a masked entry is skipped; the surviving entries are added in entry order with
+// the operations of k_gat_aggregate (bitwise equal to it under an all-ones mask and no coef).
+__global__ __launch_bounds__(256) void k_gat_aggregate_x(GatArgs a, GatEx x) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t per_snap = (int64_t)a.n * a.d4;
+  if (t >= per_snap) return;
+  const int s = blockIdx.y;
+  const int c = (int)(t % a.d4);
+  const int i = a.order[t / a.d4];
+  const int beg = a.rowptr[i], end = a.rowptr[i + 1];
+  const float *sn = a.s_nbr + (int64_t)s * a.n;
+  const float *mk = x.mask ? x.mask + (int64_t)s * x.nnz : nullptr;
+  const float *cf = x.coef ? x.coef + (int64_t)s * x.nnz : nullptr;
+  const float ss = a.s_self[(int64_t)s * a.n + i];
+  float m = -INFINITY;
+  for (int p = beg; p < end; ++p) {
+    const int j = a.col[p];
+    if (!mk || mk[p] != 0.0f || j == i) m = fmaxf(m, leaky02(ss + sn[j]));
+  }
+  const float4 *hx4 = reinterpret_cast<const float4 *>(a.hx) + (int64_t)s * a.n * a.d4 + c;
+  float den = 0.0f;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int p = beg; p < end; ++p) {
+    const int j = a.col[p];
+    if (mk && !(mk[p] != 0.0f || j == i)) continue;
+    const float w = expf(leaky02(ss + sn[j]) - m);
+    const float wc = cf ? w * cf[p] : w;
+    const float4 hv = hx4[(int64_t)j * a.d4];
+    den += w;
+    acc.x = fmaf(wc, hv.x, acc.x);
+    acc.y = fmaf(wc, hv.y, acc.y);
+    acc.z = fmaf(wc, hv.z, acc.z);
+    acc.w = fmaf(wc, hv.w, acc.w);
+  }
+  const float inv = den > 0.0f ? 1.0f / den : 0.0f;
+  float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (a.bias) b = reinterpret_cast<const float4 *>(a.bias)[c];
+  float4 o;
+  with_act(a.act, [&](auto act_) {
+    constexpr int A = decltype(act_)::value;
+    o.x = act_ct<A>(fmaf(acc.x, inv, b.x), a.act);
+    o.y = act_ct<A>(fmaf(acc.y, inv, b.y), a.act);
+    o.z = act_ct<A>(fmaf(acc.z, inv, b.z), a.act);
+    o.w = act_ct<A>(fmaf(acc.w, inv, b.w), a.act);
+  });
+  reinterpret_cast<float4 *>(a.out)[((int64_t)s * a.n + i) * a.d4 + c] = o;
+}
+
+// uds_gat_aggregate_ex: the grouped EX instantiations, the walking k_gat_aggregate_x for the other widths.
+inline hipError_t launch_gat_aggregate_ex(const GatArgs &a, const GatEx &x, hipStream_t st) {
+  int G, NC;
+  group_shape(a.d4, G, NC);
+  if (G && a.n > 0)
+    return launch_grouped(a, a.n, a.S, a.d4, st, [&](auto g_, auto nc_, dim3 grid) {
+      hipLaunchKernelGGL((k_gat_aggregate_g<decltype(g_)::value, decltype(nc_)::value, true>), grid, dim3(256), 0, st, a, x);
+    });
+  const int64_t per_snap = (int64_t)a.n * a.d4;
+  hipLaunchKernelGGL(k_gat_aggregate_x, dim3((unsigned)((per_snap + 255) / 256), (unsigned)a.S), dim3(256), 0, st, a, x);
   return hipGetLastError();
 }
 

@@ -16,8 +16,9 @@ Conv1D, the resnet prefix sum) and the link->node flow balance of post_proc_tf a
 The remaining post-processing is elementwise gating / clipping on tensors already in HBM and is written with torch
 tensor ops (device plumbing).  Training (`fit_eval`, GradNorm) and `graph_base` 1 / 2 are built for GAT, GCN and
 DiffusionConv (inference and training: `autograd.DiffusionFn` on `uds_diffusion_backward`).
-`use_adj` (per-time-step adjacency rewritten by the control action) is built for GAT as a mask over the CSR entries.
-GRU / LSTM temporal nets run (inference and, at 64 units, training).  Training-time dropout: `layers.Dropout` on `uds_dropout`.  Not built, each raises: `use_adj` with GCN / Diffusion or under autograd,
+`use_adj` (per-time-step adjacency rewritten by the control action) is built for GAT as a mask over the CSR entries, for
+inference and training (`autograd.GatFn(edge_mask=)` on `uds_gat_aggregate_ex` / `uds_gat_backward_ex`).
+GRU / LSTM temporal nets run (inference and, at 64 units, training).  Training-time dropout: `layers.Dropout` on `uds_dropout`.  Not built, each raises: `use_adj` with GCN / Diffusion,
 GeneralConv (a sparse-mode-only Spektral layer the reference's dense call cannot run either).  conv = False -- the reference's non-graph
 baseline, its shipped `*_nncat_*` models -- runs on the same Dense / temporal / cumsum kernels (`_forward_mlp`).
 """

@@ -170,30 +170,33 @@ class GATConv(nn.Module):
     def forward(self, inputs, xb=None, edge_mask=None, attn_dropout=None):
         """edge_mask (..., nnz): per-snapshot 0/1 over the entries of the pattern `a` (`use_adj`, emulator.py:268-271: the
         reference feeds a (S, N, N) adjacency here; the mask is that adjacency gathered at the static pattern's entries --
-        `Emulator.get_adj_action`).  The diagonal always takes part (set_diag).  Inference only.
+        `Emulator.get_adj_action`).  The diagonal always takes part (set_diag).  Under autograd or with attention dropout the
+        layer runs on GatFn (uds_gat_aggregate_ex / uds_gat_backward_ex); otherwise on the inference kernel.
         attn_dropout: a DropoutStream = the layer runs in Keras' training mode and `dropout_rate` > 0: Spektral's dropout on the
-        normalised attention coefficients (`attn_coef_drop = self.dropout(attn_coef)`), one mask entry per (snapshot, pattern entry)."""
+        normalised attention coefficients (`attn_coef_drop = self.dropout(attn_coef)`), one mask entry per (snapshot, pattern entry).
+        With an edge mask the draw still covers every entry of the static pattern, masked or not (S * nnz values, the order
+        and count of the unmasked layer), so the stream stays aligned with a model built without `use_adj`."""
         x, a = inputs
         if self.kernel is None:
             self.build(x.shape[-1] + (0 if xb is None else xb.shape[-1]), x.device)
         h = self._graphs.handle(a, self.add_self_loops)
         xs, lead = _flatten_snapshots(x)
         xbs = None if xb is None else _flatten_snapshots(xb)[0]
+        coef = None
+        if attn_dropout is not None and self.dropout_rate:
+            ones = torch.ones((xs.shape[0], h.nnz), device=xs.device, dtype=torch.float32)
+            coef = _lib.dropout(ones, self.dropout_rate, attn_dropout.seed, attn_dropout.take(ones.numel()))
         if edge_mask is not None:
-            if _ag.grad_on(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias):
-                raise NotImplementedError('GATConv with a per-snapshot edge mask (use_adj) is built for inference')
+            mk = edge_mask.reshape(-1, edge_mask.shape[-1]).to(torch.float32).contiguous()
+            if coef is not None or _ag.grad_on(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias):
+                out = _ag.GatFn.apply(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias,
+                                      self.activation, h, self.precision, coef, mk)
+                return out.reshape(lead + out.shape[-2:])
             fin = xs.shape[-1] + (0 if xbs is None else xbs.shape[-1])
             hx, s_self, s_nbr = _lib.dense_act(xs, self.kernel.reshape(fin, self.channels), None, 'linear', xbs,
                                                attn=(self.attn_kernel_self.reshape(-1), self.attn_kernel_neighs.reshape(-1)))
-            mk = edge_mask.reshape(-1, edge_mask.shape[-1]).to(torch.float32).contiguous()
             out = _lib.gat_aggregate(h, hx, s_self, s_nbr, self.bias, self.activation, edge_mask=mk)
             return out.reshape(lead + out.shape[-2:])
-        coef = None
-        if attn_dropout is not None and self.dropout_rate:
-            if edge_mask is not None:
-                raise NotImplementedError('attention dropout together with a per-snapshot edge mask (use_adj) is not built')
-            ones = torch.ones((xs.shape[0], h.nnz), device=xs.device, dtype=torch.float32)
-            coef = _lib.dropout(ones, self.dropout_rate, attn_dropout.seed, attn_dropout.take(ones.numel()))
         if coef is not None or _ag.grad_on(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias):
             out = _ag.GatFn.apply(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias,
                                   self.activation, h, self.precision, coef)
@@ -592,11 +595,10 @@ class SpatialLayer(nn.Module):
     def forward(self, x, e, xb=None, eb=None, adj_mask=None, attn_dropout=None):
         """xb / eb: 32 extra columns appended to a 64-wide x / e (`concat([x, b])`, emulator.py:260-262) -- read in place
         by the fused kernel; every other path concatenates.  adj_mask (..., nnz of the node adjacency): the per-snapshot
-        adjacency of `use_adj` (emulator.py:268-271,282) -- node side through the masked aggregation kernel.
+        adjacency of `use_adj` (emulator.py:268-271,282) -- node side through the masked aggregation kernels (under autograd
+        or attention dropout: GatFn on uds_gat_aggregate_ex / uds_gat_backward_ex).
         attn_dropout: a DropoutStream = Keras' training mode for the two GATConv layers (Spektral's attention dropout, rate 0.5)."""
         if adj_mask is not None:
-            if attn_dropout is not None:
-                raise NotImplementedError('use_adj in training mode (attention dropout) is not built')
             if self.conv != 'GAT':
                 raise NotImplementedError('use_adj is built for conv=GAT (GCN / Diffusion would re-normalise the filter per snapshot)')
             if xb is not None:
@@ -607,8 +609,9 @@ class SpatialLayer(nn.Module):
             es, lead_e = _flatten_snapshots(e)
             net = self.network()
             x_e, e_x = self.dense_xe(es), self.dense_ex(xs)
-            ox = self.gat_x([xs, net.adj], xb=self.node_edge_n(x_e), edge_mask=adj_mask)
-            oe = self.gat_e([es, net.edge_adj], xb=self.node_edge_e(e_x))
+            # attention-dropout draws in the order of the unmasked training branch below: gat_x, then gat_e
+            ox = self.gat_x([xs, net.adj], xb=self.node_edge_n(x_e), edge_mask=adj_mask, attn_dropout=attn_dropout)
+            oe = self.gat_e([es, net.edge_adj], xb=self.node_edge_e(e_x), attn_dropout=attn_dropout)
             self.last_path = 'unfused'
             return ox.reshape(lead_x + ox.shape[-2:]), oe.reshape(lead_e + oe.shape[-2:])
         fused_split = (xb is not None or eb is not None) and self.conv == 'GAT' and self.precision == 'bf16x3' and \

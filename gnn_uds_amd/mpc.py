@@ -79,7 +79,9 @@ def hessp(emul, y, p, state, runoff, edge_state, n_step, n_act, r_step, targets,
         H p ~ (grad f(y + eps p) - grad f(y - eps p)) / (2 eps),    eps = 1e-2 / max|p|  (settings live in [0, 1]),
     two gradient evaluations = two batched forward + backward passes through the same kernels.  The objective is piecewise
     smooth (relu, |.| of the roughness term, hard gates): like the exact second derivative, the difference is meaningful
-    away from the kinks only.  Returns (pop, n_step*n_act)."""
+    away from the kinks only.  With `use_adj` the adjacency flips there too: a setting within eps * |p| of an integer gives
+    the two gradients different adjacencies (the cast to int removes an entry below 1), so the quotient spans the jump.
+    Returns (pop, n_step*n_act)."""
     p = p.to(y.dtype)
     if eps is None:
         eps = 1e-2 / max(float(p.abs().max()), 1e-12)

@@ -369,6 +369,24 @@ int uds_gat_backward_coef(const uds_csr_t *g, const uds_csr_t *gt, const int32_t
                           int64_t S, int64_t d, float *alpha_ws, float *de_ws, float *d_hx, float *ds_self, float *ds_nbr,
                           uds_stream_t stream);
 
+/* uds_gat_aggregate with an optional per-snapshot EDGE MASK and an optional attention-dropout COEF, for training `use_adj`
+ * models (emulator.py:268-271,343-362: the action rewrites the adjacency entries of the actuated links per time step and GAT
+ * casts them to int, so a setting < 1 removes the entry; the training step, emulator.py:457-484, differentiates through it).
+ * edge_mask (S, nnz) or NULL: entry p of snapshot s takes part iff edge_mask[s, p] != 0 or p is its row's diagonal (spektral
+ * restores the diagonal with set_diag after the rewrite).  The softmax runs over the surviving entries only (a masked logit
+ * is -10e9 in the reference: its weight is exactly 0).  coef (S, nnz) or NULL multiplies the normalised coefficients as in
+ * uds_gat_aggregate_coef.  With an all-ones mask and no coef the result is bitwise that of uds_gat_aggregate. */
+int uds_gat_aggregate_ex(const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr, const float *bias,
+                         const float *edge_mask, const float *coef, int64_t S, int64_t d, int act, float *out,
+                         uds_stream_t stream);
+/* Reverse mode of uds_gat_aggregate_ex: arguments and outputs as uds_gat_backward_coef, plus the same edge_mask (or NULL).
+ * A masked entry has alpha = de = 0 in the workspace, so it contributes nothing to d_hx, ds_self or ds_nbr.  With an
+ * all-ones mask and no coef the results are bitwise those of uds_gat_backward. */
+int uds_gat_backward_ex(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *perm_t, const float *grad, const float *hx,
+                        const float *s_self, const float *s_nbr, const float *a_self, const float *a_nbr,
+                        const float *edge_mask, const float *coef, int64_t S, int64_t d, float *alpha_ws, float *de_ws,
+                        float *d_hx, float *ds_self, float *ds_nbr, uds_stream_t stream);
+
 /* out[k] = sum_s <a[s, row(k), :], b[s, col(k), :]> for every entry k of the pattern (row-major order): the gradient
  * of the per-entry values of uds_csr_spmm (a = dL/dout (S,n_rows,F), b = x (S,n_cols,F)) -- NodeEdge.weight / bias
  * on the incidence support (emulator.py:34-45). */
