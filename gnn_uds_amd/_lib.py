@@ -46,6 +46,10 @@ SYMBOLS = {
     'uds_dropout': (_c_int, [_c_ptr, _c_i64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _c_ptr, _c_ptr]),
     'uds_recurrent_forward_train': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
     'uds_recurrent_backward': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_recurrent_bwd_packed_bytes': (_c_i64, [_c_i64, _c_int]),
+    'uds_recurrent_pack_bwd': (_c_int, [_c_ptr, _c_i64, _c_int, _c_ptr, _c_ptr]),
+    'uds_recurrent_backward_h': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr,
+                                          _c_ptr]),
     'uds_rowgemm_packed_bytes': (_c_i64, [_c_i64, _c_i64]),
     'uds_rowgemm_pack': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr]),
     'uds_gat_aggregate_masked': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
@@ -449,28 +453,72 @@ def recurrent_forward_train(xp, recurrent_kernel, recurrent_bias, kind):
     return out, c
 
 
+RECURRENT_TRAIN_WIDTHS = tuple(range(16, 129, 16))      # units the back-propagation-through-time kernels are built for
+
+
+def recurrent_bwd_route(units):
+    """Which C entry back-propagates a GRU / LSTM layer of `units` units: 64 is uds_recurrent_backward (the kernel the 64-unit
+    emulator has always trained on), every other multiple of 16 from 16 to 128 uds_recurrent_backward_h; None: not built."""
+    if units == 64:
+        return 'uds_recurrent_backward'
+    return 'uds_recurrent_backward_h' if units in RECURRENT_TRAIN_WIDTHS else None
+
+
+def recurrent_bwd_packed_bytes(units, G):
+    """Bytes of the packed image of an (units, G*units) recurrent kernel: U_g and U_g^T for every gate, each ceil(units / 32)
+    k-steps x units / 16 feature blocks of a bf16 hi and a lo fragment (64 lanes x 16 bytes); 0: width not built.  The host
+    restatement of uds_recurrent_bwd_packed_bytes."""
+    if units not in RECURRENT_TRAIN_WIDTHS or G not in (3, 4):
+        return 0
+    return 2 * G * ((units + 31) // 32) * (units // 16) * 2 * 64 * 16
+
+
 def recurrent_pack_bwd(recurrent_kernel):
-    """MFMA fragments for uds_recurrent_backward: the G 64 x 64 slices of U, then of U_g^T (64 units only)."""
-    G = recurrent_kernel.shape[1] // 64
-    if tuple(recurrent_kernel.shape) != (64, G * 64) or G not in (3, 4):
-        raise UdsError('recurrent_pack_bwd: recurrent kernel %r (64 x G*64 with G = 3 or 4)' % (tuple(recurrent_kernel.shape),))
-    sl = [recurrent_kernel[:, 64 * g:64 * (g + 1)] for g in range(G)]
-    return torch.cat([rowgemm_pack(m.contiguous()) for m in sl] + [rowgemm_pack(m.t().contiguous()) for m in sl]).contiguous()
+    """MFMA fragments for recurrent_backward: the G H x H slices of U, then of U_g^T, H = the layer's units (a multiple of 16
+    from 16 to 128).  64 units: the uds_rowgemm_pack image uds_recurrent_backward takes; other widths: uds_recurrent_pack_bwd."""
+    H = recurrent_kernel.shape[0]
+    G = recurrent_kernel.shape[1] // max(H, 1)
+    route = recurrent_bwd_route(H)
+    if recurrent_kernel.dim() != 2 or tuple(recurrent_kernel.shape) != (H, G * H) or G not in (3, 4) or route is None:
+        raise UdsError('recurrent_pack_bwd: recurrent kernel %r (H x G*H with G = 3 or 4 and H one of %r)'
+                       % (tuple(recurrent_kernel.shape), RECURRENT_TRAIN_WIDTHS))
+    if route == 'uds_recurrent_backward':
+        sl = [recurrent_kernel[:, 64 * g:64 * (g + 1)] for g in range(G)]
+        return torch.cat([rowgemm_pack(m.contiguous()) for m in sl] + [rowgemm_pack(m.t().contiguous()) for m in sl]).contiguous()
+    lib = load()
+    nbytes = lib.uds_recurrent_bwd_packed_bytes(H, G - 3)
+    if nbytes != recurrent_bwd_packed_bytes(H, G):
+        raise UdsError('recurrent_pack_bwd: the library packs %d bytes for %d units, the binding expects %d' % (nbytes, H, recurrent_bwd_packed_bytes(H, G)))
+    out = torch.empty(nbytes // 4, device=recurrent_kernel.device, dtype=torch.float32)
+    _check(lib.uds_recurrent_pack_bwd(_dev(recurrent_kernel.contiguous(), 'recurrent_kernel'), H, G - 3, out.data_ptr(), _stream()),
+           'uds_recurrent_pack_bwd')
+    return out
 
 
 def recurrent_backward(xp, packed, recurrent_bias, h, c, gh, kind):
-    """(dxp (B, T, R, G*64), darec (G, B, T, R, 64)) of a 64-unit GRU / LSTM layer: back-propagation through time in one launch."""
+    """(dxp (B, T, R, G*H), darec (G, B, T, R, H)) of a GRU / LSTM layer of H units (a multiple of 16 from 16 to 128): back-
+    propagation through time in one launch.  64 units run uds_recurrent_backward, other widths uds_recurrent_backward_h."""
     lib = load()
     B, T, R, GH = xp.shape
     G = {'GRU': 3, 'LSTM': 4}[kind]
-    if GH != G * 64 or tuple(h.shape) != (B, T, R, 64) or tuple(gh.shape) != (B, T, R, 64):
-        raise UdsError('recurrent_backward: xp %r, h %r, gh %r for a 64-unit %s' % (tuple(xp.shape), tuple(h.shape), tuple(gh.shape), kind))
+    H = h.shape[-1]
+    route = recurrent_bwd_route(H)
+    if GH != G * H or tuple(h.shape) != (B, T, R, H) or tuple(gh.shape) != (B, T, R, H) or route is None:
+        raise UdsError('recurrent_backward: xp %r, h %r, gh %r for a %s of one of %r units'
+                       % (tuple(xp.shape), tuple(h.shape), tuple(gh.shape), kind, RECURRENT_TRAIN_WIDTHS))
+    if packed.numel() * 4 != recurrent_bwd_packed_bytes(H, G):
+        raise UdsError('recurrent_backward: packed image of %d bytes, %d units need %d' % (packed.numel() * 4, H, recurrent_bwd_packed_bytes(H, G)))
     dxp = torch.empty_like(xp)
-    darec = torch.empty((G, B, T, R, 64), device=xp.device, dtype=torch.float32)
+    darec = torch.empty((G, B, T, R, H), device=xp.device, dtype=torch.float32)
     if dxp.numel():
-        _check(lib.uds_recurrent_backward(_dev(xp, 'xp'), packed.data_ptr(), _dev(recurrent_bias, 'recurrent_bias', True), _dev(h, 'h'),
-                                          _dev(c, 'c', True), _dev(gh, 'gh'), B, T, R, 0 if kind == 'GRU' else 1, _dev(dxp, 'dxp'),
-                                          _dev(darec, 'darec'), _stream()), 'uds_recurrent_backward')
+        if route == 'uds_recurrent_backward':
+            _check(lib.uds_recurrent_backward(_dev(xp, 'xp'), packed.data_ptr(), _dev(recurrent_bias, 'recurrent_bias', True), _dev(h, 'h'),
+                                              _dev(c, 'c', True), _dev(gh, 'gh'), B, T, R, 0 if kind == 'GRU' else 1, _dev(dxp, 'dxp'),
+                                              _dev(darec, 'darec'), _stream()), 'uds_recurrent_backward')
+        else:
+            _check(lib.uds_recurrent_backward_h(_dev(xp, 'xp'), packed.data_ptr(), _dev(recurrent_bias, 'recurrent_bias', True), _dev(h, 'h'),
+                                                _dev(c, 'c', True), _dev(gh, 'gh'), B, T, R, H, 0 if kind == 'GRU' else 1, _dev(dxp, 'dxp'),
+                                                _dev(darec, 'darec'), _stream()), 'uds_recurrent_backward_h')
     return dxp, darec
 
 

@@ -96,7 +96,8 @@ class DenseFn(torch.autograd.Function):
     def forward(ctx, x, kernel, bias, module, act):
         xc = x.contiguous()
         fi = xc.shape[-1]
-        if module.precision == 'bf16x3' and _lib.rowgemm_supported(fi, fi, module.units):
+        # forward_precision: a module may ask for the exact forward and still take its gradients on the matrix cores (_Recurrent)
+        if getattr(module, 'forward_precision', module.precision) == 'bf16x3' and _lib.rowgemm_supported(fi, fi, module.units):
             from .layers import _packed_kernel
             y = _lib.rowgemm_forward(xc, _packed_kernel(module, kernel), bias, module.units, act)
         else:
@@ -144,11 +145,13 @@ class RemainderFn(torch.autograd.Function):
 
 
 class RecurrentFn(torch.autograd.Function):
-    """The time recurrence of a 64-unit keras GRU / LSTM on the input projection xp (B, T, R, G*64): forward exact fp32
-    (uds_recurrent_forward_train), backward = back-propagation through time in one launch on the matrix cores
-    (uds_recurrent_backward: gates recomputed from the saved xp and h), the recurrent kernel's gradient one split-K weight-
-    gradient call per gate with a time shift of one, the recurrent bias its bias row.  The Dense that made xp carries the
-    rest (kernel, input bias, dx).  Reference: emulator.py:158-161 inside the GradientTape of fit_eval (:457-484)."""
+    """The time recurrence of a keras GRU / LSTM of H units (a multiple of 16 from 16 to 128) on the input projection xp
+    (B, T, R, G*H): forward exact fp32 (uds_recurrent_forward_train), backward = back-propagation through time in one launch
+    on the matrix cores (uds_recurrent_backward at 64 units, uds_recurrent_backward_h otherwise: gates recomputed from the
+    saved xp and h), the recurrent kernel's gradient one split-K weight-gradient call per gate and 64-column block with a
+    time shift of one, the recurrent bias its bias row (up to 64 units) or the column sum of darec (above: h and the bias
+    row together exceed uds_wgrad's 128 input rows).  The Dense that made xp carries the rest (kernel, input bias, dx).
+    Reference: emulator.py:158-161 inside the GradientTape of fit_eval (:457-484)."""
 
     @staticmethod
     def forward(ctx, xp, recurrent_kernel, recurrent_bias, kind, precision):
@@ -161,15 +164,24 @@ class RecurrentFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gh):
         xp, U, rb, h, c = ctx.saved_tensors
-        G = U.shape[1] // 64
+        H = U.shape[0]
+        G = U.shape[1] // H
         dxp, darec = _lib.recurrent_backward(xp, _lib.recurrent_pack_bwd(U), rb, h, c, gh.contiguous(), ctx.kind)
         dU = drb = None
         if ctx.needs_input_grad[1] or (rb is not None and ctx.needs_input_grad[2]):
             want_b = rb is not None and ctx.needs_input_grad[2]
-            parts = [weight_grad(h, darec[g], ctx.precision, want_b, shift=1) for g in range(G)]      # dU_g = sum_t h[t-1]^T darec_g[t]
-            dU = torch.cat([p[0] for p in parts], dim=1)
-            if want_b:
-                drb = torch.cat([p[1] if p[1] is not None else darec[g].reshape(-1, 64).sum(0) for g, p in enumerate(parts)])
+            if H <= 64:
+                parts = [weight_grad(h, darec[g], ctx.precision, want_b, shift=1) for g in range(G)]      # dU_g = sum_t h[t-1]^T darec_g[t]
+                dU = torch.cat([p[0] for p in parts], dim=1)
+                if want_b:
+                    drb = torch.cat([p[1] if p[1] is not None else darec[g].reshape(-1, H).sum(0) for g, p in enumerate(parts)])
+            else:
+                # uds_wgrad takes 64 output columns and 128 input rows with the bias row: one call per gate and 64-column block,
+                # the bias as the column sum of darec
+                dU = torch.cat([weight_grad(h, darec[g][..., c0:c0 + 64].contiguous(), ctx.precision, False, shift=1)[0]
+                                for g in range(G) for c0 in range(0, H, 64)], dim=1)
+                if want_b:
+                    drb = darec.reshape(G, -1, H).sum(1).reshape(-1)
         return (dxp if ctx.needs_input_grad[0] else None), dU, drb, None, None
 
 

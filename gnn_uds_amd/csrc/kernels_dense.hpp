@@ -344,4 +344,91 @@ inline hipError_t launch_recurrent(const RecurrentArgs &a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// The same recurrence where U does not fit the LDS (a GRU above 116 units, an LSTM above 100: hidden_dim = 128).  U stays
+// in global memory -- at most 256 KiB at 128 units, read by every workgroup and so cache-resident -- and is streamed through
+// registers: thread (row group rg, feature f) owns feature f of RPT rows, so each U element it loads (coalesced over f) is
+// used RPT times; only the states live in LDS.  Per element the arithmetic is k_recurrent's, in the same order: exact fp32,
+// the same bits.
+constexpr int RC_STREAM_RPT = 8;
+
+template <int G>
+__global__ __launch_bounds__(256) void k_recurrent_stream(RecurrentArgs a) {
+  constexpr int RPT = RC_STREAM_RPT;
+  extern __shared__ float smem_rs[];        // rows x H: the previous state
+  const int H = a.H, GH = G * H;
+  const int tid = threadIdx.x, rg = tid / H, f = tid - rg * H;
+  float *hs = smem_rs + (size_t)rg * RPT * H;
+  const int64_t total = (int64_t)a.B * a.R;
+  int64_t base0[RPT];                       // row index (b * T * R + n) at t = 0, -1: beyond the last row
+#pragma unroll
+  for (int i = 0; i < RPT; ++i) {
+    const int64_t grow = (int64_t)blockIdx.x * a.rows + rg * RPT + i;      // global row = b * R + n
+    const int64_t b = grow / a.R;
+    base0[i] = grow < total ? b * a.T * a.R + (grow - b * a.R) : -1;
+    hs[i * H + f] = 0.0f;
+  }
+  float rb[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) rb[g] = a.rb ? a.rb[g * H + f] : 0.0f;
+  float c[RPT], h[RPT];
+#pragma unroll
+  for (int i = 0; i < RPT; ++i) c[i] = h[i] = 0.0f;
+  __syncthreads();
+  for (int t = 0; t < a.T; ++t) {
+    float acc[G][RPT];
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+#pragma unroll
+      for (int i = 0; i < RPT; ++i) acc[g][i] = rb[g];
+    for (int k = 0; k < H; ++k) {
+      float u[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) u[g] = a.U[k * GH + g * H + f];
+#pragma unroll
+      for (int i = 0; i < RPT; ++i) {
+        const float hk = hs[i * H + k];
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g][i] = fmaf(hk, u[g], acc[g][i]);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) {
+      const bool live = base0[i] >= 0;
+      const int64_t base = base0[i] + (int64_t)t * a.R;
+      float xg[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) xg[g] = live ? a.xp[base * GH + g * H + f] : 0.0f;
+      if (G == 3) {
+        const float z = sigmoidf_(xg[0] + acc[0][i]), r = sigmoidf_(xg[1] + acc[1][i]);
+        const float cand = tanhf(xg[2] + r * acc[2][i]);
+        h[i] = z * h[i] + (1.0f - z) * cand;
+      } else {
+        const float ig = sigmoidf_(xg[0] + acc[0][i]), fg = sigmoidf_(xg[1] + acc[1][i]);
+        const float cg = tanhf(xg[2] + acc[2][i]), og = sigmoidf_(xg[G - 1] + acc[G - 1][i]);
+        c[i] = fg * c[i] + ig * cg;
+        h[i] = og * tanhf(c[i]);
+      }
+      if (live) a.out[base * H + f] = h[i];
+      if (G == 4 && live && a.c_out) a.c_out[base * H + f] = c[i];
+    }
+    __syncthreads();                 // every thread has read the previous state
+#pragma unroll
+    for (int i = 0; i < RPT; ++i) hs[i * H + f] = h[i];
+    __syncthreads();
+  }
+}
+
+// row groups per workgroup of k_recurrent_stream (blockDim = groups * H <= 256), rows per workgroup = groups * RC_STREAM_RPT
+inline int recurrent_stream_groups(int H) { return H >= 256 ? 1 : 256 / H; }
+
+inline hipError_t launch_recurrent_stream(const RecurrentArgs &a, hipStream_t st) {      // a.rows = recurrent_stream_groups(H) * RC_STREAM_RPT
+  const int64_t total = (int64_t)a.B * a.R;
+  const unsigned grid = (unsigned)((total + a.rows - 1) / a.rows);
+  const size_t lds = (size_t)a.rows * a.H * sizeof(float);
+  const int threads = a.rows / RC_STREAM_RPT * a.H;
+  if (a.G == 3) hipLaunchKernelGGL(k_recurrent_stream<3>, dim3(grid), dim3(threads), lds, st, a);
+  else hipLaunchKernelGGL(k_recurrent_stream<4>, dim3(grid), dim3(threads), lds, st, a);
+  return hipGetLastError();
+}
+
 }  // namespace uds

@@ -364,11 +364,17 @@ int uds_recurrent_forward_train(const float *xp, const float *U, const float *rb
   const int G = kind == 0 ? 3 : 4;
   const int rows = (int)std::max<int64_t>(1, 256 / H);
   const size_t lds = ((size_t)H * G * H + (size_t)rows * H) * sizeof(float);
-  UDS_REQUIRE(lds <= 160 * 1024, "uds_recurrent_forward: the recurrent kernel (%lld x %lld floats) does not fit the 160 KiB LDS", (long long)H,
-              (long long)(G * H));
-  UDS_REQUIRE((B * R + rows - 1) / rows < INT32_MAX, "uds_recurrent_forward: too many rows");
-  uds::RecurrentArgs a{xp, U, rb, out, c_out, (int)B, (int)T, (int)R, (int)H, G, rows};
-  hipError_t e = uds::launch_recurrent(a, static_cast<hipStream_t>(stream));
+  hipError_t e;
+  if (lds <= 160 * 1024) {
+    UDS_REQUIRE((B * R + rows - 1) / rows < INT32_MAX, "uds_recurrent_forward: too many rows");
+    uds::RecurrentArgs a{xp, U, rb, out, c_out, (int)B, (int)T, (int)R, (int)H, G, rows};
+    e = uds::launch_recurrent(a, static_cast<hipStream_t>(stream));
+  } else {      // U (H x G*H floats) does not fit the LDS: streamed from global memory, the same arithmetic
+    const int srows = uds::recurrent_stream_groups((int)H) * uds::RC_STREAM_RPT;
+    UDS_REQUIRE((B * R + srows - 1) / srows < INT32_MAX, "uds_recurrent_forward: too many rows");
+    uds::RecurrentArgs a{xp, U, rb, out, c_out, (int)B, (int)T, (int)R, (int)H, G, srows};
+    e = uds::launch_recurrent_stream(a, static_cast<hipStream_t>(stream));
+  }
   if (e != hipSuccess) return fail(UDS_EHIP, "uds_recurrent_forward: launch -> %s", hipGetErrorString(e));
   return UDS_OK;
 }
@@ -388,6 +394,42 @@ int uds_recurrent_backward(const float *xp, const void *packed, const float *b_r
   hipError_t e = kind == 0 ? uds::launch_recurrent_bwd_t<3>(a, static_cast<hipStream_t>(stream))
                            : uds::launch_recurrent_bwd_t<4>(a, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return fail(UDS_EHIP, "uds_recurrent_backward: launch -> %s", hipGetErrorString(e));
+  return UDS_OK;
+}
+
+int64_t uds_recurrent_bwd_packed_bytes(int64_t H, int kind) {
+  if (!uds::recurrent_bwd_width_ok(H) || (kind != 0 && kind != 1)) return 0;
+  return (int64_t)2 * (kind == 0 ? 3 : 4) * uds::recurrent_bwd_slice((int)H) * 16;
+}
+
+int uds_recurrent_pack_bwd(const float *U, int64_t H, int kind, void *packed, uds_stream_t stream) {
+  UDS_REQUIRE(U && packed && aligned16(packed), "uds_recurrent_pack_bwd: NULL / misaligned argument");
+  const int64_t bytes = uds_recurrent_bwd_packed_bytes(H, kind);
+  UDS_REQUIRE(bytes > 0, "uds_recurrent_pack_bwd: H=%lld kind=%d (H a multiple of 16 from 16 to 128; kind 0 = GRU, 1 = LSTM)", (long long)H, kind);
+  const int total = (int)(bytes / 16 / 2);      // one thread per (slice, k-step, block, lane): a hi and a lo fragment
+  hipLaunchKernelGGL(uds::k_pack_recurrent_bwd, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), U, (int)H,
+                     kind == 0 ? 3 : 4, reinterpret_cast<uint4 *>(packed));
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(UDS_EHIP, "uds_recurrent_pack_bwd: launch -> %s", hipGetErrorString(e));
+  return UDS_OK;
+}
+
+int uds_recurrent_backward_h(const float *xp, const void *packed, const float *b_rec, const float *h, const float *c, const float *gh,
+                             int64_t B, int64_t T, int64_t R, int64_t H, int kind, float *dxp, float *darec, uds_stream_t stream) {
+  UDS_REQUIRE(xp && packed && h && gh && dxp && darec, "uds_recurrent_backward_h: NULL argument");
+  UDS_REQUIRE(kind == 0 || kind == 1, "uds_recurrent_backward_h: kind %d (0 = GRU, 1 = LSTM)", kind);
+  UDS_REQUIRE(uds::recurrent_bwd_width_ok(H), "uds_recurrent_backward_h: %lld units (a multiple of 16 from 16 to 128)", (long long)H);
+  UDS_REQUIRE(kind == 0 || c, "uds_recurrent_backward_h: the LSTM needs the cell states of the forward pass (uds_recurrent_forward_train)");
+  UDS_REQUIRE(B >= 0 && T >= 0 && R >= 0, "uds_recurrent_backward_h: bad sizes B=%lld T=%lld R=%lld", (long long)B, (long long)T, (long long)R);
+  UDS_REQUIRE(aligned16(xp) && aligned16(packed) && aligned16(b_rec) && aligned16(h) && aligned16(c) && aligned16(gh) && aligned16(dxp) &&
+                  aligned16(darec), "uds_recurrent_backward_h: buffers must be 16-byte aligned");
+  if (B == 0 || T == 0 || R == 0) return UDS_OK;
+  const int64_t n_blocks = (R + 15) / 16;
+  UDS_REQUIRE(B * n_blocks < INT32_MAX && T < INT32_MAX, "uds_recurrent_backward_h: too many rows");
+  uds::RecurrentBwdArgs a{xp, b_rec, reinterpret_cast<const uint4 *>(packed), h, c, gh, dxp, darec, (int)B, (int)T, (int)R, (int)n_blocks};
+  hipError_t e = kind == 0 ? uds::launch_recurrent_bwd_h<3>(a, (int)H, static_cast<hipStream_t>(stream))
+                           : uds::launch_recurrent_bwd_h<4>(a, (int)H, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(UDS_EHIP, "uds_recurrent_backward_h: launch -> %s", hipGetErrorString(e));
   return UDS_OK;
 }
 

@@ -18,7 +18,7 @@ tensor ops (device plumbing).  Training (`fit_eval`, GradNorm) and `graph_base` 
 DiffusionConv (inference and training: `autograd.DiffusionFn` on `uds_diffusion_backward`).
 `use_adj` (per-time-step adjacency rewritten by the control action) is built for GAT as a mask over the CSR entries, for
 inference and training (`autograd.GatFn(edge_mask=)` on `uds_gat_aggregate_ex` / `uds_gat_backward_ex`).
-GRU / LSTM temporal nets run (inference and, at 64 units, training).  Training-time dropout: `layers.Dropout` on `uds_dropout`.  Not built, each raises: `use_adj` with GCN / Diffusion,
+GRU / LSTM temporal nets run (inference and, at 16 to 128 units in steps of 16, training).  Training-time dropout: `layers.Dropout` on `uds_dropout`.  Not built, each raises: `use_adj` with GCN / Diffusion,
 GeneralConv (a sparse-mode-only Spektral layer the reference's dense call cannot run either).  conv = False -- the reference's non-graph
 baseline, its shipped `*_nncat_*` models -- runs on the same Dense / temporal / cumsum kernels (`_forward_mlp`).
 """
@@ -62,6 +62,9 @@ class Conv1D(nn.Module):
 class _DenseShim:
     """What DenseFn reads of its module, for a bare (kernel, bias) pair."""
 
+    forward_precision = 'fp32'      # the recurrent layers' input projection is exact fp32 at every width (at 64 units its 192 / 256
+                                    # columns never fitted the matrix-core row GEMM; a 16-unit GRU's 48 would)
+
     def __init__(self, precision, units):
         self.precision, self.units = precision, units
 
@@ -72,7 +75,8 @@ class _Recurrent(nn.Module):
     fp32; a 64 -> 64 layer with precision='bf16x3' is ONE launch on the matrix cores (uds_recurrent_fused).  Parameters keep the Keras names and shapes -- `kernel` (F, G*units), `recurrent_kernel` (units, G*units), `bias`
     ((2, 3*units) for the TF2 GRU with reset_after=True: input and recurrent bias; (4*units,) for the LSTM) -- and the
     Keras initialisers (glorot_uniform, orthogonal, zeros with the LSTM's forget-gate bias at one).  Under autograd (training) the
-    layer runs Dense + `RecurrentFn` (autograd.py): back-propagation through time is one HIP launch (uds_recurrent_backward)."""
+    layer runs Dense + `RecurrentFn` (autograd.py): back-propagation through time is one HIP launch (uds_recurrent_backward at 64
+    units, uds_recurrent_backward_h at every other multiple of 16 from 16 to 128; other widths raise NotImplementedError)."""
     KIND, G = None, 0
 
     def __init__(self, units, return_sequences=True, in_features=None, generator=None, precision='fp32'):
@@ -96,11 +100,11 @@ class _Recurrent(nn.Module):
         if _ag.grad_on(x, self.kernel, self.recurrent_kernel, self.bias):
             # training (fit_eval, emulator.py:457-484): input projection through the Dense operator, the recurrence through
             # RecurrentFn (exact-fp32 forward, back-propagation through time on the matrix cores)
-            if self.units != 64:
-                raise NotImplementedError('the %s backward kernel is built for 64 units (hidden_dim = 64, the reference default)' % self.KIND)
+            if _lib.recurrent_bwd_route(self.units) is None:
+                raise NotImplementedError('the %s backward kernels are built for %s units (hidden_dim a multiple of 16 from 16 to 128), not %d'
+                                          % (self.KIND, ', '.join(str(w) for w in _lib.RECURRENT_TRAIN_WIDTHS), self.units))
             b_in, b_rec = (self.bias[0], self.bias[1]) if self.KIND == 'GRU' else (self.bias, None)
-            shim = _DenseShim(self.precision, self.G * self.units)
-            xp = _ag.DenseFn.apply(x, self.kernel, b_in.contiguous(), shim, 'linear')
+            xp = self._projection(x, b_in, True)
             return _ag.RecurrentFn.apply(xp, self.recurrent_kernel, None if b_rec is None else b_rec.contiguous(), self.KIND, self.precision)
         x = x.contiguous()
         b_in, b_rec = (self.bias[0].contiguous(), self.bias[1].contiguous()) if self.KIND == 'GRU' else (self.bias, None)
@@ -127,8 +131,21 @@ class _Recurrent(nn.Module):
                 for g, pk in enumerate(packed_w):
                     _lib.rowgemm_cat(x, None, pk, fold[64 * g:64 * (g + 1)].contiguous(), 64, 'linear', out=xp, col0=64 * g)
                 return _lib.recurrent_fused(xp, packed_u, None, b_rec, self.KIND, projected=True)
-        xp = _lib.dense_act(x, self.kernel, b_in, 'linear')
-        return _lib.recurrent_forward(xp, self.recurrent_kernel, b_rec, self.KIND)
+        return _lib.recurrent_forward(self._projection(x, b_in, False), self.recurrent_kernel, b_rec, self.KIND)
+
+    def _projection(self, x, b_in, train):
+        """x @ kernel + input bias for every time step, (B, T, R, G*units): one Dense launch up to 256 columns (what uds_dense_act
+        takes: every width up to 80 units for the GRU, 64 for the LSTM), 256-column pieces above; train: through DenseFn."""
+        gh = self.G * self.units
+        pieces = []
+        for c0 in range(0, gh, 256):
+            k, b = (self.kernel, b_in) if gh <= 256 else (self.kernel[:, c0:c0 + 256], b_in[c0:c0 + 256])
+            if train:
+                k = k.contiguous()
+                pieces.append(_ag.DenseFn.apply(x, k, b.contiguous(), _DenseShim(self.precision, k.shape[1]), 'linear'))
+            else:
+                pieces.append(_lib.dense_act(x, k.contiguous(), b.contiguous(), 'linear'))
+        return pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=-1)
 
 
 class GRU(_Recurrent):

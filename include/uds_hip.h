@@ -97,7 +97,8 @@ int uds_conv1d_causal(const float *x, int64_t B, int64_t T, int64_t R, int64_t F
  * the causal Conv1D), exact fp32.  xp (B, T, R, G*H) = x @ kernel + input bias for every time step (uds_dense_act), U
  * (H, G*H) the recurrent kernel, rb (G*H) the recurrent bias or NULL; kind 0 = GRU (G = 3, gate order z, r, h, TF2's
  * reset_after=True form, sigmoid recurrent activation), 1 = LSTM (G = 4: i, f, c, o).  out (B, T, R, H) = the hidden state
- * after every step, initial state zero.  H <= 256 and H * G*H floats must fit the LDS. */
+ * after every step, initial state zero.  H <= 256.  Where H * G*H floats fit the LDS (a GRU up to 116 units, an LSTM up to
+ * 100) U is staged there once per workgroup; above that it is streamed from global memory, the same arithmetic. */
 int uds_recurrent_forward(const float *xp, const float *U, const float *rb, int64_t B, int64_t T, int64_t R, int64_t H,
                           int kind, float *out, uds_stream_t stream);
 
@@ -105,7 +106,8 @@ int uds_recurrent_forward(const float *xp, const float *U, const float *rb, int6
  * get_tem_nets, emulator.py:158-161; `recurrent: GRU` is the default of every block of utils/config.yaml): c_out (B, T, R, H)
  * additionally receives the LSTM's cell state after every step (NULL: not kept; ignored for the GRU).
  *
- * uds_recurrent_backward: back-propagation through time of a 64-unit layer, one launch on the matrix cores (split-bf16).
+ * uds_recurrent_backward: back-propagation through time of a 64-unit layer, one launch on the matrix cores (split-bf16);
+ * uds_recurrent_backward_h below is the same for every width from 16 to 128.
  * xp, h (the forward output), c (the LSTM's cell states, NULL for the GRU) and gh = dL/dh, all (B, T, R, .) as above;
  * packed = the G 64-column slices of U in uds_rowgemm_pack layout followed by the G slices of U_g^T (16 KiB each).
  * Outputs: dxp (B, T, R, G*64) = gradient of the input projection (the Dense backward takes it from there: dW = x^T dxp,
@@ -117,6 +119,22 @@ int uds_recurrent_forward_train(const float *xp, const float *U, const float *rb
 int uds_recurrent_backward(const float *xp, const void *packed, const float *b_rec, const float *h, const float *c,
                            const float *gh, int64_t B, int64_t T, int64_t R, int kind, float *dxp, float *darec,
                            uds_stream_t stream);
+
+/* uds_recurrent_backward for a layer of H units, H a multiple of 16 from 16 to 128 (`hidden_dim` of utils/config.yaml is the
+ * width of every temporal layer: emulator.py:158-161 under the GradientTape of fit_eval, emulator.py:457-484).  Arguments
+ * and outputs as uds_recurrent_backward with 64 replaced by H: xp / dxp (B, T, R, G*H), h / c / gh (B, T, R, H), b_rec (G*H)
+ * or NULL, darec (G, B, T, R, H).  H = 64 is uds_recurrent_backward itself (the same kernel, launch and bits).
+ * packed = uds_recurrent_pack_bwd(U (H, G*H) row-major), uds_recurrent_bwd_packed_bytes(H, kind) bytes (0: width or kind not
+ * supported): the G slices U[:, gH:(g+1)H], then the G slices of their transposes, each ceil(H / 32) k-steps x H / 16
+ * feature blocks of bf16 hi / lo MFMA fragments, [(kt * H/16 + m) * 2 + hl] * 64 + lane, 16 bytes each, the K rows from H up
+ * to 32 ceil(H / 32) zero.  At H = 64 that is the image uds_recurrent_backward takes.  Up to 64 units the image is staged in
+ * LDS once per workgroup; above (180 KiB and more) the kernel reads each fragment from it in place, so it must stay valid
+ * until the launch has finished. */
+int64_t uds_recurrent_bwd_packed_bytes(int64_t H, int kind);
+int uds_recurrent_pack_bwd(const float *U, int64_t H, int kind, void *packed, uds_stream_t stream);
+int uds_recurrent_backward_h(const float *xp, const void *packed, const float *b_rec, const float *h, const float *c,
+                             const float *gh, int64_t B, int64_t T, int64_t R, int64_t H, int kind, float *dxp,
+                             float *darec, uds_stream_t stream);
 
 /* A whole keras GRU / LSTM(64, return_sequences=True) layer in ONE launch on the matrix cores (split-bf16, three products,
  * fp32 accumulation): input projection, recurrent product, gates and state update per time step, the state fed back from
