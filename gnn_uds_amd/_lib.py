@@ -200,6 +200,16 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _out(out, shape, like, name):
+    """The caller's output tensor (checked: shape, fp32, contiguous, same device) or a new one."""
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=torch.float32)
+    if tuple(out.shape) != tuple(shape) or out.device != like.device:
+        raise UdsError('%s must be %r on %s, got %r on %s' % (name, tuple(shape), like.device, tuple(out.shape), out.device))
+    _dev(out, name)
+    return out
+
+
 class CsrHandle:
     """uds_csr_t: a CSR pattern resident on the device, plus its degree-sorted row schedule."""
 
@@ -740,8 +750,9 @@ def remainder_forward_dense(packed, shape, e, packed_w, bias, act, h):
     return out
 
 
-def rowgemm_forward(x, packed, bias, f_out, act='linear', taps=1, dilation=1):
-    """Matrix-core Dense (taps=1, any leading dims) or causal Conv1D (x (B,T,R,F), taps = kernel size)."""
+def rowgemm_forward(x, packed, bias, f_out, act='linear', taps=1, dilation=1, out=None):
+    """Matrix-core Dense (taps=1, any leading dims) or causal Conv1D (x (B,T,R,F), taps = kernel size).  out: the result's
+    tensor, allocated when None."""
     lib = load()
     F = x.shape[-1]
     if taps == 1:
@@ -752,7 +763,7 @@ def rowgemm_forward(x, packed, bias, f_out, act='linear', taps=1, dilation=1):
             raise UdsError('conv needs x (B,T,R,F), got %r' % (tuple(x.shape),))
         B, T, R = x.shape[:3]
         out_shape = (B, T, R, f_out)
-    out = torch.empty(out_shape, device=x.device, dtype=torch.float32)
+    out = _out(out, out_shape, x, 'out')
     if out.numel() == 0:
         _dev(x, 'x')
         return out
@@ -761,16 +772,16 @@ def rowgemm_forward(x, packed, bias, f_out, act='linear', taps=1, dilation=1):
     return out
 
 
-def rowgemm_forward_pair(x0, packed0, bias0, x1, packed1, bias1, f_out, act='linear', taps=1, dilation=1):
+def rowgemm_forward_pair(x0, packed0, bias0, x1, packed1, bias1, f_out, act='linear', taps=1, dilation=1, out=None):
     """Two causal Conv1D / Dense problems of one layer shape -- x0 (B,T,R0,F), x1 (B,T,R1,F) -- in one launch when both are small
-    (uds_rowgemm_forward_pair).  Returns (out0, out1)."""
+    (uds_rowgemm_forward_pair).  Returns (out0, out1): the tensors of out = (out0, out1) when given, else new ones."""
     lib = load()
     B, T, R0, F = x0.shape
     R1 = x1.shape[2]
     if tuple(x1.shape) != (B, T, R1, F):
         raise UdsError('rowgemm_forward_pair: x0 %r and x1 %r differ in more than the row count' % (tuple(x0.shape), tuple(x1.shape)))
-    out0 = torch.empty((B, T, R0, f_out), device=x0.device, dtype=torch.float32)
-    out1 = torch.empty((B, T, R1, f_out), device=x0.device, dtype=torch.float32)
+    out0 = _out(None if out is None else out[0], (B, T, R0, f_out), x0, 'out0')
+    out1 = _out(None if out is None else out[1], (B, T, R1, f_out), x0, 'out1')
     if out0.numel() and out1.numel():
         _check(lib.uds_rowgemm_forward_pair(_dev(x0, 'x0'), R0, packed0.data_ptr(), _dev(bias0, 'bias0', True), _dev(out0, 'out0'), _dev(x1, 'x1'), R1,
                                             packed1.data_ptr(), _dev(bias1, 'bias1', True), _dev(out1, 'out1'), B, T, F, taps, dilation, f_out,
@@ -800,16 +811,17 @@ def rowgemm_cat(x, x2, packed, bias, f_out, act='linear', out=None, col0=0):
     return out
 
 
-def dense_cumsum(x, packed, bias=None, res=None, act='linear'):
+def dense_cumsum(x, packed, bias=None, res=None, act='linear', out=None):
     """act(cumsum over axis 1 of (x @ kernel + bias) + res): x (B,T,R,64), kernel (64,64) packed by rowgemm_pack,
-    res (B,1,R,64) -- Dense + prefix sum + residual + activation in one kernel (uds_dense_cumsum)."""
+    res (B,1,R,64) -- Dense + prefix sum + residual + activation in one kernel (uds_dense_cumsum).  out: the result's tensor,
+    allocated when None."""
     lib = load()
     B, T, R, F = x.shape
     if F != 64:
         raise UdsError('dense_cumsum: 64 -> 64 only, got %d inputs' % F)
     if res is not None and tuple(res.shape) != (B, 1, R, 64):
         raise UdsError('dense_cumsum: res must be %r, got %r' % ((B, 1, R, 64), tuple(res.shape)))
-    out = torch.empty((B, T, R, 64), device=x.device, dtype=torch.float32)
+    out = _out(out, (B, T, R, 64), x, 'out')
     if out.numel() == 0:
         _dev(x, 'x')
         return out
@@ -824,11 +836,11 @@ class _Heads(ctypes.Structure):
                 ('n_hidden', ctypes.c_int32), ('act_h', ctypes.c_int32), ('act_f', ctypes.c_int32)]
 
 
-def dense_cumsum_heads(x, packed, bias, res, act, head_a, hidden=(), head_f=None):
+def dense_cumsum_heads(x, packed, bias, res, act, head_a, hidden=(), head_f=None, out=None):
     """uds_dense_cumsum_heads: act(cumsum_t(x @ kernel + bias) + res) consumed by its heads without being written.
     head_a = (packed (64, n_a), bias, n_a, activation); hidden = [(packed, bias), ...] the Dense(32) layers of the second
     head with their common activation in hidden_act = head_f[3]; head_f = (packed (32, 1), bias, activation, hidden activation).
-    Returns (B, T, R, n_a + (1 if hidden else 0))."""
+    Returns (B, T, R, n_a + (1 if hidden else 0)): `out` when given, else a new tensor."""
     lib = load()
     B, T, R, F = x.shape
     if F != 64:
@@ -845,7 +857,7 @@ def dense_cumsum_heads(x, packed, bias, res, act, head_a, hidden=(), head_f=None
     if hidden:
         hd.f_packed, hd.f_bias, hd.act_f, hd.act_h = head_f[0].data_ptr(), _dev(head_f[1], 'f_bias', True), ACT[head_f[2]], ACT[head_f[3]]
         keep += [head_f[0], head_f[1]]
-    out = torch.empty((B, T, R, hd.n_a + (1 if hidden else 0)), device=x.device, dtype=torch.float32)
+    out = _out(out, (B, T, R, hd.n_a + (1 if hidden else 0)), x, 'out')
     if out.numel():
         _check(lib.uds_dense_cumsum_heads(_dev(x, 'x'), B, T, R, packed.data_ptr(), _dev(bias, 'bias', True), _dev(res, 'res', True), ACT[act],
                                           ctypes.byref(hd), _dev(out, 'out'), _stream()), 'uds_dense_cumsum_heads')
@@ -883,9 +895,10 @@ def flow_balance(handle, sign, flow, scale_in, scale_out):
     return q_in, q_out
 
 
-def roll_update(handle, sign, span_e, mini_e, scale_in, scale_out, y, ey, b, x, ex, flood):
-    """The post-forward part of one autoregressive chunk (include/uds_hip.h: uds_roll_update): returns preds (B,so,N,cy+2) and
-    shifts the state windows x (B,T,N,cy+3), ex (B,T,E,ce+1) IN PLACE, feeding the prediction back."""
+def roll_update(handle, sign, span_e, mini_e, scale_in, scale_out, y, ey, b, x, ex, flood, preds=None):
+    """The post-forward part of one autoregressive chunk (include/uds_hip.h: uds_roll_update): returns preds (B,so,N,cy+2)
+    (the tensor `preds` when given, else a new one) and shifts the state windows x (B,T,N,cy+3), ex (B,T,E,ce+1) IN PLACE,
+    feeding the prediction back."""
     lib = load()
     B, so, N, cy = y.shape
     ce, T = ey.shape[-1], x.shape[1]
@@ -894,7 +907,7 @@ def roll_update(handle, sign, span_e, mini_e, scale_in, scale_out, y, ey, b, x, 
         raise UdsError('roll_update: inconsistent shapes y %r ey %r b %r x %r ex %r' % tuple(tuple(t.shape) for t in (y, ey, b, x, ex)))
     if not (x.is_contiguous() and ex.is_contiguous()):
         raise UdsError('roll_update: the state windows are updated in place and must be contiguous')
-    preds = torch.empty((B, so, N, cy + 2), device=y.device, dtype=torch.float32)
+    preds = _out(preds, (B, so, N, cy + 2), y, 'preds')
     _check(lib.uds_roll_update(handle.ptr, _dev(sign, 'sign'), _dev(span_e, 'span_e'), _dev(mini_e, 'mini_e'), _dev(scale_in, 'scale_in'),
                                _dev(scale_out, 'scale_out'), _dev(y.contiguous(), 'y'), cy, _dev(ey.contiguous(), 'ey'), ce, _dev(b.contiguous(), 'b'),
                                B, so, T, int(bool(flood)), _dev(x, 'x'), _dev(ex, 'ex'), _dev(preds, 'preds'), _stream()), 'uds_roll_update')

@@ -424,8 +424,11 @@ __global__ __launch_bounds__(DH_WAVES * 64, 2) void k_dense_cumsum_heads(DenseCu
     int rs = slot + DH_PREF;
     rs = rs >= DH_RING ? rs - DH_RING : rs;
     issue(t + DH_PREF, rs);
-    // x[t] landed once everything older than its 4 pieces is done: younger = 4 pieces per prefetched step (the head outputs are
-    // plain stores of a few bytes per row: they count as vector-memory operations too, one per step, hence the + K below)
+    // x[t] landed once at most the 4 pieces of each of the DH_PREF younger prefetched steps are outstanding: vmcnt(4 * DH_PREF)
+    // in every branch.  The head outputs of earlier steps are plain stores that count as vector-memory operations too, but
+    // every one of them was issued AFTER the pieces of x[t] (x[t] is DH_PREF steps old when it is awaited), i.e. they are
+    // younger than the piece awaited: allowing for none of them makes the wait at worst conservative (it may also wait for
+    // some stores), never too weak.
     const int st = min(t, DH_PREF);
     bool waited = false;
     static_for<DH_PREF>([&](auto k_) {

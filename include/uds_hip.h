@@ -325,9 +325,11 @@ int uds_flow_balance(const uds_csr_t *inc_n, const float *sign, const float *flo
 /* One chunk of the autoregressive rollout after the forward (Emulator._model, emulator.py:403-423, with the edge-fusion
  * branch of post_proc_tf, :717-724): flow = ey[..., ce-1] * span_e + mini_e (de-normalised link flow, per link), q_in /
  * q_out as uds_flow_balance, preds (B,so,N,cy+2) = [y[...,0], q_in, q_out, y[...,1:]]; then both state windows are shifted
- * by `so` steps IN PLACE and fed with the prediction: x (B,T,N,cy+3) gets [preds with the last channel thresholded at 0.5
- * when flood != 0, b], ex (B,T,E,ce+1) gets [ey, 1].  y (B,so,N,cy), ey (B,so,E,ce), b (B,so,N,1).  Bit-identical to the
- * tensor-by-tensor composition. */
+ * by `so` steps IN PLACE and fed with the prediction: x (B,T,N,cy+3) gets [preds with the last y channel, y[...,cy-1] > 0.5 ?
+ * 1 : 0, in place of its value when flood != 0 and cy >= 2 (the flood bit is a y channel of its own after the depth: with
+ * cy = 1 nothing is thresholded), b], ex (B,T,E,ce+1) gets [ey, 1].  y (B,so,N,cy), ey (B,so,E,ce), b (B,so,N,1); the kept
+ * T - so steps of both windows are the old steps so .. T-1 (none when so = T).  Bit-identical to the tensor-by-tensor
+ * composition. */
 int uds_roll_update(const uds_csr_t *inc_n, const float *sign, const float *span_e, const float *mini_e,
                     const float *scale_in, const float *scale_out, const float *y, int64_t cy, const float *ey,
                     int64_t ce, const float *b, int64_t B, int64_t so, int64_t T, int flood, float *x, float *ex,

@@ -349,9 +349,11 @@ def _forward_mlp(c, params, X, B, E, AE, act, D):
     return out, D(e, params['e_out'], 'tanh').reshape(nb, c.seq_out, c.n_edge, c.e_out)
 
 
-def forward(args, params, X, B, E, AE=None, ADJ=None):
+def forward(args, params, X, B, E, AE=None, ADJ=None, tail=None):
     """`Emulator.build_network` as a function: X (B,T_in,N,n_in), B (B,T_out,N,b_in), E (B,T_in,E,e_in),
-    AE (B,T_out,E,1) when act -> out (B,T_out,N,n_out[+1]), e_out (B,T_out,E,e_out).  emulator.py:195-338."""
+    AE (B,T_out,E,1) when act -> out (B,T_out,N,n_out[+1]), e_out (B,T_out,E,e_out).  emulator.py:195-338.
+    tail: a dict that receives the activations the resnet tail starts from (x, e: the outputs of the second temporal block;
+    res, res_e: the residuals), for tests of the tail alone; the result does not depend on it."""
     c = config(args)
     dt = X.dtype
     act = OD.activation(c.activation)
@@ -409,6 +411,8 @@ def forward(args, params, X, B, E, AE=None, ADJ=None):
     x, e = spatial(x, e, params['block2'], ADJ)                       # :264-288 (A = A_in with use_adj)
     x = temporal(x, params['tem2_x'], c.n_node)
     e = temporal(e, params['tem2_e'], c.n_edge)
+    if tail is not None:
+        tail.update(x=x, e=e, res=res, res_e=res_e)
     x_out = _drop(D(x, params['res_x']), dr)                      # :313-314
     x = act(torch.cumsum(x_out, dim=1) + res) if c.resnet else act(x_out)   # :315-316
     e_o = _drop(D(e, params['res_e']), dr)                        # :317-318
