@@ -914,15 +914,15 @@ def roll_update(handle, sign, span_e, mini_e, scale_in, scale_out, y, ey, b, x, 
     return preds
 
 
-def csr_spmm(handle, val, x, bias=None, act='linear'):
-    """out[s,r,:] = act(sum_p val[p] x[s,col[p],:] + bias); x:(S,n_cols,F) -> (S,n_rows,F)."""
+def csr_spmm(handle, val, x, bias=None, act='linear', out=None):
+    """out[s,r,:] = act(sum_p val[p] x[s,col[p],:] + bias); x:(S,n_cols,F) -> (S,n_rows,F).  out: the caller's result tensor."""
     lib = load()
     if x.dim() != 3 or x.shape[1] != handle.n_cols:
         raise UdsError('x must be (S,%d,F), got %r' % (handle.n_cols, tuple(x.shape)))
     if val is not None and val.numel() != handle.nnz:
         raise UdsError('val has %d entries, pattern has %d' % (val.numel(), handle.nnz))
     S, _, F = x.shape
-    out = torch.empty((S, handle.n_rows, F), device=x.device, dtype=torch.float32)
+    out = _out(out, (S, handle.n_rows, F), x, 'out')
     if out.numel() == 0:
         _dev(x, 'x')
         return out
@@ -957,8 +957,8 @@ def gat_forward(handle, xa, kernel, a_self, a_nbr, bias=None, act='relu', xb=Non
     return out
 
 
-def gat_aggregate(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask=None, coef=None):
-    """Attention softmax + neighbour sum of a GATConv from precomputed hx (S,n,d), s_self / s_nbr (S,n).
+def gat_aggregate(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask=None, coef=None, out=None):
+    """Attention softmax + neighbour sum of a GATConv from precomputed hx (S,n,d), s_self / s_nbr (S,n); out: the caller's result tensor.
     edge_mask (S, nnz): per-snapshot 0/1 over the pattern's entries (`use_adj`; the diagonal always takes part).
     coef (S, nnz): multiplier of the normalised coefficients (Spektral's attention dropout in training, uds_gat_aggregate_coef)."""
     lib = load()
@@ -969,7 +969,7 @@ def gat_aggregate(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask=No
         if tuple(coef.shape) != (S, handle.nnz) or n != handle.n_rows or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
             raise UdsError('gat_aggregate: coef %r / hx %r for %d snapshots of a %d-row, %d-entry pattern' %
                            (tuple(coef.shape), tuple(hx.shape), S, handle.n_rows, handle.nnz))
-        out = torch.empty_like(hx)
+        out = _out(out, hx.shape, hx, 'out')
         if out.numel():
             _check(lib.uds_gat_aggregate_coef(handle.ptr, _dev(hx, 'hx'), _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(bias, 'bias', True),
                                               _dev(coef, 'coef'), S, d, ACT[act], _dev(out, 'out'), _stream()), 'uds_gat_aggregate_coef')
@@ -979,7 +979,7 @@ def gat_aggregate(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask=No
             raise UdsError('gat_aggregate: edge_mask %r for %d snapshots of a %d-entry pattern' % (tuple(edge_mask.shape), S, handle.nnz))
         if n != handle.n_rows or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
             raise UdsError('gat_aggregate: hx %r does not match a %d-row pattern' % (tuple(hx.shape), handle.n_rows))
-        out = torch.empty_like(hx)
+        out = _out(out, hx.shape, hx, 'out')
         if out.numel():
             _check(lib.uds_gat_aggregate_masked(handle.ptr, _dev(hx, 'hx'), _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(bias, 'bias', True),
                                                 _dev(edge_mask, 'edge_mask'), S, d, ACT[act], _dev(out, 'out'), _stream()),
@@ -988,7 +988,7 @@ def gat_aggregate(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask=No
     if n != handle.n_rows or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
         raise UdsError('gat_aggregate: hx %r, s_self %r, s_nbr %r do not match a %d-row pattern' %
                        (tuple(hx.shape), tuple(s_self.shape), tuple(s_nbr.shape), handle.n_rows))
-    out = torch.empty_like(hx)
+    out = _out(out, hx.shape, hx, 'out')
     if out.numel() == 0:
         _dev(hx, 'hx')
         return out
@@ -997,18 +997,24 @@ def gat_aggregate(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask=No
     return out
 
 
-def gat_backward(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, coef=None):
+def _gat_backward_outputs(grad, out):
+    """(d_hx, ds_self, ds_nbr): the caller's tensors (checked) or new ones."""
+    S, n, _ = grad.shape
+    o = out if out is not None else (None, None, None)
+    return _out(o[0], grad.shape, grad, 'd_hx'), _out(o[1], (S, n), grad, 'ds_self'), _out(o[2], (S, n), grad, 'ds_nbr')
+
+
+def gat_backward(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, coef=None, out=None, workspace=None):
     """Reverse mode of the attention / aggregation part of gat_forward (uds_gat_backward): grad = dL/d(pre-activation)
-    (S,n,d) -> d_hx (S,n,d), ds_self (S,n), ds_nbr (S,n).  coef: the attention-dropout multiplier of the forward pass, if any."""
+    (S,n,d) -> d_hx (S,n,d), ds_self (S,n), ds_nbr (S,n).  coef: the attention-dropout multiplier of the forward pass, if any.
+    out: the caller's (d_hx, ds_self, ds_nbr); workspace: the caller's (2, S, max(nnz, 1)) alpha / de scratch."""
     lib = load()
     S, n, d = grad.shape
-    d_hx = torch.empty_like(grad)
-    ds_self = torch.empty((S, n), device=grad.device, dtype=torch.float32)
-    ds_nbr = torch.empty_like(ds_self)
+    d_hx, ds_self, ds_nbr = _gat_backward_outputs(grad, out)
     if grad.numel() == 0:
         _dev(grad, 'grad')
         return d_hx, ds_self, ds_nbr
-    ws = torch.empty((2, S, max(handle.nnz, 1)), device=grad.device, dtype=torch.float32)
+    ws = _out(workspace, (2, S, max(handle.nnz, 1)), grad, 'workspace')      # alpha and de per pattern entry
     _check(lib.uds_gat_backward_coef(handle.ptr, handle_t.ptr, _dev_i32(perm_t, 'perm_t'), _dev(grad, 'grad'), _dev(hx, 'hx'),
                                      _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(a_self, 'a_self'), _dev(a_nbr, 'a_nbr'),
                                      _dev(coef, 'coef', True), S, d, _dev(ws[0], 'alpha_ws'), _dev(ws[1], 'de_ws'), _dev(d_hx, 'd_hx'),
@@ -1021,7 +1027,7 @@ def _check_entry_operand(name, t, S, handle):
         raise UdsError('%s %r for %d snapshots of a %d-entry pattern' % (name, tuple(t.shape), S, handle.nnz))
 
 
-def gat_aggregate_ex(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask=None, coef=None):
+def gat_aggregate_ex(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask=None, coef=None, out=None):
     """gat_aggregate with an optional per-snapshot edge_mask (S, nnz) AND an optional attention-dropout coef (S, nnz) on the
     grouped kernels (uds_gat_aggregate_ex): the training path of `use_adj` GAT layers.  A masked entry leaves the softmax; the
     diagonal always takes part.  With edge_mask = all ones and coef None the result is bitwise that of gat_aggregate."""
@@ -1032,7 +1038,7 @@ def gat_aggregate_ex(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask
                        (tuple(hx.shape), tuple(s_self.shape), tuple(s_nbr.shape), handle.n_rows))
     _check_entry_operand('gat_aggregate_ex: edge_mask', edge_mask, S, handle)
     _check_entry_operand('gat_aggregate_ex: coef', coef, S, handle)
-    out = torch.empty_like(hx)
+    out = _out(out, hx.shape, hx, 'out')
     if out.numel() == 0:
         _dev(hx, 'hx')
         return out
@@ -1042,8 +1048,9 @@ def gat_aggregate_ex(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask
     return out
 
 
-def gat_backward_ex(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, edge_mask=None, coef=None):
-    """Reverse mode of gat_aggregate_ex (uds_gat_backward_ex): outputs as gat_backward.  A masked entry contributes nothing."""
+def gat_backward_ex(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, edge_mask=None, coef=None, out=None, workspace=None):
+    """Reverse mode of gat_aggregate_ex (uds_gat_backward_ex): outputs, out and workspace as gat_backward.  A masked entry
+    contributes nothing."""
     lib = load()
     S, n, d = grad.shape
     if n != handle.n_rows or tuple(hx.shape) != (S, n, d) or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
@@ -1051,13 +1058,11 @@ def gat_backward_ex(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a
                        (tuple(grad.shape), tuple(hx.shape), tuple(s_self.shape), tuple(s_nbr.shape), handle.n_rows))
     _check_entry_operand('gat_backward_ex: edge_mask', edge_mask, S, handle)
     _check_entry_operand('gat_backward_ex: coef', coef, S, handle)
-    d_hx = torch.empty_like(grad)
-    ds_self = torch.empty((S, n), device=grad.device, dtype=torch.float32)
-    ds_nbr = torch.empty_like(ds_self)
+    d_hx, ds_self, ds_nbr = _gat_backward_outputs(grad, out)
     if grad.numel() == 0:
         _dev(grad, 'grad')
         return d_hx, ds_self, ds_nbr
-    ws = torch.empty((2, S, max(handle.nnz, 1)), device=grad.device, dtype=torch.float32)
+    ws = _out(workspace, (2, S, max(handle.nnz, 1)), grad, 'workspace')      # alpha and de per pattern entry
     _check(lib.uds_gat_backward_ex(handle.ptr, handle_t.ptr, _dev_i32(perm_t, 'perm_t'), _dev(grad, 'grad'), _dev(hx, 'hx'),
                                    _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(a_self, 'a_self'), _dev(a_nbr, 'a_nbr'),
                                    _dev(edge_mask, 'edge_mask', True), _dev(coef, 'coef', True), S, d, _dev(ws[0], 'alpha_ws'),
@@ -1089,17 +1094,21 @@ def wgrad(a, g, shift=0, with_bias=True):
     return dk, db
 
 
-def csr_sddmm(handle, a, b):
-    """out[k] = sum_s <a[s,row(k),:], b[s,col(k),:]> per pattern entry; a:(S,n_rows,F), b:(S,n_cols,F) -> (nnz,)."""
+def csr_sddmm(handle, a, b, out=None):
+    """out[k] = sum_s <a[s,row(k),:], b[s,col(k),:]> per pattern entry; a:(S,n_rows,F), b:(S,n_cols,F) -> (nnz,).
+    out: the caller's result tensor (zeroed here where the kernel does not run)."""
     lib = load()
     if a.dim() != 3 or b.dim() != 3 or a.shape[1] != handle.n_rows or b.shape[1] != handle.n_cols or a.shape[0] != b.shape[0] \
             or a.shape[2] != b.shape[2]:
         raise UdsError('sddmm: a must be (S,%d,F) and b (S,%d,F), got %r, %r' % (handle.n_rows, handle.n_cols, tuple(a.shape),
                                                                                tuple(b.shape)))
-    out = torch.zeros(handle.nnz, device=a.device, dtype=torch.float32)
+    if out is None:
+        out = torch.zeros(handle.nnz, device=a.device, dtype=torch.float32)
+    else:
+        out = _out(out, (handle.nnz,), a, 'out')
     if handle.nnz == 0 or a.numel() == 0:
         _dev(a, 'a')
-        return out
+        return out.zero_() if out.numel() else out
     _check(lib.uds_csr_sddmm(handle.ptr, _dev(a, 'a'), _dev(b, 'b'), a.shape[0], a.shape[2], _dev(out, 'out'), _stream()),
            'uds_csr_sddmm')
     return out

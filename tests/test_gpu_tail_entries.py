@@ -31,47 +31,18 @@ from gnn_uds_amd import _lib
 from oracle import emulator_ref as OE
 from oracle import spektral_dense as OD
 from oracle.tail_ref import roll_update_ref
-from tests.util import HEADS_CASES, close, heads_case_id, heads_inputs, heads_ref, heads_tol
+from tests.util import HEADS_CASES, SENTINEL, Guarded, close, heads_case_id, heads_inputs, heads_ref, heads_tol, nan_in
 
 pytestmark = pytest.mark.gpu
 
 TOL_ROWGEMM = 1e-4
 TOL_FLOW = 1e-6
-SENTINEL = 0x4B5A5A5A      # int32 bits of the guard floats (1.43e7 as a float: nothing a kernel here computes)
-PAD = 1024                 # guard floats on each side of a view (a multiple of 4: the view stays 16-byte aligned)
 
 
 @pytest.fixture(scope='module')
 def dev():
     assert torch.cuda.is_available()
     return torch.device('cuda', 0)
-
-
-class Guarded:
-    """A contiguous fp32 view of `shape` in the middle of a sentinel-filled allocation."""
-
-    def __init__(self, shape, dev, init=None):
-        self.n = int(np.prod(shape))
-        self.buf = torch.full((self.n + 2 * PAD,), SENTINEL, dtype=torch.int32, device=dev).view(torch.float32)
-        self.view = self.buf[PAD:PAD + self.n].view(shape)
-        if init is not None:
-            self.view.copy_(init)
-
-    def check(self, what):
-        bits = self.buf.view(torch.int32)
-        assert bool((bits[:PAD] == SENTINEL).all()), '%s: written before its first element' % what
-        assert bool((bits[PAD + self.n:] == SENTINEL).all()), '%s: written past its last element' % what
-        assert bool(torch.isfinite(self.view).all()), '%s: non-finite output (an input was read outside its tensor?)' % what
-
-
-def nan_in(t, dev):
-    """`t` as a contiguous fp32 device view inside a NaN-filled allocation (None stays None)."""
-    if t is None:
-        return None
-    buf = torch.full((t.numel() + 2 * PAD,), float('nan'), dtype=torch.float32, device=dev)
-    v = buf[PAD:PAD + t.numel()].view(t.shape)
-    v.copy_(t)
-    return v
 
 
 def pack(kernel2d, dev):

@@ -1,86 +1,12 @@
 """The masked GAT forward and backward that uds_gat_aggregate_ex / uds_gat_backward_ex compute, restated in fp64 on the CSR
-pattern and pinned against torch autograd of the dense restatement (oracle.spektral_dense.gat_conv_dense) fed the
-per-snapshot (S, N, N) adjacency of `use_adj`.  Per snapshot s and row i, with l_p = ss_i + sn_j (j = col p):
-
-    survivors  P_i = {p in row i : mask[s, p] != 0 or j == i}          (spektral's set_diag after the rewrite)
-    m_i        = max_{p in P_i} leaky(l_p)                             (over the survivors only)
-    alpha_p    = exp(leaky(l_p) - m_i) / sum_{P_i} exp(..)  on P_i,  0 off it
-    pre_i      = sum_p alpha_p coef_p hx_j,   out = act(pre + bias),   g = act'(out) gout
-    q_p        = coef_p <g_i, hx_j>,   cbar_i = sum_p alpha_p q_p,   de_p = alpha_p (q_p - cbar_i) leaky'(l_p)  (0 off P_i)
-    ds_self_i  = sum_{p in row i} de_p
-    d_hx_j     = sum_{p : col p = j} alpha_p coef_p g_{row p} + a_nbr ds_nbr_j + a_self ds_self_j,   ds_nbr_j = sum_{col p = j} de_p
-
-(coef: the attention-dropout multiplier, folded in as GatBwdRowsArgs documents; 1 without dropout.)"""
+pattern (oracle/gat_csr_ref.py, whose header holds the formulas) and pinned against torch autograd of the dense restatement
+(oracle.spektral_dense.gat_conv_dense) fed the per-snapshot (S, N, N) adjacency of `use_adj`."""
 import numpy as np
 import pytest
 import torch
 
 from oracle import spektral_dense as OD
-
-
-def leaky(v):
-    return np.where(v > 0, v, 0.2 * v)
-
-
-def act_fn(z, act):
-    return {'relu': lambda t: np.maximum(t, 0.0), 'tanh': np.tanh}[act](z)
-
-
-def act_grad(y, gy, act):
-    return {'relu': gy * (y > 0), 'tanh': gy * (1.0 - y * y)}[act]
-
-
-def survivors(rowptr, col, mask):
-    """(S, nnz) bool: entry p of snapshot s takes part."""
-    rows = np.repeat(np.arange(len(rowptr) - 1), np.diff(rowptr))
-    return (mask != 0) | (col == rows)[None, :]
-
-
-def masked_forward(rowptr, col, mask, coef, hx, ss, sn, bias, act):
-    """out (S, n, d) and alpha (S, nnz) in fp64, row by row as the kernels walk them."""
-    S, n, d = hx.shape
-    on = survivors(rowptr, col, mask)
-    alpha = np.zeros(mask.shape)
-    out = np.empty((S, n, d))
-    for s in range(S):
-        for i in range(n):
-            ps = np.arange(rowptr[i], rowptr[i + 1])
-            ps = ps[on[s, ps]]
-            pre = np.zeros(d)
-            if len(ps):
-                lg = leaky(ss[s, i] + sn[s, col[ps]])
-                w = np.exp(lg - lg.max())
-                alpha[s, ps] = w / w.sum()
-                pre = (alpha[s, ps] * coef[s, ps]) @ hx[s, col[ps]]
-            out[s, i] = act_fn(pre + bias, act)
-    return out, alpha
-
-
-def masked_backward(rowptr, col, mask, coef, hx, ss, sn, a_self, a_nbr, alpha, out, gout, act):
-    """(d_hx (S, n, d), ds_self (S, n), ds_nbr (S, n)) in fp64: the row pass, then the transposed walk."""
-    S, n, d = hx.shape
-    on = survivors(rowptr, col, mask)
-    g = act_grad(out, gout, act)
-    de = np.zeros(mask.shape)
-    ds_self = np.zeros((S, n))
-    for s in range(S):
-        for i in range(n):
-            ps = np.arange(rowptr[i], rowptr[i + 1])
-            q = coef[s, ps] * (hx[s, col[ps]] @ g[s, i])
-            cbar = (alpha[s, ps] * q).sum()
-            slope = np.where(ss[s, i] + sn[s, col[ps]] > 0, 1.0, 0.2)
-            de[s, ps] = np.where(on[s, ps], alpha[s, ps] * (q - cbar) * slope, 0.0)
-            ds_self[s, i] = de[s, ps].sum()
-    rows = np.repeat(np.arange(n), np.diff(rowptr))
-    order = np.lexsort((rows, col))                  # the transposed pattern, column by column
-    d_hx = np.zeros((S, n, d))
-    ds_nbr = np.zeros((S, n))
-    for s in range(S):
-        for p in order:
-            d_hx[s, col[p]] += alpha[s, p] * coef[s, p] * g[s, rows[p]]
-            ds_nbr[s, col[p]] += de[s, p]
-        d_hx[s] += np.outer(ds_nbr[s], a_nbr) + np.outer(ds_self[s], a_self)
-    return d_hx, ds_self, ds_nbr, g
+from oracle.gat_csr_ref import act_fn, act_grad, leaky, masked_backward, masked_forward, survivors  # noqa: F401
 
 
 def hub_pattern(n=24, seed=0):

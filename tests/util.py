@@ -283,3 +283,174 @@ def heads_tol(c):
     """Tolerance of a heads case for close() (relative to max(1, max|ref|)); the header of tests/test_gpu_tail_entries.py lists
     the measurements it is set from."""
     return HEADS_TOL
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# guarded device memory (tests/test_gpu_tail_entries.py, tests/test_gpu_sparse_widths.py): plain allocations, nothing here
+# is meant to fault
+# ---------------------------------------------------------------------------------------------------------------
+SENTINEL = 0x4B5A5A5A      # int32 bits of the guard floats (1.43e7 as a float: nothing a kernel here computes)
+PAD = 1024                 # guard floats on each side of a view (a multiple of 4: the view stays 16-byte aligned)
+
+
+class Guarded:
+    """A contiguous fp32 view of `shape` in the middle of a sentinel-filled allocation."""
+
+    def __init__(self, shape, dev, init=None):
+        self.n = int(np.prod(shape))
+        self.buf = torch.full((self.n + 2 * PAD,), SENTINEL, dtype=torch.int32, device=dev).view(torch.float32)
+        self.view = self.buf[PAD:PAD + self.n].view(shape)
+        if init is not None:
+            self.view.copy_(init)
+
+    def check(self, what):
+        bits = self.buf.view(torch.int32)
+        assert bool((bits[:PAD] == SENTINEL).all()), '%s: written before its first element' % what
+        assert bool((bits[PAD + self.n:] == SENTINEL).all()), '%s: written past its last element' % what
+        assert bool(torch.isfinite(self.view).all()), '%s: non-finite output (an input was read outside its tensor?)' % what
+
+
+def nan_in(t, dev):
+    """`t` as a contiguous fp32 device view inside a NaN-filled allocation (None stays None)."""
+    if t is None:
+        return None
+    buf = torch.full((t.numel() + 2 * PAD,), float('nan'), dtype=torch.float32, device=dev)
+    v = buf[PAD:PAD + t.numel()].view(t.shape)
+    v.copy_(t)
+    return v
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the degree ladder: patterns and operands shared by tests/test_sparse_ref_math.py (CPU: the cases are what they claim to
+# be and the references carry signal) and tests/test_gpu_sparse_widths.py (GPU parity at every lane-group shape)
+# ---------------------------------------------------------------------------------------------------------------
+LADDER_DEGREES = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33)      # G - 1, G, G + 1, 2 G, 2 G + 1 for G = 2, 4, 8, 16
+HUB_DEGREE = 49                                                        # more than three chunks of 16
+LADDER_NO_DIAG = 40                                                    # the row without its diagonal
+SPARSE_WIDTHS = [4, 8, 12, 16, 32, 64, 96, 128, 256]
+
+
+def sparse_lanes(d):
+    """(G, NC) of kernels_sparse.hpp's group_shape for a row of d floats, (0, 1) for the widths that walk."""
+    return {2: (2, 1), 4: (4, 1), 8: (8, 1), 16: (16, 1), 32: (16, 2)}.get(d // 4, (0, 1))
+
+
+def ladder(n, seed=0):
+    """Square directed pattern of n >= 67 nodes, columns ascending, every row but one holding its diagonal:
+      row r = 1 .. 14       LADDER_DEGREES[r - 1] entries (its diagonal plus random columns)
+      row n - 1             the hub row: HUB_DEGREE = 49 entries; no other row holds column n - 1 (its targets do not point back)
+      column c = 15 .. 28   LADDER_DEGREES[c - 15] entries (its diagonal plus random rows): the ladder of the transposed pattern
+      column 0              the hub column: rows 30 .. 65 all point at node 0 (37 entries or more)
+      row LADDER_NO_DIAG    lacks its diagonal (it keeps (40, 0) and whatever the ladder columns drew)
+      every other row       its diagonal plus what the ladder columns and the hub column put there.
+    Ladder rows and the hub row draw their columns outside 15 .. 28 and n - 1, ladder columns draw their rows outside 1 .. 14 and
+    n - 1, so both ladders hold exactly."""
+    assert n >= 67
+    rng = np.random.default_rng(100 * seed + n)
+    hub, lrows, lcols = n - 1, range(1, 15), range(15, 29)
+    free_cols = [c for c in range(n) if c not in lcols and c != hub]
+    free_rows = [r for r in range(n) if r not in lrows and r != hub]
+    pairs = {(r, r) for r in range(n)}
+    for r, deg in zip(lrows, LADDER_DEGREES):
+        pairs |= {(r, int(c)) for c in rng.choice([c for c in free_cols if c != r], deg - 1, replace=False)}
+    pairs |= {(hub, int(c)) for c in rng.choice(free_cols, HUB_DEGREE - 1, replace=False)}
+    for c, deg in zip(lcols, LADDER_DEGREES):
+        pairs |= {(int(r), c) for r in rng.choice([r for r in free_rows if r != c], deg - 1, replace=False)}
+    pairs |= {(r, 0) for r in range(30, 66)}
+    pairs.discard((LADDER_NO_DIAG, LADDER_NO_DIAG))
+    return _pairs_csr(pairs, n, n)
+
+
+def thick(n=67):
+    """Square directed pattern whose every row is multi-chunk at every G: row i holds columns i, i + 1, .. (mod n), 33 + i % 17 of
+    them.  The degree-sorted schedule runs by DESCENDING degree, so the row that comes last in order[] -- the one surplus groups
+    of the ordered kernels shadow -- is the lowest-degree row; here that is row 51 with 33 entries (three chunks of 16)."""
+    pairs = {(i, (i + k) % n) for i in range(n) for k in range(33 + i % 17)}
+    return _pairs_csr(pairs, n, n)
+
+
+def ladder_rect(seed=0):
+    """67 x 41 pattern with values (SpMM / SDDMM): rows 0, 33 and 66 are empty -- 66 comes last in order[] --, row r = 1 .. 14 holds
+    LADDER_DEGREES[r - 1] entries, row 65 all 41 columns (chunks of 16, 16, 9), the others 1 .. 6; values uniform in +-0.5."""
+    rng = np.random.default_rng(7 + seed)
+    n_rows, n_cols = 67, 41
+    pairs = set()
+    for r in range(n_rows):
+        if r in (0, 33, 66):
+            continue
+        deg = LADDER_DEGREES[r - 1] if 1 <= r <= 14 else n_cols if r == 65 else int(rng.integers(1, 7))
+        pairs |= {(r, int(c)) for c in rng.choice(n_cols, deg, replace=False)}
+    csr = _pairs_csr(pairs, n_rows, n_cols)
+    csr.val = f32_exact(rng.uniform(-0.5, 0.5, csr.nnz))
+    return csr
+
+
+def _pairs_csr(pairs, n_rows, n_cols):
+    from gnn_uds_amd.graph import CSR
+    rc = np.array(sorted(pairs), dtype=np.int64)
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(rc[:, 0], minlength=n_rows))])
+    return CSR(rowptr.astype(np.int32), rc[:, 1].astype(np.int32), n_rows, n_cols)
+
+
+def f32_exact(a):
+    """fp64 array whose every value is an fp32 number: the device sees the same values."""
+    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+def ladder_scores(csr, seed=0):
+    """(s_self, s_nbr), each (3, n) fp64 of fp32 values.  Snapshots 0 and 1: s_nbr uniform in +-2 and s_self of a multi-entry row
+    placed so that -s_self lies strictly between the smallest and the largest s_nbr of the row: both leaky slopes occur in it.
+    Snapshot 2, the overflow snapshot: multiples of 0.25 in [-48, 48] (fp32 forms s_self + s_nbr exactly) with the last row's
+    largest logit set to 48 + 44 = 92: exp(92) is not an fp32 number, only the row-maximum shift keeps expf finite."""
+    rng = np.random.default_rng(1000 + seed + csr.n_rows)
+    n, rp, col = csr.n_rows, csr.rowptr, csr.col
+    ss, sn = np.empty((3, n)), np.empty((3, n))
+    for s in range(2):
+        sn[s] = f32_exact(rng.uniform(-2.0, 2.0, n))
+        for i in range(n):
+            v = sn[s, col[rp[i]:rp[i + 1]]]
+            ss[s, i] = f32_exact(-(v.min() + rng.uniform(0.25, 0.75) * (v.max() - v.min())) if len(v) > 1 else rng.uniform(-2.0, 2.0))
+    ss[2], sn[2] = rng.integers(-192, 193, n) * 0.25, rng.integers(-192, 193, n) * 0.25
+    ss[2, n - 1], sn[2, col[rp[n - 1] + 5]] = 48.0, 44.0
+    return ss, sn
+
+
+def ladder_mask(csr, seed=0):
+    """(3, nnz) 0/1 fp64: every entry -- the diagonal ones too, the kernels must keep those -- is off with probability 1/3; in
+    snapshot 0 the last row (the 49-entry hub of a ladder), row 11 (17 entries there) and every row without a diagonal lose all
+    their off-diagonal entries; in snapshot 1 the last row has its odd entries off and its even entries on, so every chunk of two
+    or more entries is partly masked at every G."""
+    rng = np.random.default_rng(2000 + seed + csr.n_rows)
+    rows, col, rp, n = csr.rows(), csr.col.astype(np.int64), csr.rowptr, csr.n_rows
+    mask = (rng.random((3, csr.nnz)) > 1.0 / 3.0).astype(np.float64)
+    no_diag = [i for i in range(n) if i not in col[rp[i]:rp[i + 1]]]
+    for r in [n - 1, 11] + no_diag:
+        mask[0, (rows == r) & (col != r)] = 0.0
+    k = np.arange(rp[n - 1], rp[n])
+    mask[1, k] = ((k - rp[n - 1]) % 2 == 0).astype(np.float64)
+    return mask
+
+
+def ladder_coef(nnz, seed=11):
+    """(3, nnz) fp64 attention-dropout multiplier, 0 or 2: the CPU restatement of _lib.dropout(ones, 0.5, seed, 0)."""
+    from oracle.dropout_ref import dropout
+    return dropout(np.ones((3, nnz)), 0.5, seed, 0)
+
+
+def ladder_operands(n, d, seed=0):
+    """hx, grad (3, n, d) and bias, a_self, a_nbr (d,): uniform in +-0.5, fp64 arrays of fp32 values."""
+    rng = np.random.default_rng(3000 + seed + 1000 * n + d)
+    u = lambda *shape: f32_exact(rng.uniform(-0.5, 0.5, shape))
+    return dict(hx=u(3, n, d), grad=u(3, n, d), bias=u(d), a_self=u(d), a_nbr=u(d))
+
+
+def gat_ref(csr, ss, sn, mask, coef, op):
+    """fp64 reference of one (pattern, width, mask, coef) case from oracle.gat_csr_ref: pre (the aggregation before bias and
+    activation), d_hx, ds_self, ds_nbr (the reverse mode of `pre` for the upstream gradient op['grad']).  mask / coef None = ones."""
+    from oracle.gat_csr_ref import masked_backward, masked_forward
+    rp, col = csr.rowptr.astype(np.int64), csr.col.astype(np.int64)
+    ones = np.ones((ss.shape[0], csr.nnz))
+    mk, cf = ones if mask is None else mask, ones if coef is None else coef
+    pre, alpha = masked_forward(rp, col, mk, cf, op['hx'], ss, sn, np.zeros(op['hx'].shape[-1]), 'linear')
+    d_hx, ds_self, ds_nbr, _ = masked_backward(rp, col, mk, cf, op['hx'], ss, sn, op['a_self'], op['a_nbr'], alpha, pre, op['grad'], 'linear')
+    return dict(pre=pre, alpha=alpha, d_hx=d_hx, ds_self=ds_self, ds_nbr=ds_nbr)
