@@ -92,6 +92,10 @@ SYMBOLS = {
     'uds_gat_aggregate_ex': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
     'uds_gat_backward_ex': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
                                      _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_gat_aggregate_heads': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_ptr,
+                                         _c_ptr, _c_ptr]),
+    'uds_gat_backward_heads': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
+                                        _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     'uds_csr_sddmm': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr]),
     'uds_wgrad_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_int]),
     'uds_wgrad': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
@@ -1068,6 +1072,69 @@ def gat_backward_ex(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a
                                    _dev(edge_mask, 'edge_mask', True), _dev(coef, 'coef', True), S, d, _dev(ws[0], 'alpha_ws'),
                                    _dev(ws[1], 'de_ws'), _dev(d_hx, 'd_hx'), _dev(ds_self, 'ds_self'), _dev(ds_nbr, 'ds_nbr'),
                                    _stream()), 'uds_gat_backward_ex')
+    return d_hx, ds_self, ds_nbr
+
+
+def _check_heads_operands(name, handle, hx, s_self, s_nbr, edge_mask, coef):
+    """(S, n, H, C) of a multi-head call: hx (S,n,H*C), scores (S,n,H), edge_mask (S,nnz), coef (S,H,nnz)."""
+    if hx.dim() != 3 or s_self.dim() != 3 or tuple(s_nbr.shape) != tuple(s_self.shape):
+        raise UdsError('%s: hx %r must be (S,n,H*C) and s_self %r, s_nbr %r (S,n,H)' %
+                       (name, tuple(hx.shape), tuple(s_self.shape), tuple(s_nbr.shape)))
+    S, n, width = hx.shape
+    H = s_self.shape[-1]
+    if n != handle.n_rows or tuple(s_self.shape) != (S, n, H) or H < 1 or width % H:
+        raise UdsError('%s: hx %r, s_self %r, s_nbr %r do not match a %d-row pattern' %
+                       (name, tuple(hx.shape), tuple(s_self.shape), tuple(s_nbr.shape), handle.n_rows))
+    _check_entry_operand('%s: edge_mask' % name, edge_mask, S, handle)
+    if coef is not None and tuple(coef.shape) != (S, H, handle.nnz):
+        raise UdsError('%s: coef %r for %d snapshots and %d heads of a %d-entry pattern' % (name, tuple(coef.shape), S, H, handle.nnz))
+    return S, n, H, width // H
+
+
+def gat_aggregate_heads(handle, hx, s_self, s_nbr, bias=None, act='relu', concat=True, edge_mask=None, coef=None, out=None,
+                        alpha_out=None):
+    """Multi-head attention softmax + neighbour sum (uds_gat_aggregate_heads): hx (S,n,H*C) head-major, s_self / s_nbr (S,n,H),
+    edge_mask (S,nnz) shared by the heads, coef (S,H,nnz) per head.  concat: out (S,n,H*C) with bias (H*C,); otherwise the mean
+    over the heads, out (S,n,C) with bias (C,).  alpha_out: True or the caller's (S,H,nnz) tensor -- the coefficients the
+    aggregation used (alpha * coef, 0 for a masked entry); the call then returns (out, alpha_out)."""
+    lib = load()
+    S, n, H, C = _check_heads_operands('gat_aggregate_heads', handle, hx, s_self, s_nbr, edge_mask, coef)
+    width = H * C if concat else C
+    if bias is not None and tuple(bias.shape) != (width,):
+        raise UdsError('gat_aggregate_heads: bias %r, expected (%d,)' % (tuple(bias.shape), width))
+    out = _out(out, (S, n, width), hx, 'out')
+    alpha = None if alpha_out is None or alpha_out is False else _out(None if alpha_out is True else alpha_out, (S, H, handle.nnz), hx, 'alpha_out')
+    if out.numel() == 0:
+        _dev(hx, 'hx')
+    else:
+        _check(lib.uds_gat_aggregate_heads(handle.ptr, _dev(hx, 'hx'), _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(bias, 'bias', True),
+                                           _dev(edge_mask, 'edge_mask', True), _dev(coef, 'coef', True), S, H, C, int(bool(concat)), ACT[act],
+                                           _dev(out, 'out'), _dev(alpha, 'alpha_out', True), _stream()), 'uds_gat_aggregate_heads')
+    return out if alpha is None else (out, alpha)
+
+
+def gat_backward_heads(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, concat=True, edge_mask=None, coef=None, out=None,
+                       workspace=None):
+    """Reverse mode of gat_aggregate_heads (uds_gat_backward_heads): grad = dL/d(pre-activation), (S,n,H*C) or, for the mean,
+    (S,n,C) -> d_hx (S,n,H*C), ds_self (S,n,H), ds_nbr (S,n,H).  a_self / a_nbr (H*C,) head-major.  out: the caller's
+    (d_hx, ds_self, ds_nbr); workspace: the caller's (2, S, H, max(nnz, 1)) alpha / de scratch."""
+    lib = load()
+    S, n, H, C = _check_heads_operands('gat_backward_heads', handle, hx, s_self, s_nbr, edge_mask, coef)
+    if tuple(grad.shape) != (S, n, H * C if concat else C):
+        raise UdsError('gat_backward_heads: grad %r for hx %r, %d heads, concat=%r' % (tuple(grad.shape), tuple(hx.shape), H, bool(concat)))
+    if a_self.numel() != H * C or a_nbr.numel() != H * C:
+        raise UdsError('gat_backward_heads: a_self %r / a_nbr %r, expected %d values' % (tuple(a_self.shape), tuple(a_nbr.shape), H * C))
+    o = out if out is not None else (None, None, None)
+    d_hx, ds_self, ds_nbr = _out(o[0], hx.shape, grad, 'd_hx'), _out(o[1], (S, n, H), grad, 'ds_self'), _out(o[2], (S, n, H), grad, 'ds_nbr')
+    if grad.numel() == 0:
+        _dev(grad, 'grad')
+        return d_hx, ds_self, ds_nbr
+    ws = _out(workspace, (2, S, H, max(handle.nnz, 1)), grad, 'workspace')      # alpha and de per head and pattern entry
+    _check(lib.uds_gat_backward_heads(handle.ptr, handle_t.ptr, _dev_i32(perm_t, 'perm_t'), _dev(grad, 'grad'), _dev(hx, 'hx'),
+                                      _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(a_self, 'a_self'), _dev(a_nbr, 'a_nbr'),
+                                      _dev(edge_mask, 'edge_mask', True), _dev(coef, 'coef', True), S, H, C, int(bool(concat)),
+                                      _dev(ws[0], 'alpha_ws'), _dev(ws[1], 'de_ws'), _dev(d_hx, 'd_hx'), _dev(ds_self, 'ds_self'),
+                                      _dev(ds_nbr, 'ds_nbr'), _stream()), 'uds_gat_backward_heads')
     return d_hx, ds_self, ds_nbr
 
 

@@ -7,6 +7,8 @@ the fused kernel are the batch elements.
     ConvNet(args, conv)(X, E[, B]) -> (batch, conv_dim)
 
 Weight names follow the Keras layers (`embed_x`, `embed_e`, `block.layers.i.*`, `pool.attn_kernel` (F, 1)).
+`args.attn_heads` (default 1; NOT a reference key -- the reference's GATConv layers have one head) builds the GAT layers with H
+heads of conv_dim / H channels each, concatenated.
 """
 import numpy as np
 import torch
@@ -48,6 +50,7 @@ class ConvNet(nn.Module):
         self.graph_base = int(g('graph_base', 0))
         self.n_edge, self.e_in = g('edge_state_shape', (40, 3))
         self.activation = g('activation', None) or 'linear'
+        self.attn_heads = int(g('attn_heads', 1) or 1)
         kind = 'GAT' if 'GAT' in conv else ('GCN' if 'GCN' in conv else None)
         if kind is None:
             raise NotImplementedError('conv=%r is not built (GAT and GCN are)' % (conv,))
@@ -61,7 +64,8 @@ class ConvNet(nn.Module):
             if kind == 'GCN':
                 from .layers import GCNConv
                 filt = GCNConv.preprocess(adj)
-            self.block = GraphBaseBlock(self.n_node, self.n_edge, filt, d, self.n_sp_layer, a, generator=gen, conv=kind, precision=precision)
+            self.block = GraphBaseBlock(self.n_node, self.n_edge, filt, d, self.n_sp_layer, a, generator=gen, conv=kind, precision=precision,
+                                        attn_heads=self.attn_heads)
         else:
             if isinstance(graph, DrainageGraph):
                 filters = (None, None)
@@ -73,7 +77,8 @@ class ConvNet(nn.Module):
                     filters = (GCNConv.preprocess(adj), GCNConv.preprocess(edge_adj))
                 else:
                     filters = (None, None)
-            self.block = SpatialBlock(graph, d, self.n_sp_layer, a, generator=gen, precision=precision, conv=kind, filters=filters)
+            self.block = SpatialBlock(graph, d, self.n_sp_layer, a, generator=gen, precision=precision, conv=kind, filters=filters,
+                                      attn_heads=self.attn_heads)
         self.pool = GlobalAttnSumPool(d, generator=gen)
 
     def forward(self, X, E, B=None):

@@ -7,6 +7,7 @@ operator of the forward carries its own backward, so `loss.backward()` on an `Em
     Conv1DFn       causal dilated Conv1D           dX = the same kernels looking AHEAD (dilation < 0) with transposed taps
     SpmmFn         NodeEdge on its support / GCN   dX = spmm on the transposed pattern, dval = uds_csr_sddmm
     GatFn          MixedGAT(GATConv)               uds_gat_backward (softmax / leaky-relu / aggregation), then Dense rules
+    GatHeadsFn     GATConv(attn_heads=H, ..)       uds_gat_aggregate_heads / uds_gat_backward_heads, then the same Dense rules
     DiffusionFn    DiffusionConv on its support    uds_diffusion_backward: d r (transposed pattern) and d kernel, 3 launches
     CumsumActFn    relu(cumsum_T(x) + res)         reverse cumulative sum
     FlowBalanceFn  post_proc_tf incidence sums     gather along the link end nodes
@@ -314,6 +315,81 @@ class GatFn(torch.autograd.Function):
         if ctx.has_bias and ctx.needs_input_grad[5]:
             db = g.reshape(-1, d).sum(0)
         return dxa, dxb, dk, das, dan, db, None, None, None, None, None
+
+
+def heads_score_matrix(a_self, a_nbr):
+    """The block-diagonal (H*C, 2H) matrix that takes hx (.., H*C), head-major, to its 2H attention scores: column h holds
+    attn_kernel_self[:, h, 0] in rows h*C .. (h+1)*C, column H + h attn_kernel_neighs[:, h, 0].  Also returns the two kernels
+    head-major, (H*C,) each, as uds_gat_backward_heads takes them."""
+    C, H = a_self.shape[0], a_self.shape[1]
+    as_hm, an_hm = a_self.reshape(C, H).t().contiguous(), a_nbr.reshape(C, H).t().contiguous()        # (H, C)
+    eye = torch.eye(H, device=a_self.device, dtype=a_self.dtype)
+    m = torch.cat([as_hm.unsqueeze(-1) * eye.unsqueeze(1), an_hm.unsqueeze(-1) * eye.unsqueeze(1)], dim=-1)      # (H, C, 2H)
+    return m.reshape(H * C, 2 * H).contiguous(), as_hm.reshape(-1), an_hm.reshape(-1)
+
+
+def gat_heads_forward(xa, xb, kernel, a_self, a_nbr, bias, act, handle, concat, coef=None, edge_mask=None, want_attn=False):
+    """The multi-head GATConv forward on the HIP kernels: hx = [xa | xb] @ kernel.reshape(F, H*C) and the 2H scores
+    hx @ heads_score_matrix as exact-fp32 row products (uds_dense_act), then uds_gat_aggregate_heads.
+    Returns out, alpha (S, H, nnz) or None, and (hx, s_self, s_nbr) for the backward."""
+    fin, H, C = kernel.shape
+    hx = _lib.dense_act(xa, kernel.reshape(fin, H * C), None, 'linear', xb)
+    s2 = _lib.dense_act(hx, heads_score_matrix(a_self, a_nbr)[0], None, 'linear')
+    s_self, s_nbr = s2[..., :H].contiguous(), s2[..., H:].contiguous()
+    res = _lib.gat_aggregate_heads(handle, hx, s_self, s_nbr, bias, act, concat=concat, edge_mask=edge_mask, coef=coef,
+                                   alpha_out=True if want_attn else None)
+    out, alpha = res if want_attn else (res, None)
+    return out, alpha, (hx, s_self, s_nbr)
+
+
+class GatHeadsFn(torch.autograd.Function):
+    """GATConv with attn_heads = H (kernel (F, H, C), attention kernels (C, H, 1)), concatenated or averaged heads:
+    uds_gat_aggregate_heads / uds_gat_backward_heads, then the Dense rules of GatFn on the (F, H*C) view of the kernel.
+    edge_mask (S, nnz) is shared by the heads, coef (S, H, nnz) is per head.  Returns (out, alpha); alpha (S, H, nnz) carries
+    no gradient (an empty tensor when it was not asked for)."""
+
+    @staticmethod
+    def forward(ctx, xa, xb, kernel, a_self, a_nbr, bias, act, handle, precision, concat, coef=None, edge_mask=None, want_attn=False):
+        xa = xa.contiguous()
+        xb = None if xb is None else xb.contiguous()
+        out, alpha, (hx, s_self, s_nbr) = gat_heads_forward(xa, xb, kernel, a_self, a_nbr, bias, act, handle, concat, coef, edge_mask, want_attn)
+        ctx.save_for_backward(xa, xb, kernel, a_self, a_nbr, out, hx, s_self, s_nbr)
+        ctx.act, ctx.handle, ctx.precision, ctx.has_bias, ctx.coef = act, handle, precision, bias is not None, coef
+        ctx.edge_mask, ctx.concat = edge_mask, concat
+        if alpha is None:
+            alpha = out.new_empty(0)
+        ctx.mark_non_differentiable(alpha)
+        return out, alpha
+
+    @staticmethod
+    def backward(ctx, gout, _galpha):
+        xa, xb, kernel, a_self, a_nbr, out, hx, s_self, s_nbr = ctx.saved_tensors
+        fin, H, C = kernel.shape
+        g = act_grad(out, gout.contiguous(), ctx.act).contiguous()
+        ht, perm = ctx.handle.transposed(g.device)
+        _, as_hm, an_hm = heads_score_matrix(a_self, a_nbr)
+        d_hx, ds_self, ds_nbr = _lib.gat_backward_heads(ctx.handle, ht, perm, g, hx, s_self, s_nbr, as_hm, an_hm, concat=ctx.concat,
+                                                        edge_mask=ctx.edge_mask, coef=ctx.coef)
+        fa = xa.shape[-1]
+        w2 = kernel.reshape(fin, H * C)
+        dxa = dxb = dk = das = dan = db = None
+        if ctx.needs_input_grad[0]:
+            dxa = rows_matmul(d_hx, w2[:fa].t(), ctx.precision)
+        if xb is not None and ctx.needs_input_grad[1]:
+            dxb = rows_matmul(d_hx, w2[fa:].t(), ctx.precision)
+        if ctx.needs_input_grad[2]:
+            dk = weight_grad(xa, d_hx, ctx.precision, False)[0]
+            if xb is not None:
+                dk = torch.cat([dk, weight_grad(xb, d_hx, ctx.precision, False)[0]], dim=0)
+            dk = dk.reshape(kernel.shape)
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            # d a_self[:, h] = sum_r ds_self[r, h] hx[r, h*C:(h+1)*C]: the diagonal blocks of one (rows, 2H)^T (rows, H*C) reduction
+            da = weight_grad(torch.cat([ds_self, ds_nbr], dim=-1), hx, ctx.precision, False)[0].reshape(2, H, H, C)
+            da = da.diagonal(dim1=1, dim2=2)                                   # (2, C, H)
+            das, dan = da[0].reshape(a_self.shape), da[1].reshape(a_nbr.shape)
+        if ctx.has_bias and ctx.needs_input_grad[5]:
+            db = g.reshape(-1, g.shape[-1]).sum(0)
+        return dxa, dxb, dk, das, dan, db, None, None, None, None, None, None, None
 
 
 class DiffusionFn(torch.autograd.Function):

@@ -412,6 +412,376 @@ inline hipError_t launch_gat_bwd_cols(const GatBwdColsArgs &a, hipStream_t st) {
   return hipGetLastError();
 }
 
+// Reverse mode of the multi-head aggregation (uds_gat_backward_heads; layouts as GatHeadsArgs in kernels_sparse.hpp).  A work
+// item is one (row, head) in the row pass and one (column, head) in the column pass; alpha / de are (S, H, nnz), ds_* (S, n, H).
+// The upstream gradient is (S, n, H * C) for the concatenation; for the mean it is (S, n, C) and every head reads it scaled by
+// 1 / H (gscale).  Per head the operations are those of k_gat_bwd_rows_g<G, NC, true> / k_gat_bwd_rows and k_gat_bwd_cols[_g]:
+// H = 1 with concatenation is bitwise equal to uds_gat_backward_ex.
+struct GatBwdHeadsArgs {
+  const int32_t *rowptr, *col, *rowptr_t, *col_t, *perm_t;
+  const float *g, *hx, *s_self, *s_nbr, *a_self, *a_nbr, *mask, *coef;
+  float *alpha, *de, *d_hx, *ds_self, *ds_nbr;
+  int n, H, c4, S, G, mean;       // G: lanes per item of the walking row pass (lanes_per_item(c4))
+  int64_t nnz;
+};
+
+__device__ __forceinline__ float4 scaled(float4 v, float f) { return make_float4(v.x * f, v.y * f, v.z * f, v.w * f); }
+
+template <int G, int NC>
+__global__ __launch_bounds__(256) void k_gat_bwd_rows_hg(GatBwdHeadsArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int c = (int)(t % G);
+  const int64_t items = (int64_t)a.n * a.H;
+  const bool row_ok = t / G < items;
+  const int64_t it = row_ok ? t / G : items - 1;
+  const int i = (int)(it / a.H), h = (int)(it % a.H);
+  const int s = blockIdx.y;
+  const int beg = a.rowptr[i], end = a.rowptr[i + 1];
+  const int rs = a.H * a.c4;
+  const float *sn = a.s_nbr + (int64_t)s * a.n * a.H + h;
+  const float ss = a.s_self[((int64_t)s * a.n + i) * a.H + h];
+  const float4 *g4 = reinterpret_cast<const float4 *>(a.g) + (a.mean ? ((int64_t)s * a.n + i) * a.c4 : ((int64_t)s * a.n + i) * rs + h * a.c4) + c;
+  const float4 *hx4 = reinterpret_cast<const float4 *>(a.hx) + (int64_t)s * a.n * rs + h * a.c4 + c;
+  float *al = a.alpha + ((int64_t)s * a.H + h) * a.nnz, *de = a.de + ((int64_t)s * a.H + h) * a.nnz;
+  const float *mk = a.mask ? a.mask + (int64_t)s * a.nnz : nullptr;
+  const float *cf = a.coef ? a.coef + ((int64_t)s * a.H + h) * a.nnz : nullptr;
+  float4 gv[NC];
+#pragma unroll
+  for (int q = 0; q < NC; ++q) gv[q] = g4[G * q];
+  if (a.mean) {
+    const float rh = 1.0f / (float)a.H;
+#pragma unroll
+    for (int q = 0; q < NC; ++q) gv[q] = scaled(gv[q], rh);
+  }
+  float m = -INFINITY, l0 = 0.f, c0 = 1.f;
+  int j0 = 0;
+  bool on0 = true;
+  for (int b0 = beg; b0 < end; b0 += G) {
+    const int p = b0 + c;
+    const int pc = min(p, end - 1);
+    const int j = a.col[pc];
+    const float lgt = ss + sn[(int64_t)j * a.H];
+    bool on = p < end;
+    if (mk) on = on && (mk[pc] != 0.0f || j == i);
+    if (b0 == beg) {
+      j0 = j;
+      l0 = lgt;
+      on0 = on;
+      if (cf) c0 = cf[pc];
+    }
+    m = fmaxf(m, on ? leaky02(lgt) : -INFINITY);
+  }
+  m = group_max<G>(m);
+  const bool single = end - beg <= G;
+  float den = 0.f, cn = 0.f, wk = 0.f, qk = 0.f, lk = 0.f, ck = 1.f;
+  bool onk = true;
+  for (int b0 = beg; b0 < end; b0 += G) {
+    const int p = b0 + c;
+    int j = j0;
+    float lgt = l0, cv = c0;
+    bool on = on0;
+    if (b0 != beg) {
+      const int pc = min(p, end - 1);
+      j = a.col[pc];
+      lgt = ss + sn[(int64_t)j * a.H];
+      on = p < end;
+      if (mk) on = on && (mk[pc] != 0.0f || j == i);
+      if (cf) cv = cf[pc];
+    }
+    const float w = on ? expf(leaky02(lgt) - m) : 0.f;
+    const int nk = min(G, end - b0);
+    float qm = 0.f;
+    for (int k0 = 0; k0 < nk; k0 += GU) {
+      float ww[GU], qq[GU], cc[GU];
+      float4 hv[GU][NC];
+#pragma unroll
+      for (int u = 0; u < GU; ++u) {
+        const int k = min(k0 + u, nk - 1);
+        const int jj = __shfl(j, k, G);
+        ww[u] = __shfl(w, k, G);
+        if (cf) cc[u] = __shfl(cv, k, G);
+#pragma unroll
+        for (int v = 0; v < NC; ++v) hv[u][v] = hx4[(int64_t)jj * rs + G * v];
+      }
+#pragma unroll
+      for (int u = 0; u < GU; ++u) {
+        float q = 0.f;
+#pragma unroll
+        for (int v = 0; v < NC; ++v)
+          q = fmaf(gv[v].x, hv[u][v].x, fmaf(gv[v].y, hv[u][v].y, fmaf(gv[v].z, hv[u][v].z, fmaf(gv[v].w, hv[u][v].w, q))));
+        qq[u] = q;
+      }
+#pragma unroll
+      for (int o = G >> 1; o > 0; o >>= 1)
+#pragma unroll
+        for (int u = 0; u < GU; ++u) qq[u] += __shfl_xor(qq[u], o);
+      if (cf)
+#pragma unroll
+        for (int u = 0; u < GU; ++u) qq[u] *= cc[u];
+#pragma unroll
+      for (int u = 0; u < GU; ++u)
+        if (k0 + u < nk) {
+          den += ww[u];
+          cn = fmaf(ww[u], qq[u], cn);
+          if (k0 + u == c) qm = qq[u];
+        }
+    }
+    if (single) {
+      wk = w;
+      qk = qm;
+      lk = lgt;
+      ck = cv;
+      onk = on;
+    } else if (p < end && row_ok) {
+      al[p] = w;
+      de[p] = qm;
+    }
+  }
+  const float inv = den > 0.0f ? 1.0f / den : 0.0f;
+  const float cbar = cn * inv;
+  float *dss_out = a.ds_self + ((int64_t)s * a.n + i) * a.H + h;
+  if (single) {
+    const bool mine = c < end - beg;
+    const float w = wk * inv;
+    const float dl = w * (qk - cbar);
+    const float dv = mine && onk ? (lk > 0.0f ? dl : 0.2f * dl) : 0.f;
+    if (mine && row_ok) {
+      al[beg + c] = cf ? w * ck : w;
+      de[beg + c] = dv;
+    }
+    float dss = 0.f;
+    for (int k = 0; k < end - beg; ++k) dss += __shfl(dv, k, G);
+    if (c == 0 && row_ok) *dss_out = dss;
+    return;
+  }
+  float dss = 0.f;
+  for (int b0 = beg; b0 < end; b0 += G) {
+    const int p = b0 + c;
+    float dv = 0.f;
+    if (p < end && row_ok) {
+      const float w = al[p] * inv;
+      const float dl = w * (de[p] - cbar);
+      const int j = a.col[p];
+      dv = mk && !(mk[p] != 0.0f || j == i) ? 0.f : (ss + sn[(int64_t)j * a.H] > 0.0f ? dl : 0.2f * dl);
+      al[p] = cf ? w * cf[p] : w;
+      de[p] = dv;
+    }
+    dss += dv;
+  }
+#pragma unroll
+  for (int o = G >> 1; o > 0; o >>= 1) dss += __shfl_xor(dss, o);
+  if (c == 0 && row_ok) *dss_out = dss;
+}
+
+// The walking row pass per (row, head): a.G lanes per item, the operations of k_gat_bwd_rows.
+__global__ __launch_bounds__(256) void k_gat_bwd_rows_hx(GatBwdHeadsArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int lg = (int)(t % a.G);
+  const int64_t items = (int64_t)a.n * a.H;
+  const bool row_ok = t / a.G < items;
+  const int64_t it = row_ok ? t / a.G : items - 1;
+  const int i = (int)(it / a.H), h = (int)(it % a.H);
+  const int s = blockIdx.y;
+  const int beg = a.rowptr[i], end = a.rowptr[i + 1];
+  const int rs = a.H * a.c4;
+  const float *sn = a.s_nbr + (int64_t)s * a.n * a.H + h;
+  const float ss = a.s_self[((int64_t)s * a.n + i) * a.H + h];
+  const float4 *g4 = reinterpret_cast<const float4 *>(a.g) + (a.mean ? ((int64_t)s * a.n + i) * a.c4 : ((int64_t)s * a.n + i) * rs + h * a.c4);
+  const float4 *hx4 = reinterpret_cast<const float4 *>(a.hx) + (int64_t)s * a.n * rs + h * a.c4;
+  float *al = a.alpha + ((int64_t)s * a.H + h) * a.nnz, *de = a.de + ((int64_t)s * a.H + h) * a.nnz;
+  const float *mk = a.mask ? a.mask + (int64_t)s * a.nnz : nullptr;
+  const float *cf = a.coef ? a.coef + ((int64_t)s * a.H + h) * a.nnz : nullptr;
+  const float gscale = 1.0f / (float)a.H;
+  float *dss_out = a.ds_self + ((int64_t)s * a.n + i) * a.H + h;
+  float m = -INFINITY;
+  for (int p = beg; p < end; ++p) {
+    const int j = a.col[p];
+    if (!mk || mk[p] != 0.0f || j == i) m = fmaxf(m, leaky02(ss + sn[(int64_t)j * a.H]));
+  }
+  float den = 0.f, cn = 0.f;
+  const bool single = end - beg <= a.G;
+  float wk = 0.f, qk = 0.f;
+  bool pos = false, onk = true;
+  for (int p = beg; p < end; ++p) {
+    const int j = a.col[p];
+    const float lgt = ss + sn[(int64_t)j * a.H];
+    const bool on = !mk || mk[p] != 0.0f || j == i;
+    const float w = on ? expf(leaky02(lgt) - m) : 0.f;
+    float q = 0.f;
+    for (int c = lg; c < a.c4; c += a.G) {
+      float4 gv = g4[c];
+      if (a.mean) gv = scaled(gv, gscale);
+      const float4 hv = hx4[(int64_t)j * rs + c];
+      q = fmaf(gv.x, hv.x, fmaf(gv.y, hv.y, fmaf(gv.z, hv.z, fmaf(gv.w, hv.w, q))));
+    }
+    for (int o = a.G >> 1; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    if (cf) q *= cf[p];
+    den += w;
+    cn = fmaf(w, q, cn);
+    if (single) {
+      if (p - beg == lg) {
+        wk = w;
+        qk = q;
+        pos = lgt > 0.0f;
+        onk = on;
+      }
+    } else if (lg == 0 && row_ok) {
+      al[p] = w;
+      de[p] = q;
+    }
+  }
+  const float inv = den > 0.0f ? 1.0f / den : 0.0f;
+  const float cbar = cn * inv;
+  if (single) {
+    const bool mine = lg < end - beg;
+    const float w = wk * inv;
+    const float dl = w * (qk - cbar);
+    const float dv = mine && onk ? (pos ? dl : 0.2f * dl) : 0.f;
+    if (mine && row_ok) {
+      al[beg + lg] = cf ? w * cf[beg + lg] : w;
+      de[beg + lg] = dv;
+    }
+    float dss = 0.f;
+    for (int k = 0; k < end - beg; ++k) dss += __shfl(dv, k, a.G);
+    if (lg == 0 && row_ok) *dss_out = dss;
+    return;
+  }
+  if (lg != 0 || !row_ok) return;
+  float dss = 0.f;
+  for (int p = beg; p < end; ++p) {       // same lane wrote al / de above
+    const float w = al[p] * inv;
+    const float dl = w * (de[p] - cbar);
+    const int j = a.col[p];
+    const float dv = mk && !(mk[p] != 0.0f || j == i) ? 0.f : (ss + sn[(int64_t)j * a.H] > 0.0f ? dl : 0.2f * dl);
+    al[p] = cf ? w * cf[p] : w;
+    de[p] = dv;
+    dss += dv;
+  }
+  *dss_out = dss;
+}
+
+template <int G, int NC>
+__global__ __launch_bounds__(256) void k_gat_bwd_cols_hg(GatBwdHeadsArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int c = (int)(t % G);
+  const int64_t items = (int64_t)a.n * a.H;
+  const bool row_ok = t / G < items;
+  const int64_t it = row_ok ? t / G : items - 1;
+  const int j = (int)(it / a.H), h = (int)(it % a.H);
+  const int s = blockIdx.y;
+  const int rs = a.H * a.c4, gs = a.mean ? a.c4 : rs;
+  const float4 *g4 = reinterpret_cast<const float4 *>(a.g) + (int64_t)s * a.n * gs + (a.mean ? 0 : h * a.c4) + c;
+  const float *al = a.alpha + ((int64_t)s * a.H + h) * a.nnz, *de = a.de + ((int64_t)s * a.H + h) * a.nnz;
+  const float gscale = 1.0f / (float)a.H;
+  float4 acc[NC];
+#pragma unroll
+  for (int q = 0; q < NC; ++q) acc[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float dsn = 0.f;
+  const int beg = a.rowptr_t[j], end = a.rowptr_t[j + 1];
+  for (int b0 = beg; b0 < end; b0 += G) {
+    const int p = min(b0 + c, end - 1);
+    const int i = a.col_t[p], k = a.perm_t[p];
+    const float w = al[k], d = de[k];
+    const int nk = min(G, end - b0);
+    for (int e0 = 0; e0 < nk; e0 += GU) {
+      float ww[GU], dd[GU];
+      float4 gv[GU][NC];
+#pragma unroll
+      for (int u = 0; u < GU; ++u) {
+        const int e = min(e0 + u, nk - 1);
+        const int ii = __shfl(i, e, G);
+        ww[u] = __shfl(w, e, G);
+        dd[u] = __shfl(d, e, G);
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+          gv[u][q] = g4[(int64_t)ii * gs + G * q];
+          if (a.mean) gv[u][q] = scaled(gv[u][q], gscale);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < GU; ++u)
+        if (e0 + u < nk) {
+          dsn += dd[u];
+#pragma unroll
+          for (int q = 0; q < NC; ++q) {
+            acc[q].x = fmaf(ww[u], gv[u][q].x, acc[q].x);
+            acc[q].y = fmaf(ww[u], gv[u][q].y, acc[q].y);
+            acc[q].z = fmaf(ww[u], gv[u][q].z, acc[q].z);
+            acc[q].w = fmaf(ww[u], gv[u][q].w, acc[q].w);
+          }
+        }
+    }
+  }
+  if (!row_ok) return;
+  const float dss = a.ds_self[((int64_t)s * a.n + j) * a.H + h];
+#pragma unroll
+  for (int q = 0; q < NC; ++q) {
+    const float4 as = reinterpret_cast<const float4 *>(a.a_self)[h * a.c4 + c + G * q];
+    const float4 an = reinterpret_cast<const float4 *>(a.a_nbr)[h * a.c4 + c + G * q];
+    float4 o;
+    o.x = fmaf(an.x, dsn, fmaf(as.x, dss, acc[q].x));
+    o.y = fmaf(an.y, dsn, fmaf(as.y, dss, acc[q].y));
+    o.z = fmaf(an.z, dsn, fmaf(as.z, dss, acc[q].z));
+    o.w = fmaf(an.w, dsn, fmaf(as.w, dss, acc[q].w));
+    reinterpret_cast<float4 *>(a.d_hx)[((int64_t)s * a.n + j) * rs + h * a.c4 + c + G * q] = o;
+  }
+  if (c == 0) a.ds_nbr[((int64_t)s * a.n + j) * a.H + h] = dsn;
+}
+
+__global__ __launch_bounds__(256) void k_gat_bwd_cols_hx(GatBwdHeadsArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (int64_t)a.n * a.H * a.c4) return;
+  const int s = blockIdx.y;
+  const int c = (int)(t % a.c4);
+  const int64_t it = t / a.c4;
+  const int j = (int)(it / a.H), h = (int)(it % a.H);
+  const int rs = a.H * a.c4, gs = a.mean ? a.c4 : rs;
+  const float4 *g4 = reinterpret_cast<const float4 *>(a.g) + (int64_t)s * a.n * gs + (a.mean ? 0 : h * a.c4) + c;
+  const float *al = a.alpha + ((int64_t)s * a.H + h) * a.nnz, *de = a.de + ((int64_t)s * a.H + h) * a.nnz;
+  const float gscale = 1.0f / (float)a.H;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  float dsn = 0.f;
+  for (int p = a.rowptr_t[j]; p < a.rowptr_t[j + 1]; ++p) {
+    const int i = a.col_t[p], k = a.perm_t[p];
+    const float w = al[k];
+    float4 gv = g4[(int64_t)i * gs];
+    if (a.mean) gv = scaled(gv, gscale);
+    acc.x = fmaf(w, gv.x, acc.x);
+    acc.y = fmaf(w, gv.y, acc.y);
+    acc.z = fmaf(w, gv.z, acc.z);
+    acc.w = fmaf(w, gv.w, acc.w);
+    dsn += de[k];
+  }
+  const float dss = a.ds_self[((int64_t)s * a.n + j) * a.H + h];
+  const float4 as = reinterpret_cast<const float4 *>(a.a_self)[h * a.c4 + c], an = reinterpret_cast<const float4 *>(a.a_nbr)[h * a.c4 + c];
+  acc.x = fmaf(an.x, dsn, fmaf(as.x, dss, acc.x));
+  acc.y = fmaf(an.y, dsn, fmaf(as.y, dss, acc.y));
+  acc.z = fmaf(an.z, dsn, fmaf(as.z, dss, acc.z));
+  acc.w = fmaf(an.w, dsn, fmaf(as.w, dss, acc.w));
+  reinterpret_cast<float4 *>(a.d_hx)[((int64_t)s * a.n + j) * rs + h * a.c4 + c] = acc;
+  if (c == 0) a.ds_nbr[((int64_t)s * a.n + j) * a.H + h] = dsn;
+}
+
+inline hipError_t launch_gat_bwd_heads(const GatBwdHeadsArgs &a, hipStream_t st) {
+  int G, NC;
+  group_shape(a.c4, G, NC);
+  const int64_t items = (int64_t)a.n * a.H;
+  if (G) {
+    hipError_t e = launch_grouped(a, items, a.S, a.c4, st, [&](auto g_, auto nc_, dim3 grid) {
+      hipLaunchKernelGGL((k_gat_bwd_rows_hg<decltype(g_)::value, decltype(nc_)::value>), grid, dim3(256), 0, st, a);
+    });
+    if (e != hipSuccess) return e;
+    return launch_grouped(a, items, a.S, a.c4, st, [&](auto g_, auto nc_, dim3 grid) {
+      hipLaunchKernelGGL((k_gat_bwd_cols_hg<decltype(g_)::value, decltype(nc_)::value>), grid, dim3(256), 0, st, a);
+    });
+  }
+  hipLaunchKernelGGL(k_gat_bwd_rows_hx, dim3((unsigned)((items * a.G + 255) / 256), (unsigned)a.S), dim3(256), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_gat_bwd_cols_hx, dim3((unsigned)((items * a.c4 + 255) / 256), (unsigned)a.S), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 // out[k] = sum_s <a[s, row(k), :], b[s, col(k), :]> for every pattern entry k: the gradient of a per-entry weight of
 // out = A(val) @ x  (a = dL/dout, b = x).  G lanes per entry walk the snapshots.
 struct SddmmArgs {

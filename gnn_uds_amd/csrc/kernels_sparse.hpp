@@ -496,6 +496,256 @@ inline hipError_t launch_gat_aggregate_ex(const GatArgs &a, const GatEx &x, hipS
   return hipGetLastError();
 }
 
+// Multi-head GATConv (spektral GATConv with attn_heads = H > 1, concat_heads true or false, return_attn_coef;
+// uds_gat_aggregate_heads).  hx (S, n, H * C) with head-major columns, scores (S, n, H), coef and alpha_out (S, H, nnz), the edge
+// mask (S, nnz) shared by the heads.  A work item is one (row, head) for the concatenation and one row, walking its heads, for the
+// mean: the mean needs the sum over the heads before bias and activation, and the entry has no workspace to park them in.
+// Per head the operations and their order are those of k_gat_aggregate_g<G, NC, true> / k_gat_aggregate_x, so H = 1 with
+// concatenation is bitwise equal to uds_gat_aggregate_ex.  alpha_out, when given, gets alpha * coef of every entry of every head
+// (0 for a masked one) in a third walk that recomputes the weights with the same operations the aggregation used.
+struct GatHeadsArgs {
+  const int32_t *rowptr, *col, *order;
+  const float *hx, *s_self, *s_nbr, *bias, *mask, *coef;
+  float *out, *alpha_out;
+  int n, H, c4, act, S, mean;
+  int64_t nnz;
+};
+
+// MEAN: the head loop and the cross-head sum exist in the mean instantiations only (the concatenation keeps the registers of one head)
+template <int G, int NC, bool MEAN>
+__global__ __launch_bounds__(256) void k_gat_aggregate_hg(GatHeadsArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t grp = t / G;
+  const int c = (int)(t % G);
+  const int per_row = MEAN ? 1 : a.H;                     // items per row
+  const int64_t items = (int64_t)a.n * per_row;
+  const bool item_ok = grp < items;
+  const int64_t it = item_ok ? grp : items - 1;             // surplus groups shadow the last item (they take part in the shuffles)
+  const int i = a.order[it / per_row];
+  const int h_beg = MEAN ? 0 : (int)(it % per_row), h_end = MEAN ? a.H : h_beg + 1;
+  const int s = blockIdx.y;
+  const int beg = a.rowptr[i], end = a.rowptr[i + 1];
+  const int rs = a.H * a.c4;                                // float4 chunks of one hx row
+  const float *mk = a.mask ? a.mask + (int64_t)s * a.nnz : nullptr;
+  float4 tot[NC];
+#pragma unroll
+  for (int q = 0; q < NC; ++q) tot[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int h = h_beg; h < h_end; ++h) {
+    const float *sn = a.s_nbr + (int64_t)s * a.n * a.H + h;
+    const float ss = a.s_self[((int64_t)s * a.n + i) * a.H + h];
+    const float *cf = a.coef ? a.coef + ((int64_t)s * a.H + h) * a.nnz : nullptr;
+    float m = -INFINITY, l0 = -INFINITY, c0 = 1.0f;
+    int j0 = 0;
+    for (int b0 = beg; b0 < end; b0 += G) {
+      const int p = b0 + c;
+      const int pc = min(p, end - 1);
+      const int j = a.col[pc];
+      bool on = p < end;
+      if (mk) on = on && (mk[pc] != 0.0f || j == i);
+      const float l = on ? leaky02(ss + sn[(int64_t)j * a.H]) : -INFINITY;
+      if (b0 == beg) {
+        j0 = j;
+        l0 = l;
+        if (cf) c0 = cf[pc];
+      }
+      m = fmaxf(m, l);
+    }
+    m = group_max<G>(m);
+    const float4 *hx4 = reinterpret_cast<const float4 *>(a.hx) + (int64_t)s * a.n * rs + h * a.c4 + c;
+    float den = 0.0f;
+    float4 acc[NC];
+#pragma unroll
+    for (int q = 0; q < NC; ++q) acc[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int b0 = beg; b0 < end; b0 += G) {
+      const int p = b0 + c;
+      int j = j0;
+      float l = l0, cv = c0;
+      if (b0 != beg) {
+        const int pc = min(p, end - 1);
+        j = a.col[pc];
+        bool on = p < end;
+        if (mk) on = on && (mk[pc] != 0.0f || j == i);
+        l = on ? leaky02(ss + sn[(int64_t)j * a.H]) : -INFINITY;
+        if (cf) cv = cf[pc];
+      }
+      const float w = l == -INFINITY ? 0.0f : expf(l - m);
+      const float wc = cf ? w * cv : w;
+      const int nk = min(G, end - b0);
+      for (int k0 = 0; k0 < nk; k0 += GU) {
+        float ww[GU], wm[GU];
+        float4 hv[GU][NC];
+#pragma unroll
+        for (int u = 0; u < GU; ++u) {
+          const int k = min(k0 + u, nk - 1);
+          const int jj = __shfl(j, k, G);
+          ww[u] = __shfl(w, k, G);
+          wm[u] = cf ? __shfl(wc, k, G) : ww[u];
+#pragma unroll
+          for (int q = 0; q < NC; ++q) hv[u][q] = hx4[(int64_t)jj * rs + G * q];
+        }
+#pragma unroll
+        for (int u = 0; u < GU; ++u)
+          if (k0 + u < nk) {
+            den += ww[u];
+#pragma unroll
+            for (int q = 0; q < NC; ++q) {
+              acc[q].x = fmaf(wm[u], hv[u][q].x, acc[q].x);
+              acc[q].y = fmaf(wm[u], hv[u][q].y, acc[q].y);
+              acc[q].z = fmaf(wm[u], hv[u][q].z, acc[q].z);
+              acc[q].w = fmaf(wm[u], hv[u][q].w, acc[q].w);
+            }
+          }
+      }
+    }
+    const float inv = den > 0.0f ? 1.0f / den : 0.0f;
+    if (a.alpha_out && item_ok) {
+      float *ao = a.alpha_out + ((int64_t)s * a.H + h) * a.nnz;
+      for (int p = beg + c; p < end; p += G) {
+        const int j = a.col[p];
+        const bool on = !mk || mk[p] != 0.0f || j == i;
+        const float w = on ? expf(leaky02(ss + sn[(int64_t)j * a.H]) - m) : 0.0f;
+        ao[p] = (cf ? w * cf[p] : w) * inv;
+      }
+    }
+    if (MEAN) {
+#pragma unroll
+      for (int q = 0; q < NC; ++q) {
+        tot[q].x = fmaf(acc[q].x, inv, tot[q].x);
+        tot[q].y = fmaf(acc[q].y, inv, tot[q].y);
+        tot[q].z = fmaf(acc[q].z, inv, tot[q].z);
+        tot[q].w = fmaf(acc[q].w, inv, tot[q].w);
+      }
+    } else if (item_ok) {
+#pragma unroll
+      for (int q = 0; q < NC; ++q) {
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a.bias) b = reinterpret_cast<const float4 *>(a.bias)[h * a.c4 + c + G * q];
+        float4 o;
+        with_act(a.act, [&](auto act_) {
+          constexpr int A = decltype(act_)::value;
+          o.x = act_ct<A>(fmaf(acc[q].x, inv, b.x), a.act);
+          o.y = act_ct<A>(fmaf(acc[q].y, inv, b.y), a.act);
+          o.z = act_ct<A>(fmaf(acc[q].z, inv, b.z), a.act);
+          o.w = act_ct<A>(fmaf(acc[q].w, inv, b.w), a.act);
+        });
+        reinterpret_cast<float4 *>(a.out)[((int64_t)s * a.n + i) * rs + h * a.c4 + c + G * q] = o;
+      }
+    }
+  }
+  if (!MEAN || !item_ok) return;
+  const float rh = 1.0f / (float)a.H;
+#pragma unroll
+  for (int q = 0; q < NC; ++q) {
+    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (a.bias) b = reinterpret_cast<const float4 *>(a.bias)[c + G * q];
+    float4 o;
+    with_act(a.act, [&](auto act_) {
+      constexpr int A = decltype(act_)::value;
+      o.x = act_ct<A>(fmaf(tot[q].x, rh, b.x), a.act);
+      o.y = act_ct<A>(fmaf(tot[q].y, rh, b.y), a.act);
+      o.z = act_ct<A>(fmaf(tot[q].z, rh, b.z), a.act);
+      o.w = act_ct<A>(fmaf(tot[q].w, rh, b.w), a.act);
+    });
+    reinterpret_cast<float4 *>(a.out)[((int64_t)s * a.n + i) * a.c4 + c + G * q] = o;
+  }
+}
+
+// One lane per (row, head, 16-byte chunk) -- per (row, chunk) for the mean -- for the head widths group_shape does not cover
+// (C / 4 = 1, 3, ..): the operations of k_gat_aggregate_x per head.  The lane of chunk 0 writes alpha_out.
+__global__ __launch_bounds__(256) void k_gat_aggregate_hx(GatHeadsArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int per_row = a.mean ? 1 : a.H;
+  if (t >= (int64_t)a.n * per_row * a.c4) return;
+  const int s = blockIdx.y;
+  const int c = (int)(t % a.c4);
+  const int64_t it = t / a.c4;
+  const int i = a.order[it / per_row];
+  const int h_beg = a.mean ? 0 : (int)(it % per_row), h_end = a.mean ? a.H : h_beg + 1;
+  const int beg = a.rowptr[i], end = a.rowptr[i + 1];
+  const int rs = a.H * a.c4;
+  const float *mk = a.mask ? a.mask + (int64_t)s * a.nnz : nullptr;
+  float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int h = h_beg; h < h_end; ++h) {
+    const float *sn = a.s_nbr + (int64_t)s * a.n * a.H + h;
+    const float ss = a.s_self[((int64_t)s * a.n + i) * a.H + h];
+    const float *cf = a.coef ? a.coef + ((int64_t)s * a.H + h) * a.nnz : nullptr;
+    float m = -INFINITY;
+    for (int p = beg; p < end; ++p) {
+      const int j = a.col[p];
+      if (!mk || mk[p] != 0.0f || j == i) m = fmaxf(m, leaky02(ss + sn[(int64_t)j * a.H]));
+    }
+    const float4 *hx4 = reinterpret_cast<const float4 *>(a.hx) + (int64_t)s * a.n * rs + h * a.c4 + c;
+    float den = 0.0f;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int p = beg; p < end; ++p) {
+      const int j = a.col[p];
+      if (mk && !(mk[p] != 0.0f || j == i)) continue;
+      const float w = expf(leaky02(ss + sn[(int64_t)j * a.H]) - m);
+      const float wc = cf ? w * cf[p] : w;
+      const float4 hv = hx4[(int64_t)j * rs];
+      den += w;
+      acc.x = fmaf(wc, hv.x, acc.x);
+      acc.y = fmaf(wc, hv.y, acc.y);
+      acc.z = fmaf(wc, hv.z, acc.z);
+      acc.w = fmaf(wc, hv.w, acc.w);
+    }
+    const float inv = den > 0.0f ? 1.0f / den : 0.0f;
+    if (a.alpha_out && c == 0) {
+      float *ao = a.alpha_out + ((int64_t)s * a.H + h) * a.nnz;
+      for (int p = beg; p < end; ++p) {
+        const int j = a.col[p];
+        const bool on = !mk || mk[p] != 0.0f || j == i;
+        const float w = on ? expf(leaky02(ss + sn[(int64_t)j * a.H]) - m) : 0.0f;
+        ao[p] = (cf ? w * cf[p] : w) * inv;
+      }
+    }
+    if (a.mean) {
+      tot.x = fmaf(acc.x, inv, tot.x);
+      tot.y = fmaf(acc.y, inv, tot.y);
+      tot.z = fmaf(acc.z, inv, tot.z);
+      tot.w = fmaf(acc.w, inv, tot.w);
+    } else {
+      float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (a.bias) b = reinterpret_cast<const float4 *>(a.bias)[h * a.c4 + c];
+      float4 o;
+      with_act(a.act, [&](auto act_) {
+        constexpr int A = decltype(act_)::value;
+        o.x = act_ct<A>(fmaf(acc.x, inv, b.x), a.act);
+        o.y = act_ct<A>(fmaf(acc.y, inv, b.y), a.act);
+        o.z = act_ct<A>(fmaf(acc.z, inv, b.z), a.act);
+        o.w = act_ct<A>(fmaf(acc.w, inv, b.w), a.act);
+      });
+      reinterpret_cast<float4 *>(a.out)[((int64_t)s * a.n + i) * rs + h * a.c4 + c] = o;
+    }
+  }
+  if (!a.mean) return;
+  const float rh = 1.0f / (float)a.H;
+  float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (a.bias) b = reinterpret_cast<const float4 *>(a.bias)[c];
+  float4 o;
+  with_act(a.act, [&](auto act_) {
+    constexpr int A = decltype(act_)::value;
+    o.x = act_ct<A>(fmaf(tot.x, rh, b.x), a.act);
+    o.y = act_ct<A>(fmaf(tot.y, rh, b.y), a.act);
+    o.z = act_ct<A>(fmaf(tot.z, rh, b.z), a.act);
+    o.w = act_ct<A>(fmaf(tot.w, rh, b.w), a.act);
+  });
+  reinterpret_cast<float4 *>(a.out)[((int64_t)s * a.n + i) * a.c4 + c] = o;
+}
+
+inline hipError_t launch_gat_aggregate_heads(const GatHeadsArgs &a, hipStream_t st) {
+  int G, NC;
+  group_shape(a.c4, G, NC);
+  const int64_t items = (int64_t)a.n * (a.mean ? 1 : a.H);
+  if (G)
+    return launch_grouped(a, items, a.S, a.c4, st, [&](auto g_, auto nc_, dim3 grid) {
+      if (a.mean) hipLaunchKernelGGL((k_gat_aggregate_hg<decltype(g_)::value, decltype(nc_)::value, true>), grid, dim3(256), 0, st, a);
+      else hipLaunchKernelGGL((k_gat_aggregate_hg<decltype(g_)::value, decltype(nc_)::value, false>), grid, dim3(256), 0, st, a);
+    });
+  hipLaunchKernelGGL(k_gat_aggregate_hx, dim3((unsigned)((items * a.c4 + 255) / 256), (unsigned)a.S), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
 // out[b,t,r,:] = act(sum_{t' <= t} x[b,t',r,:] + res[b,0,r,:])   -- `cumsum(x_out, axis=1) + tile(res)` then the
 // activation (emulator.py:313-320).  One lane owns one float4 feature chunk of one (b, r) and walks the T steps.
 struct CumsumArgs {

@@ -1079,6 +1079,47 @@ int uds_gat_backward_ex(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *
   return UDS_OK;
 }
 
+int uds_gat_aggregate_heads(const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr, const float *bias,
+                            const float *edge_mask, const float *coef, int64_t S, int64_t H, int64_t C, int concat, int act,
+                            float *out, float *alpha_out, uds_stream_t stream) {
+  UDS_REQUIRE(g && hx && s_self && s_nbr && out, "uds_gat_aggregate_heads: NULL argument");
+  UDS_REQUIRE(g->n_rows == g->n_cols, "uds_gat_aggregate_heads: pattern must be square");
+  UDS_REQUIRE(H > 0 && H <= 64, "uds_gat_aggregate_heads: H=%lld outside [1,64]", (long long)H);
+  UDS_REQUIRE(C > 0 && C % 4 == 0 && C <= 256, "uds_gat_aggregate_heads: C=%lld must be a multiple of 4, at most 256", (long long)C);
+  UDS_REQUIRE(S >= 0 && S <= 65535, "uds_gat_aggregate_heads: S=%lld outside [0,65535]", (long long)S);
+  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "uds_gat_aggregate_heads: unknown activation %d", act);
+  UDS_REQUIRE(aligned16(hx) && aligned16(out) && aligned16(bias), "uds_gat_aggregate_heads: hx/out/bias must be 16-byte aligned");
+  if (S == 0 || g->n_rows == 0) return UDS_OK;
+  uds::GatHeadsArgs a{g->d_rowptr, g->d_col, g->d_order, hx, s_self, s_nbr, bias, edge_mask, coef, out, alpha_out,
+                      (int)g->n_rows, (int)H, (int)(C / 4), act, (int)S, concat ? 0 : 1, g->nnz};
+  hipError_t e = uds::launch_gat_aggregate_heads(a, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_aggregate_heads: launch -> %s", hipGetErrorString(e));
+  return UDS_OK;
+}
+
+int uds_gat_backward_heads(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *perm_t, const float *grad, const float *hx,
+                           const float *s_self, const float *s_nbr, const float *a_self, const float *a_nbr,
+                           const float *edge_mask, const float *coef, int64_t S, int64_t H, int64_t C, int concat,
+                           float *alpha_ws, float *de_ws, float *d_hx, float *ds_self, float *ds_nbr, uds_stream_t stream) {
+  UDS_REQUIRE(g && gt && perm_t && grad && hx && s_self && s_nbr && a_self && a_nbr && alpha_ws && de_ws && d_hx && ds_self && ds_nbr,
+              "uds_gat_backward_heads: NULL argument");
+  UDS_REQUIRE(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_cols && gt->nnz == g->nnz,
+              "uds_gat_backward_heads: the pattern and its transpose must be square with the same shape and entry count");
+  UDS_REQUIRE(H > 0 && H <= 64, "uds_gat_backward_heads: H=%lld outside [1,64]", (long long)H);
+  UDS_REQUIRE(C > 0 && C % 4 == 0 && C <= 256, "uds_gat_backward_heads: C=%lld must be a multiple of 4, at most 256", (long long)C);
+  UDS_REQUIRE(S >= 0 && S <= 65535, "uds_gat_backward_heads: S=%lld outside [0,65535]", (long long)S);
+  UDS_REQUIRE(aligned16(grad) && aligned16(hx) && aligned16(d_hx) && aligned16(a_self) && aligned16(a_nbr),
+              "uds_gat_backward_heads: grad/hx/d_hx/a_self/a_nbr must be 16-byte aligned");
+  if (S == 0 || g->n_rows == 0) return UDS_OK;
+  const int c4 = (int)(C / 4);
+  uds::GatBwdHeadsArgs a{g->d_rowptr, g->d_col, gt->d_rowptr, gt->d_col, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, edge_mask, coef,
+                         alpha_ws, de_ws, d_hx, ds_self, ds_nbr, (int)g->n_rows, (int)H, c4, (int)S, uds::lanes_per_item(c4),
+                         concat ? 0 : 1, g->nnz};
+  hipError_t e = uds::launch_gat_bwd_heads(a, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_backward_heads: launch -> %s", hipGetErrorString(e));
+  return UDS_OK;
+}
+
 int uds_csr_sddmm(const uds_csr_t *csr, const float *a, const float *b, int64_t S, int64_t F, float *out, uds_stream_t stream) {
   UDS_REQUIRE(csr && a && b && out, "uds_csr_sddmm: NULL argument");
   UDS_REQUIRE(S >= 0 && F > 0 && F % 4 == 0, "uds_csr_sddmm: S=%lld F=%lld (F must be a positive multiple of 4)", (long long)S,

@@ -351,6 +351,8 @@ def hip_layers(prob, global_params, embed_size, activation='relu', precision='bf
     from .layers import SpatialLayer
     layers = []
     for p in global_params:
+        if p['gx_k'].dim() == 3 and p['gx_k'].shape[1] != 1:
+            raise NotImplementedError('hip_layers: attn_heads=%d -- the sharded layers are single-head' % p['gx_k'].shape[1])
         fx, fe = p['ex_k'].shape[0], p['xe_k'].shape[0]
         ly = SpatialLayer(prob.graph, embed_size, activation, fx=fx, fe=fe, sparse_params=True, precision=precision).to(device)
         f = lambda t: None if t is None else t.to(torch.float32).to(device).contiguous()
@@ -642,6 +644,8 @@ def _refuse_unsharded_configuration(emul):
         return NotImplementedError, 'use_adj: the per-step adjacency of block 2 is not sharded'
     if emul.dropout:
         return NotImplementedError, 'dropout=%r: the sharded forward is inference only' % emul.dropout
+    if getattr(emul, 'attn_heads', 1) > 1:
+        return NotImplementedError, 'attn_heads=%d: the sharded layers and their halo backward are single-head' % emul.attn_heads
     for bi, block in enumerate((emul.block1, emul.block2)):
         for li, ly in enumerate(block.layers):
             for name in ('node_edge_n', 'node_edge_e'):

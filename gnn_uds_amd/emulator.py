@@ -247,6 +247,9 @@ class Emulator(nn.Module):
         self.kernel_size, self.n_sp_layer, self.n_tp_layer = g('kernel_size', 3), g('n_sp_layer', 3), g('n_tp_layer', 2)
         self.dropout = g('dropout', 0.0)
         self.activation = g('activation', 'relu')
+        # attention heads of the GATConv layers: NOT a reference key (the reference builds every GATConv with Spektral's default,
+        # one head); H > 1 gives H heads of embed_size / H channels each, concatenated -- the same width and bytes per row
+        self.attn_heads = int(g('attn_heads', 1) or 1)
         self.if_flood = int(g('if_flood', 0))
         if self.if_flood:
             self.n_in += 1
@@ -382,10 +385,11 @@ class Emulator(nn.Module):
         sp = self.n_node * self.n_edge > (1 << 24) if sp is None else bool(sp)
         if self.graph_base:
             self.block1 = GraphBaseBlock(self.n_node, self.n_edge, self._base_filter, d, L, a, generator=gen, conv=self.conv_kind,
-                                         precision=precision)                                                          # :220-223
+                                         precision=precision, attn_heads=self.attn_heads)                              # :220-223
         else:
             self.block1 = SpatialBlock(self.graph, d, L, a, sparse_params=sp, generator=gen, precision=precision,
-                                       conv=self.conv_kind, filters=(self.filter, self.edge_filter))                  # :219-235
+                                       conv=self.conv_kind, filters=(self.filter, self.edge_filter),
+                                       attn_heads=self.attn_heads)                                                    # :219-235
         rec = self.recurrent if self.recurrent in ('Conv1D', 'GRU', 'LSTM') else None              # get_tem_nets, :154-163
 
         def tem(f):
@@ -405,10 +409,11 @@ class Emulator(nn.Module):
             if fx2 != fe2:
                 raise ValueError('graph_base stacks node and link rows in block 2: needs act=True (equal widths %d / %d)' % (fx2, fe2))
             self.block2 = GraphBaseBlock(self.n_node, self.n_edge, self._base_filter, d, L, a, f_in=fx2, generator=gen,
-                                         conv=self.conv_kind, precision=precision)                                     # :273-276
+                                         conv=self.conv_kind, precision=precision, attn_heads=self.attn_heads)         # :273-276
         else:
             self.block2 = SpatialBlock(self.graph, d, L, a, fx=fx2, fe=fe2, sparse_params=sp, generator=gen, precision=precision,
-                                       conv=self.conv_kind, filters=(self.filter, self.edge_filter))                  # :272-288
+                                       conv=self.conv_kind, filters=(self.filter, self.edge_filter),
+                                       attn_heads=self.attn_heads)                                                    # :272-288
         self.tem2_x, self.tem2_e = tem(d), tem(d)                                               # :302,308
         self.res_x = Dense(d, 'linear' if self.resnet else a, in_features=H, generator=gen, precision=pr)     # :313 'dense_resx'
         self.res_e = Dense(d, 'linear' if self.resnet else a, in_features=H, generator=gen, precision=pr)     # :317
@@ -513,6 +518,23 @@ class Emulator(nn.Module):
         return out, self.e_out_layer(e).reshape(nb, T, self.n_edge, self.e_out)
 
     # ------------------------------------------------------------------ network forward (build_network)
+    def attention_coefficients(self, X, B, E, AE=None, ADJ=None):
+        """What the GATConv layers attend to: inputs as `forward` takes them, run without autograd and without dropout.  Returns
+        {'block1': [...], 'block2': [...]} with one (alpha_x, alpha_e) pair per spatial layer -- (B, T, H, nnz of the node
+        adjacency) and (B, T, H, nnz of the link adjacency), in the entry order of `self.graph.adj` / `self.graph.edge_adj`
+        (T = seq_in in block 1, seq_out in block 2) -- or, for `graph_base`, one (B, T, H, nnz) tensor per layer.  The softmax
+        coefficients themselves (Spektral's return_attn_coef); works for single-head models too.  The layers run the unfused
+        chain (uds_gat_aggregate_heads): the fused kernels never hold the coefficients."""
+        if not self.conv or self.conv_kind != 'GAT':
+            raise NotImplementedError('attention coefficients exist for conv=GAT models')
+        self._attn_sink = sink = {}
+        try:
+            with torch.no_grad():
+                self.forward(X, B, E, AE, ADJ, training=False)
+        finally:
+            self._attn_sink = None
+        return sink
+
     def forward(self, X, B, E, AE=None, ADJ=None, training=False):
         """ADJ: the per-time-step node adjacency of `use_adj` (emulator.py:178-180,268-271; block 2 only): the edge mask
         (B, T_out, nnz) of `get_adj_action`, or the reference's dense (B, T_out, n, n) integer array (small networks).
@@ -554,7 +576,13 @@ class Emulator(nn.Module):
                 kw['dropout'] = dr
                 if self.conv_kind == 'GAT':      # training=True reaches the GATConv layers too: Spektral's attention dropout (rate 0.5)
                     kw['attn_dropout'] = self.dropout_stream
+            sink = getattr(self, '_attn_sink', None)
+            if sink is not None:                 # attention_coefficients(): the layers run unfused and hand their coefficients out
+                kw['attn_out'] = got = []
             xs, es = block(r(x, self.n_node), r(e, self.n_edge), r(xb, self.n_node), r(eb, self.n_edge), **kw)
+            if sink is not None:
+                bt = lambda t: t.reshape((nb, T) + t.shape[-2:])
+                sink['block1' if block is self.block1 else 'block2'] = [bt(a) if isinstance(a, torch.Tensor) else (bt(a[0]), bt(a[1])) for a in got]
             return xs.reshape(nb, T, self.n_node, -1), es.reshape(nb, T, self.n_edge, -1)
 
         def temporal(mods_x, mods_e, x, e):

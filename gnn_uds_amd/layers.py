@@ -136,21 +136,27 @@ class _GraphArg:
 
 
 class GATConv(nn.Module):
-    """spektral.layers.GATConv in batch/mixed mode, single head (what the reference uses).
+    """spektral.layers.GATConv in batch/mixed mode.
 
     forward([x, a]): x (..., N, F); a = dense (N, N) 0/1 filter as in the reference
     (`emulator.py:143-145,229`), a `graph.CSR`, or a prebuilt `_lib.CsrHandle` (CSR inputs must
     already hold the self loops).  Weights keep Spektral's names and shapes:
-    kernel (F,1,C), attn_kernel_self (C,1,1), attn_kernel_neighs (C,1,1), bias (C)."""
+    kernel (F,H,C), attn_kernel_self (C,H,1), attn_kernel_neighs (C,H,1), bias (H*C) or, with concat_heads=False, (C).
+
+    attn_heads=1 without return_attn_coef is what the reference uses and runs on the single-head kernels.  attn_heads=H > 1,
+    concat_heads=False and return_attn_coef=True run on uds_gat_aggregate_heads / uds_gat_backward_heads (C % 4 == 0,
+    H*C <= 256): forward then returns `out` or `(out, attn)`, attn (..., H, nnz) in the entry order of the pattern
+    (`dense_attn_coef` scatters it to Spektral's (..., N, H, N))."""
 
     def __init__(self, channels, attn_heads=1, concat_heads=True, dropout_rate=0.5, return_attn_coef=False,
                  add_self_loops=True, activation=None, use_bias=True, in_channels=None, generator=None):
         super().__init__()
-        if attn_heads != 1:
-            raise NotImplementedError('the HIP engine builds the single-head GAT the reference uses (attn_heads=1)')
-        if return_attn_coef:
-            raise NotImplementedError('return_attn_coef is not built')
-        self.channels, self.attn_heads, self.concat_heads = int(channels), 1, concat_heads
+        if int(attn_heads) < 1:
+            raise ValueError('GATConv: attn_heads must be positive, got %r' % (attn_heads,))
+        self.channels, self.attn_heads, self.concat_heads = int(channels), int(attn_heads), bool(concat_heads)
+        self.return_attn_coef = bool(return_attn_coef)
+        if (self.attn_heads > 1 or self.return_attn_coef) and self.channels % 4:
+            raise ValueError('GATConv: channels must be a multiple of 4 for attn_heads > 1 or return_attn_coef, got %d' % self.channels)
         self.dropout_rate, self.add_self_loops = dropout_rate, add_self_loops
         self.activation, self.use_bias = activation or 'linear', use_bias
         self._gen = generator
@@ -160,28 +166,64 @@ class GATConv(nn.Module):
         if in_channels is not None:
             self.build(in_channels, 'cpu')
 
-    def build(self, in_channels, device):
-        c = self.channels
-        self.kernel = _param(_glorot_uniform((int(in_channels), 1, c), device, self._gen))
-        self.attn_kernel_self = _param(_glorot_uniform((c, 1, 1), device, self._gen))
-        self.attn_kernel_neighs = _param(_glorot_uniform((c, 1, 1), device, self._gen))
-        self.bias = _param(torch.zeros(c, device=device)) if self.use_bias else None
+    @property
+    def output_dim(self):
+        return self.channels * self.attn_heads if self.concat_heads else self.channels
 
-    def forward(self, inputs, xb=None, edge_mask=None, attn_dropout=None):
+    def build(self, in_channels, device):
+        c, nh = self.channels, self.attn_heads
+        self.kernel = _param(_glorot_uniform((int(in_channels), nh, c), device, self._gen))
+        self.attn_kernel_self = _param(_glorot_uniform((c, nh, 1), device, self._gen))
+        self.attn_kernel_neighs = _param(_glorot_uniform((c, nh, 1), device, self._gen))
+        self.bias = _param(torch.zeros(self.output_dim, device=device)) if self.use_bias else None
+
+    def dense_attn_coef(self, attn, a):
+        """attn (..., H, nnz) as forward returns it -> Spektral's dense (..., N, H, N) coefficients (zero off the pattern of
+        `a`); for small graphs."""
+        h = self._graphs.handle(a, self.add_self_loops)
+        rows = torch.as_tensor(np.repeat(np.arange(h.n_rows), np.diff(h._rowptr.astype(np.int64))), device=attn.device)
+        cols = torch.as_tensor(h._col.astype(np.int64), device=attn.device)
+        dense = attn.new_zeros(tuple(attn.shape[:-1]) + (h.n_rows, h.n_cols))
+        dense[..., rows, cols] = attn
+        return dense.transpose(-3, -2).contiguous()
+
+    def _forward_heads(self, xs, xbs, h, lead, edge_mask, attn_dropout, want_attn):
+        """attn_heads > 1, the mean over heads or return_attn_coef: uds_gat_aggregate_heads, under autograd GatHeadsFn."""
+        nh = self.attn_heads
+        coef = None
+        if attn_dropout is not None and self.dropout_rate:      # one multiplier per (snapshot, head, pattern entry)
+            ones = torch.ones((xs.shape[0], nh, h.nnz), device=xs.device, dtype=torch.float32)
+            coef = _lib.dropout(ones, self.dropout_rate, attn_dropout.seed, attn_dropout.take(ones.numel()))
+        mk = None if edge_mask is None else edge_mask.reshape(-1, edge_mask.shape[-1]).to(torch.float32).contiguous()
+        if coef is not None or _ag.grad_on(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias):
+            out, alpha = _ag.GatHeadsFn.apply(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias,
+                                              self.activation, h, self.precision, self.concat_heads, coef, mk, want_attn)
+        else:
+            out, alpha, _ = _ag.gat_heads_forward(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias,
+                                                  self.activation, h, self.concat_heads, coef, mk, want_attn)
+        out = out.reshape(lead + out.shape[-2:])
+        return (out, alpha.reshape(lead + alpha.shape[-2:])) if want_attn else out
+
+    def forward(self, inputs, xb=None, edge_mask=None, attn_dropout=None, return_attn_coef=None):
         """edge_mask (..., nnz): per-snapshot 0/1 over the entries of the pattern `a` (`use_adj`, emulator.py:268-271: the
         reference feeds a (S, N, N) adjacency here; the mask is that adjacency gathered at the static pattern's entries --
         `Emulator.get_adj_action`).  The diagonal always takes part (set_diag).  Under autograd or with attention dropout the
         layer runs on GatFn (uds_gat_aggregate_ex / uds_gat_backward_ex); otherwise on the inference kernel.
         attn_dropout: a DropoutStream = the layer runs in Keras' training mode and `dropout_rate` > 0: Spektral's dropout on the
-        normalised attention coefficients (`attn_coef_drop = self.dropout(attn_coef)`), one mask entry per (snapshot, pattern entry).
+        normalised attention coefficients (`attn_coef_drop = self.dropout(attn_coef)`), one mask entry per (snapshot, pattern entry)
+        and, with attn_heads = H > 1, per head: S * H * nnz positions of the stream.
         With an edge mask the draw still covers every entry of the static pattern, masked or not (S * nnz values, the order
-        and count of the unmasked layer), so the stream stays aligned with a model built without `use_adj`."""
+        and count of the unmasked layer), so the stream stays aligned with a model built without `use_adj`.
+        return_attn_coef: overrides the constructor's setting for this call (True: return (out, attn))."""
         x, a = inputs
         if self.kernel is None:
             self.build(x.shape[-1] + (0 if xb is None else xb.shape[-1]), x.device)
         h = self._graphs.handle(a, self.add_self_loops)
         xs, lead = _flatten_snapshots(x)
         xbs = None if xb is None else _flatten_snapshots(xb)[0]
+        want_attn = self.return_attn_coef if return_attn_coef is None else bool(return_attn_coef)
+        if self.attn_heads > 1 or want_attn:
+            return self._forward_heads(xs, xbs, h, lead, edge_mask, attn_dropout, want_attn)
         coef = None
         if attn_dropout is not None and self.dropout_rate:
             ones = torch.ones((xs.shape[0], h.nnz), device=xs.device, dtype=torch.float32)
@@ -486,10 +528,16 @@ class SpatialLayer(nn.Module):
     entry uds_spatial_layer_forward (concats are never materialised)."""
 
     def __init__(self, graph, embed_size, activation='relu', fx=None, fe=None, sparse_params=None, net=None,
-                 generator=None, precision='bf16x3', conv='GAT', filters=None):
+                 generator=None, precision='bf16x3', conv='GAT', filters=None, attn_heads=1):
         super().__init__()
         if conv not in ('GAT', 'GCN', 'Diffusion'):
             raise NotImplementedError('conv=%r: GAT, GCN and Diffusion are built' % (conv,))
+        self.attn_heads = int(attn_heads)
+        if self.attn_heads < 1 or int(embed_size) % (4 * self.attn_heads):
+            raise ValueError('embed_size must be a multiple of 4 * attn_heads (heads of d / H channels, float4 rows), got d=%d, H=%d'
+                             % (int(embed_size), self.attn_heads))
+        if self.attn_heads > 1 and conv != 'GAT':
+            raise ValueError('attn_heads=%d needs conv=GAT, got %r' % (self.attn_heads, conv))
         if conv != 'GAT' and filters is None:
             raise ValueError("conv=%r needs filters=(preprocess(adj), preprocess(edge_adj)) of its layer class" % (conv,))
         self.conv, self.filters = conv, filters
@@ -515,8 +563,10 @@ class SpatialLayer(nn.Module):
         self.node_edge_e = NodeEdge(abs_e, sparse=sparse_params, generator=g)           # emulator.py:228
         self.node_edge_n.precision = self.node_edge_e.precision = precision
         if conv == 'GAT':
-            self.gat_x = GATConv(self.d, activation=activation, in_channels=fx + self.h, generator=g)   # :229
-            self.gat_e = GATConv(self.d, activation=activation, in_channels=fe + self.h, generator=g)   # :230
+            # attn_heads = H > 1 (not a reference key): H heads of d / H channels, concatenated -- the same width d
+            nh = self.attn_heads
+            self.gat_x = GATConv(self.d // nh, attn_heads=nh, activation=activation, in_channels=fx + self.h, generator=g)   # :229
+            self.gat_e = GATConv(self.d // nh, attn_heads=nh, activation=activation, in_channels=fe + self.h, generator=g)   # :230
             self.gat_x.precision = self.gat_e.precision = precision
         elif conv == 'GCN':
             self.gcn_x = GCNConv(self.d, activation=activation, in_channels=fx + self.h, generator=g)
@@ -579,6 +629,9 @@ class SpatialLayer(nn.Module):
         c = lambda t: None if t is None else t.detach().cpu().clone()
         if self.conv != 'GAT':
             raise NotImplementedError('export_params covers the GAT layer')
+        if self.attn_heads > 1:
+            raise NotImplementedError('export_params covers the single-head layer (uds_spatial_params_t has one head); attn_heads=%d'
+                                      % self.attn_heads)
         p = dict(xe_k=c(self.dense_xe.kernel), xe_b=c(self.dense_xe.bias), ex_k=c(self.dense_ex.kernel),
                  ex_b=c(self.dense_ex.bias),
                  gx_k=c(self.gat_x.kernel), gx_as=c(self.gat_x.attn_kernel_self), gx_an=c(self.gat_x.attn_kernel_neighs),
@@ -592,15 +645,19 @@ class SpatialLayer(nn.Module):
                 p['ne_%s_w' % tag], p['ne_%s_b' % tag] = c(ne.weight), c(ne.bias)
         return p
 
-    def forward(self, x, e, xb=None, eb=None, adj_mask=None, attn_dropout=None):
+    def forward(self, x, e, xb=None, eb=None, adj_mask=None, attn_dropout=None, return_attn_coef=False):
         """xb / eb: 32 extra columns appended to a 64-wide x / e (`concat([x, b])`, emulator.py:260-262) -- read in place
         by the fused kernel; every other path concatenates.  adj_mask (..., nnz of the node adjacency): the per-snapshot
         adjacency of `use_adj` (emulator.py:268-271,282) -- node side through the masked aggregation kernels (under autograd
         or attention dropout: GatFn on uds_gat_aggregate_ex / uds_gat_backward_ex).
-        attn_dropout: a DropoutStream = Keras' training mode for the two GATConv layers (Spektral's attention dropout, rate 0.5)."""
-        if adj_mask is not None:
+        attn_dropout: a DropoutStream = Keras' training mode for the two GATConv layers (Spektral's attention dropout, rate 0.5).
+        A multi-head layer (attn_heads > 1) and return_attn_coef=True run the unfused chain: the fused kernels are single-head
+        and never hold the coefficients.  return_attn_coef: also return (alpha_x, alpha_e), (..., H, nnz) of the node and link
+        adjacency (GAT only)."""
+        if adj_mask is not None or self.attn_heads > 1 or return_attn_coef:
             if self.conv != 'GAT':
-                raise NotImplementedError('use_adj is built for conv=GAT (GCN / Diffusion would re-normalise the filter per snapshot)')
+                raise NotImplementedError('use_adj and return_attn_coef are built for conv=GAT (GCN / Diffusion would re-normalise '
+                                          'the filter per snapshot and have no coefficients)')
             if xb is not None:
                 x = torch.cat([x, xb], dim=-1)
             if eb is not None:
@@ -610,9 +667,14 @@ class SpatialLayer(nn.Module):
             net = self.network()
             x_e, e_x = self.dense_xe(es), self.dense_ex(xs)
             # attention-dropout draws in the order of the unmasked training branch below: gat_x, then gat_e
-            ox = self.gat_x([xs, net.adj], xb=self.node_edge_n(x_e), edge_mask=adj_mask, attn_dropout=attn_dropout)
-            oe = self.gat_e([es, net.edge_adj], xb=self.node_edge_e(e_x), attn_dropout=attn_dropout)
+            ox = self.gat_x([xs, net.adj], xb=self.node_edge_n(x_e), edge_mask=adj_mask, attn_dropout=attn_dropout,
+                            return_attn_coef=return_attn_coef)
+            oe = self.gat_e([es, net.edge_adj], xb=self.node_edge_e(e_x), attn_dropout=attn_dropout, return_attn_coef=return_attn_coef)
             self.last_path = 'unfused'
+            if return_attn_coef:
+                (ox, ax), (oe, ae) = ox, oe
+                return (ox.reshape(lead_x + ox.shape[-2:]), oe.reshape(lead_e + oe.shape[-2:]),
+                        (ax.reshape(lead_x + ax.shape[-2:]), ae.reshape(lead_e + ae.shape[-2:])))
             return ox.reshape(lead_x + ox.shape[-2:]), oe.reshape(lead_e + oe.shape[-2:])
         fused_split = (xb is not None or eb is not None) and self.conv == 'GAT' and self.precision == 'bf16x3' and \
             self.h == 32 and self.d == 64 and x.shape[-1] + (0 if xb is None else xb.shape[-1]) in (64, 96) and \
@@ -758,20 +820,30 @@ class GraphBaseBlock(nn.Module):
     normalised filter (GCN)."""
 
     def __init__(self, n_node, n_edge, filt, embed_size, n_sp_layer, activation='relu', f_in=None, generator=None, conv='GAT',
-                 precision='bf16x3'):
+                 precision='bf16x3', attn_heads=1):
         super().__init__()
         if conv not in ('GAT', 'GCN', 'Diffusion'):
             raise NotImplementedError('conv=%r: GAT, GCN and Diffusion are built' % (conv,))
         self.n_node, self.n_edge, self.filt, self.conv = int(n_node), int(n_edge), filt, conv
+        self.attn_heads = int(attn_heads)
+        if self.attn_heads < 1 or (self.attn_heads > 1 and int(embed_size) % (4 * self.attn_heads)):
+            raise ValueError('embed_size must be a multiple of 4 * attn_heads, got d=%d, H=%d' % (int(embed_size), self.attn_heads))
+        if self.attn_heads > 1 and conv != 'GAT':
+            raise ValueError('attn_heads=%d needs conv=GAT, got %r' % (self.attn_heads, conv))
         f_in = int(embed_size) if f_in is None else int(f_in)
         mk = {'GAT': GATConv, 'GCN': GCNConv, 'Diffusion': DiffusionConv}[conv]
+        if self.attn_heads > 1:      # H heads of d / H channels, concatenated: the same width d (not a reference key)
+            mk = lambda d, **kw: GATConv(int(d) // self.attn_heads, attn_heads=self.attn_heads, **kw)
         self.layers = nn.ModuleList([mk(embed_size, activation=activation, in_channels=(f_in if i == 0 else embed_size), generator=generator)
                                      for i in range(n_sp_layer)])
         for ly in self.layers:
             if conv == 'GAT':
                 ly.precision = precision
 
-    def forward(self, x, e, xb=None, eb=None, adj_mask=None, dropout=None, attn_dropout=None):
+    def forward(self, x, e, xb=None, eb=None, adj_mask=None, dropout=None, attn_dropout=None, attn_out=None):
+        """attn_out: a list that receives every layer's attention coefficients (..., H, nnz of the combined pattern), GAT only."""
+        if attn_out is not None and self.conv != 'GAT':
+            raise NotImplementedError('attention coefficients exist for conv=GAT only')
         if xb is not None:
             x = torch.cat([x, xb], dim=-1)
         if eb is not None:
@@ -782,7 +854,10 @@ class GraphBaseBlock(nn.Module):
             raise NotImplementedError('use_adj is built for conv=GAT')
         z = torch.cat([x, e], dim=-2)
         for ly in self.layers:
-            if attn_dropout is not None and self.conv == 'GAT':
+            if attn_out is not None:
+                z, alpha = ly([z, self.filt], edge_mask=adj_mask, attn_dropout=attn_dropout, return_attn_coef=True)
+                attn_out.append(alpha)
+            elif attn_dropout is not None and self.conv == 'GAT':
                 z = ly([z, self.filt], edge_mask=adj_mask, attn_dropout=attn_dropout)
             else:
                 z = ly([z, self.filt], edge_mask=adj_mask) if adj_mask is not None else ly([z, self.filt])
@@ -834,12 +909,13 @@ class SpatialBlock(nn.Module):
     """`for _ in range(n_sp_layer)` (`emulator.py:219-235`): first layer takes (fx, fe) features."""
 
     def __init__(self, graph, embed_size, n_sp_layer, activation='relu', fx=None, fe=None, sparse_params=None,
-                 generator=None, precision='bf16x3', conv='GAT', filters=None):
+                 generator=None, precision='bf16x3', conv='GAT', filters=None, attn_heads=1):
         super().__init__()
         layers = []
         for i in range(n_sp_layer):
             layers.append(SpatialLayer(graph, embed_size, activation, fx if i == 0 else None, fe if i == 0 else None,
-                                       sparse_params, generator=generator, precision=precision, conv=conv, filters=filters))
+                                       sparse_params, generator=generator, precision=precision, conv=conv, filters=filters,
+                                       attn_heads=attn_heads))
         self.layers = nn.ModuleList(layers)
         self.graph = graph
 
@@ -867,8 +943,9 @@ class SpatialBlock(nn.Module):
         replay.graph = graph
         return replay
 
-    def forward(self, x, e, xb=None, eb=None, adj_mask=None, dropout=None, attn_dropout=None):
-        """xb / eb: extra input columns of the FIRST layer (`concat([x, b])` before block 2, emulator.py:260-262);
+    def forward(self, x, e, xb=None, eb=None, adj_mask=None, dropout=None, attn_dropout=None, attn_out=None):
+        """attn_out: a list that receives one (alpha_x, alpha_e) pair per layer (the layers then run unfused), GAT only.
+        xb / eb: extra input columns of the FIRST layer (`concat([x, b])` before block 2, emulator.py:260-262);
         adj_mask: the per-snapshot node adjacency of `use_adj`, seen by every layer of the block (emulator.py:268-282);
         dropout: callable applied to x and e after every layer (`Dropout(self.dropout)`, emulator.py:234-235,287-288), training only;
         attn_dropout: DropoutStream for Spektral's attention dropout inside the GATConv layers, training only."""
@@ -876,7 +953,11 @@ class SpatialBlock(nn.Module):
         for i, layer in enumerate(self.layers):
             layer._net = net
             kw = {'attn_dropout': attn_dropout} if attn_dropout is not None and layer.conv == 'GAT' else {}
-            x, e = layer(x, e, xb if i == 0 else None, eb if i == 0 else None, adj_mask=adj_mask, **kw)
+            if attn_out is not None:
+                x, e, alphas = layer(x, e, xb if i == 0 else None, eb if i == 0 else None, adj_mask=adj_mask, return_attn_coef=True, **kw)
+                attn_out.append(alphas)
+            else:
+                x, e = layer(x, e, xb if i == 0 else None, eb if i == 0 else None, adj_mask=adj_mask, **kw)
             if dropout is not None:
                 x, e = dropout(x), dropout(e)
         return x, e

@@ -407,6 +407,27 @@ int uds_gat_backward_ex(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *
                         const float *edge_mask, const float *coef, int64_t S, int64_t d, float *alpha_ws, float *de_ws,
                         float *d_hx, float *ds_self, float *ds_nbr, uds_stream_t stream);
 
+/* MULTI-HEAD attention / aggregation: spektral GATConv with attn_heads = H, concat_heads true or false and return_attn_coef
+ * (GATConv._call_dense; the reference builds its layers with one head, emulator.py:229-230, so H > 1 is an extension of it).
+ * hx (S, n, H*C) with head-major columns (x @ kernel.reshape(F, H*C)), s_self / s_nbr (S, n, H), edge_mask (S, nnz) or NULL shared
+ * by the heads, coef (S, H, nnz) or NULL per head, both as in uds_gat_aggregate_ex.  Per head h
+ *   pre[s,i,h,:] = sum_j alpha[s,h,i,j] coef[s,h,ij] hx[s,j,h*C:(h+1)*C],  alpha = softmax_j leaky_relu_0.2(s_self[s,i,h] + s_nbr[s,j,h]).
+ * concat != 0: out (S, n, H*C) = act(pre + bias (H*C,)); concat == 0: out (S, n, C) = act(mean_h pre + bias (C,)).
+ * alpha_out (S, H, nnz) or NULL receives alpha * coef of every entry of every head, 0 for a masked one: without coef the softmax
+ * itself, which is what return_attn_coef returns.  C % 4 == 0, C <= 256.  With H == 1 and concat != 0 the result is bitwise that
+ * of uds_gat_aggregate_ex. */
+int uds_gat_aggregate_heads(const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr, const float *bias,
+                            const float *edge_mask, const float *coef, int64_t S, int64_t H, int64_t C, int concat, int act,
+                            float *out, float *alpha_out, uds_stream_t stream);
+/* Reverse mode of uds_gat_aggregate_heads (the tape through GATConv._call_dense with attn_heads = H).  grad = dL/dpre shaped like
+ * `out` (for concat == 0 every head receives grad / H), a_self / a_nbr (H*C,) head-major, alpha_ws / de_ws S*H*nnz floats each,
+ * d_hx (S, n, H*C), ds_self / ds_nbr (S, n, H).  A row pass and a column pass, no atomics: deterministic.  With H == 1 and
+ * concat != 0 the results are bitwise those of uds_gat_backward_ex. */
+int uds_gat_backward_heads(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *perm_t, const float *grad, const float *hx,
+                           const float *s_self, const float *s_nbr, const float *a_self, const float *a_nbr,
+                           const float *edge_mask, const float *coef, int64_t S, int64_t H, int64_t C, int concat,
+                           float *alpha_ws, float *de_ws, float *d_hx, float *ds_self, float *ds_nbr, uds_stream_t stream);
+
 /* out[k] = sum_s <a[s, row(k), :], b[s, col(k), :]> for every entry k of the pattern (row-major order): the gradient
  * of the per-entry values of uds_csr_spmm (a = dL/dout (S,n_rows,F), b = x (S,n_cols,F)) -- NodeEdge.weight / bias
  * on the incidence support (emulator.py:34-45). */
