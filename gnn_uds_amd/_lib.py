@@ -43,6 +43,9 @@ SYMBOLS = {
     'uds_recurrent_fused_supported': (_c_int, [_c_i64, _c_int]),
     'uds_recurrent_forward': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
     'uds_attn_sum_pool': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr]),
+    'uds_attn_sum_pool_pair': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_attn_sum_pool_backward': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr,
+                                            _c_ptr, _c_ptr]),
     'uds_dropout': (_c_int, [_c_ptr, _c_i64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _c_ptr, _c_ptr]),
     'uds_recurrent_forward_train': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
     'uds_recurrent_backward': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
@@ -435,6 +438,47 @@ def attn_sum_pool(x, attn_kernel):
     if B:
         _check(lib.uds_attn_sum_pool(_dev(x, 'x'), _dev(k, 'attn_kernel'), B, R, F, _dev(out, 'out'), _stream()), 'uds_attn_sum_pool')
     return out
+
+
+def _pool_pair_shapes(what, x, e, attn_kernel):
+    if x.dim() != 3 or (e is not None and (e.dim() != 3 or e.shape[0] != x.shape[0] or e.shape[2] != x.shape[2])) or attn_kernel.numel() != x.shape[2]:
+        raise UdsError('%s: x %r, e %r, attn_kernel %r' % (what, tuple(x.shape), None if e is None else tuple(e.shape), tuple(attn_kernel.shape)))
+    if e is not None and e.shape[1] == 0:
+        e = None
+    return x.shape[0], x.shape[1], 0 if e is None else e.shape[1], x.shape[2], e, attn_kernel.reshape(-1).contiguous()
+
+
+def attn_sum_pool_pair(x, e, attn_kernel, want_stat=False):
+    """GlobalAttnSumPool over the rows of x (B, Rx, F) followed by those of e (B, Re, F) or None, without the concatenation
+    (uds_attn_sum_pool_pair): out (B, F), bit for bit attn_sum_pool of the stacked tensor.  want_stat: also stat (B, 2), the
+    running maximum and the sum of exponentials of every sample, which attn_sum_pool_backward takes."""
+    lib = load()
+    B, Rx, Re, F, e, k = _pool_pair_shapes('attn_sum_pool_pair', x, e, attn_kernel)
+    out = torch.empty((B, F), device=x.device, dtype=torch.float32)
+    stat = torch.empty((B, 2), device=x.device, dtype=torch.float32) if want_stat else None
+    if B:
+        _check(lib.uds_attn_sum_pool_pair(_dev(x, 'x'), Rx, _dev(e, 'e', True), Re, _dev(k, 'attn_kernel'), B, F, _dev(out, 'out'),
+                                          _dev(stat, 'stat', True), _stream()), 'uds_attn_sum_pool_pair')
+    return (out, stat) if want_stat else out
+
+
+def attn_sum_pool_backward(x, e, attn_kernel, out, stat, grad, want_dx=True, want_de=True, want_dk=True, dx=None, de=None, dk=None, dk_ws=None):
+    """(dx, de, dk) of attn_sum_pool_pair from its saved `out` and `stat` for the upstream gradient grad (B, F)
+    (uds_attn_sum_pool_backward): dx like x, de like e, dk (F,); None for a gradient that is not wanted (and de when e is None).
+    dx / de / dk / dk_ws (B, F): the caller's tensors instead of new ones."""
+    lib = load()
+    B, Rx, Re, F, e, k = _pool_pair_shapes('attn_sum_pool_backward', x, e, attn_kernel)
+    if tuple(out.shape) != (B, F) or tuple(stat.shape) != (B, 2) or tuple(grad.shape) != (B, F):
+        raise UdsError('attn_sum_pool_backward: out %r, stat %r, grad %r for B=%d, F=%d' % (tuple(out.shape), tuple(stat.shape), tuple(grad.shape), B, F))
+    dx = _out(dx, (B, Rx, F), x, 'dx') if want_dx else None
+    de = _out(de, (B, Re, F), x, 'de') if want_de and e is not None else None
+    dk = _out(dk, (F,), x, 'dk') if want_dk else None
+    dk_ws = _out(dk_ws, (B, F), x, 'dk_ws') if want_dk else None
+    if dx is not None or de is not None or dk is not None:
+        _check(lib.uds_attn_sum_pool_backward(_dev(x, 'x'), Rx, _dev(e, 'e', True), Re, _dev(k, 'attn_kernel'), _dev(out, 'out'), _dev(stat, 'stat'),
+                                              _dev(grad, 'grad'), B, F, _dev(dx, 'dx', True), _dev(de, 'de', True), _dev(dk_ws, 'dk_ws', True),
+                                              _dev(dk, 'dk', True), _stream()), 'uds_attn_sum_pool_backward')
+    return dx, de, dk
 
 
 def dropout(x, rate, seed, offset):

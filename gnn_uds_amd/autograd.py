@@ -9,6 +9,7 @@ operator of the forward carries its own backward, so `loss.backward()` on an `Em
     GatFn          MixedGAT(GATConv)               uds_gat_backward (softmax / leaky-relu / aggregation), then Dense rules
     GatHeadsFn     GATConv(attn_heads=H, ..)       uds_gat_aggregate_heads / uds_gat_backward_heads, then the same Dense rules
     DiffusionFn    DiffusionConv on its support    uds_diffusion_backward: d r (transposed pattern) and d kernel, 3 launches
+    AttnSumPoolFn  GlobalAttnSumPool(x | e)        uds_attn_sum_pool_backward: d x, d e and d attn_kernel in one pass, 2 launches
     CumsumActFn    relu(cumsum_T(x) + res)         reverse cumulative sum
     FlowBalanceFn  post_proc_tf incidence sums     gather along the link end nodes
     SpatialLayerFn the fused spatial layer forward, backward through the unfused chain above (intermediates recomputed)
@@ -415,6 +416,30 @@ class DiffusionFn(torch.autograd.Function):
             gy = gy.clone()
         dr, dk = _lib.diffusion_backward(ctx.handle, a, vals, c0, r, tot, out, gy, ctx.K1, ctx.act)
         return (dr if ctx.needs_input_grad[0] else None), (dk if ctx.needs_input_grad[1] else None), None, None, None, None, None
+
+
+class AttnSumPoolFn(torch.autograd.Function):
+    """GlobalAttnSumPool over the rows of x (B, Rx, F) followed by those of e (B, Re, F) or None (uds_attn_sum_pool_pair: the stack
+    is never built).  Saves the output and the (max, sum of exponentials) pair of every sample; backward is one pass over the rows
+    (uds_attn_sum_pool_backward), the kernel's gradient summed in a fixed order: two launches, no float atomics."""
+
+    @staticmethod
+    def forward(ctx, x, e, attn_kernel):
+        x = x.contiguous()
+        e = None if e is None else e.contiguous()
+        out, stat = _lib.attn_sum_pool_pair(x, e, attn_kernel, want_stat=True)
+        ctx.save_for_backward(x, e, attn_kernel, out, stat)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, e, k, out, stat = ctx.saved_tensors
+        g = g.contiguous()
+        if g.data_ptr() % 16:                    # a view at an odd offset: the kernel reads 16-byte vectors
+            g = g.clone()
+        dx, de, dk = _lib.attn_sum_pool_backward(x, e, k, out, stat, g, want_dx=ctx.needs_input_grad[0],
+                                                 want_de=e is not None and ctx.needs_input_grad[1], want_dk=ctx.needs_input_grad[2])
+        return dx, de, (None if dk is None else dk.reshape(k.shape))
 
 
 class CumsumActFn(torch.autograd.Function):

@@ -17,6 +17,7 @@
 
 #include "kernels_dense.hpp"
 #include "kernels_sparse.hpp"
+#include "kernels_pool.hpp"
 #include "kernels_backward.hpp"
 #include "kernels_fused.hpp"
 #include "kernels_fused_ws.hpp"
@@ -741,6 +742,52 @@ int uds_attn_sum_pool(const float *x, const float *k, int64_t B, int64_t R, int6
   hipLaunchKernelGGL(uds::k_attn_sum_pool, dim3((unsigned)B), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(UDS_EHIP, "uds_attn_sum_pool: launch -> %s", hipGetErrorString(e));
+  return UDS_OK;
+}
+
+int uds_attn_sum_pool_pair(const float *x, int64_t Rx, const float *e, int64_t Re, const float *k, int64_t B, int64_t F, float *out, float *stat,
+                           uds_stream_t stream) {
+  UDS_REQUIRE(x && k && out && (e || Re == 0), "uds_attn_sum_pool_pair: NULL argument");
+  UDS_REQUIRE(B >= 0 && Rx > 0 && Re >= 0 && F >= 4 && F <= 256 && (F & (F - 1)) == 0,
+              "uds_attn_sum_pool_pair: B=%lld Rx=%lld Re=%lld F=%lld (F a power of two, 4 .. 256)", (long long)B, (long long)Rx, (long long)Re, (long long)F);
+  UDS_REQUIRE(aligned16(x) && aligned16(e) && aligned16(k) && aligned16(out), "uds_attn_sum_pool_pair: x/e/k/out must be 16-byte aligned");
+  UDS_REQUIRE(B < INT32_MAX && Rx < INT32_MAX && Re < INT32_MAX && Rx + Re < INT32_MAX, "uds_attn_sum_pool_pair: too many rows");
+  if (B == 0) return UDS_OK;
+  uds::AttnPoolPairArgs a{x, Re ? e : nullptr, k, out, stat, (int)Rx, (int)Re, (int)(F / 4)};
+  hipLaunchKernelGGL(uds::k_attn_sum_pool_pair, dim3((unsigned)B), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(UDS_EHIP, "uds_attn_sum_pool_pair: launch -> %s", hipGetErrorString(err));
+  return UDS_OK;
+}
+
+int uds_attn_sum_pool_backward(const float *x, int64_t Rx, const float *e, int64_t Re, const float *k, const float *out, const float *stat,
+                               const float *grad, int64_t B, int64_t F, float *dx, float *de, float *dk_ws, float *dk, uds_stream_t stream) {
+  UDS_REQUIRE(x && k && out && stat && grad && (e || Re == 0), "uds_attn_sum_pool_backward: NULL argument");
+  UDS_REQUIRE(B >= 0 && Rx > 0 && Re >= 0 && F >= 4 && F <= 256 && (F & (F - 1)) == 0,
+              "uds_attn_sum_pool_backward: B=%lld Rx=%lld Re=%lld F=%lld (F a power of two, 4 .. 256)", (long long)B, (long long)Rx, (long long)Re,
+              (long long)F);
+  UDS_REQUIRE(!dk || dk_ws, "uds_attn_sum_pool_backward: dk needs the workspace dk_ws (B, F)");
+  UDS_REQUIRE(aligned16(x) && aligned16(e) && aligned16(k) && aligned16(out) && aligned16(grad) && aligned16(dx) && aligned16(de) &&
+                  aligned16(dk_ws) && aligned16(dk),
+              "uds_attn_sum_pool_backward: x/e/k/out/grad/dx/de/dk_ws/dk must be 16-byte aligned");
+  UDS_REQUIRE(B < INT32_MAX && Rx < INT32_MAX && Re < INT32_MAX && Rx + Re < INT32_MAX, "uds_attn_sum_pool_backward: too many rows");
+  if (!Re) de = nullptr;
+  if (!dx && !de && !dk) return UDS_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int f4 = (int)(F / 4);
+  if (B > 0) {
+    uds::AttnPoolBwdArgs a{x, Re ? e : nullptr, k, out, stat, grad, dx, de, dk ? dk_ws : nullptr, (int)Rx, (int)Re, f4};
+    hipLaunchKernelGGL(uds::k_attn_sum_pool_bwd, dim3((unsigned)B), dim3(256), 0, st, a);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(UDS_EHIP, "uds_attn_sum_pool_backward: launch -> %s", hipGetErrorString(err));
+  }
+  if (dk) {                                           // B = 0: the sum over no samples, zeros
+    const int cw = std::min(f4, 16);
+    uds::AttnPoolDkArgs r{dk_ws, dk, (int)B, f4, cw};
+    hipLaunchKernelGGL(uds::k_attn_sum_pool_dk, dim3((unsigned)(f4 / cw)), dim3(256), 0, st, r);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return fail(UDS_EHIP, "uds_attn_sum_pool_backward: dk reduction launch -> %s", hipGetErrorString(err));
+  }
   return UDS_OK;
 }
 

@@ -308,6 +308,25 @@ int uds_cumsum_act(const float *x, const float *res, int64_t B, int64_t T, int64
  * rows (online softmax), fixed merge order: bitwise reproducible. */
 int uds_attn_sum_pool(const float *x, const float *k, int64_t B, int64_t R, int64_t F, float *out, uds_stream_t stream);
 
+/* The same pool over two row blocks, without the concatenation `ConvNet` used to build for it: per sample b the rows are those of
+ * x[b] (Rx, F) followed by those of e[b] (Re, F); e may be NULL with Re = 0.  With s_r = <row_r, k>, M = max_r s_r, L = sum_r
+ * exp(s_r - M), alpha_r = exp(s_r - M) / L: out[b, :] = sum_r alpha_r row_r, and stat (B, 2), when not NULL, receives (M, L) for
+ * the backward.  Every row is visited at the step and with the operations of uds_attn_sum_pool on the stacked tensor: `out` is
+ * bit for bit that entry's result.  F a power of two from 4 to 256, x / e / k / out 16-byte aligned. */
+int uds_attn_sum_pool_pair(const float *x, int64_t Rx, const float *e, int64_t Re, const float *k, int64_t B, int64_t F, float *out,
+                           float *stat, uds_stream_t stream);
+
+/* Reverse mode of uds_attn_sum_pool_pair from its saved out (B, F) and stat (B, 2), for the upstream gradient grad (B, F).  With
+ * g = grad[b] and t_r = <g, row_r> - <g, out[b]>:
+ *   ds_r = alpha_r t_r,   d row_r = alpha_r g + ds_r k  (dx (B, Rx, F) / de (B, Re, F)),   dk (F) = sum_b sum_r ds_r row_r
+ * alpha_r is recomputed from the row and (M, L): nothing of size (B, R) is stored.  One pass: x / e are read once, dx / de
+ * written once.  dk is summed without float atomics -- per-sample partial sums go to the caller's workspace dk_ws (B, F), a
+ * second launch adds them over b in a fixed order -- so a second call gives the same bits.  dx, de and dk may each be NULL
+ * (that gradient is not computed; dk_ws is needed only with dk).  Limits and alignment as uds_attn_sum_pool_pair. */
+int uds_attn_sum_pool_backward(const float *x, int64_t Rx, const float *e, int64_t Re, const float *k, const float *out,
+                               const float *stat, const float *grad, int64_t B, int64_t F, float *dx, float *de, float *dk_ws,
+                               float *dk, uds_stream_t stream);
+
 /* keras Dropout in training mode (the emulator's Dropout(0.2) / Dropout(self.dropout) layers,   emulator.py:199-213,234-235,
  * 287-288,314-318; `self.model(inp, training=fit)`, :411,434): out[i] = x[i] / (1 - rate) if element i is kept, else 0, for n floats;
  * out may be x.  0 <= rate < 1.  The mask is a pure function of (seed, offset + i) -- Philox4x32-10, key = seed, counter =
