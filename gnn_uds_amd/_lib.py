@@ -61,6 +61,10 @@ SYMBOLS = {
     'uds_diffusion_backward_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
     'uds_diffusion_backward': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
                                         _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_diffusion_forward_m': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
+    'uds_diffusion_backward_m_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    'uds_diffusion_backward_m': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64,
+                                          _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     'uds_halo_pack': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr]),
     'uds_halo_unpack': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr]),
     'uds_halo_pack_all': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_i64,
@@ -649,6 +653,54 @@ def diffusion_backward(csr, a, vals, c0, r, tot, y, gy, K1, act='tanh'):
     _check(lib.uds_diffusion_backward(csr.ptr, ht.ptr, _dev_i32(perm, 'perm_t'), _dev(a, 'a'), _dev(vals, 'vals'), _dev(c0, 'c0'),
                                       _dev(r, 'r'), _dev(tot, 'tot'), _dev(y, 'y'), _dev(gy, 'gy'), S, C, K1, ACT[act], ws.data_ptr(),
                                       _dev(dr, 'dr'), _dev(dtheta, 'dtheta'), _stream()), 'uds_diffusion_backward')
+    return dr, dtheta
+
+
+def diffusion_forward_m(csr, a, theta, r, tot, act='tanh', out=None):
+    """diffusion_forward without the (nnz, C) table: out[s, i, q] = act(sum_m theta[q][K - m] M_m[s, i]), M_0 = tot[s],
+    M_m = sum_p a[p]^m r[s, col[p]] over row i; `a` (nnz,) the filter's support values, theta (C, K1) the layer's kernel
+    (uds_diffusion_forward_m).  out: a contiguous (S, n_rows, C) tensor to write into."""
+    lib = load()
+    S, (C, K1) = r.shape[0], theta.shape
+    if tuple(a.shape) != (csr.nnz,) or tuple(r.shape) != (S, csr.n_cols) or tuple(tot.shape) != (S,):
+        raise UdsError('diffusion_forward_m: a %r theta %r r %r tot %r for a %d x %d pattern with %d entries'
+                       % (tuple(a.shape), tuple(theta.shape), tuple(r.shape), tuple(tot.shape), csr.n_rows, csr.n_cols, csr.nnz))
+    if out is None:
+        out = torch.empty((S, csr.n_rows, C), device=r.device, dtype=torch.float32)
+    elif tuple(out.shape) != (S, csr.n_rows, C):
+        raise UdsError('diffusion_forward_m: out %r, expected %r' % (tuple(out.shape), (S, csr.n_rows, C)))
+    _check(lib.uds_diffusion_forward_m(csr.ptr, _dev(a, 'a'), _dev(theta, 'theta'), _dev(r, 'r'), _dev(tot, 'tot'), S, C, K1, ACT[act],
+                                       _dev(out, 'out'), _stream()), 'uds_diffusion_forward_m')
+    return out
+
+
+def diffusion_backward_m(csr, a, theta, r, tot, y, gy, act='tanh', out=None, workspace=None):
+    """(dr (S, n_cols), dtheta (C, K1)) of diffusion_forward_m's out = y given dL/dout = gy (uds_diffusion_backward_m).
+    out: (dr, dtheta) tensors to write into; workspace: at least uds_diffusion_backward_m_workspace_floats floats."""
+    lib = load()
+    S, (C, K1) = r.shape[0], theta.shape
+    if (tuple(a.shape) != (csr.nnz,) or tuple(r.shape) != (S, csr.n_cols) or tuple(tot.shape) != (S,)
+            or tuple(y.shape) != (S, csr.n_rows, C) or tuple(gy.shape) != (S, csr.n_rows, C)):
+        raise UdsError('diffusion_backward_m: a %r theta %r r %r tot %r y %r gy %r for a %d x %d pattern with %d entries'
+                       % (tuple(a.shape), tuple(theta.shape), tuple(r.shape), tuple(tot.shape), tuple(y.shape), tuple(gy.shape),
+                          csr.n_rows, csr.n_cols, csr.nnz))
+    nws = lib.uds_diffusion_backward_m_workspace_floats(csr.n_rows, S, C, K1)
+    if nws < 0:
+        raise UdsError('diffusion_backward_m: C=%d K1=%d not taken (C %% 4 == 0, C <= 256, 1 <= K1 <= 16)' % (C, K1))
+    ht, perm = csr.transposed(r.device)
+    ws = torch.empty(max(int(nws), 4), device=r.device, dtype=torch.float32) if workspace is None else workspace
+    if ws.numel() < nws:
+        raise UdsError('diffusion_backward_m: workspace of %d floats, needs %d' % (ws.numel(), nws))
+    if out is None:
+        dr = torch.empty((S, csr.n_cols), device=r.device, dtype=torch.float32)
+        dtheta = torch.empty((C, K1), device=r.device, dtype=torch.float32)
+    else:
+        dr, dtheta = out
+        if tuple(dr.shape) != (S, csr.n_cols) or tuple(dtheta.shape) != (C, K1):
+            raise UdsError('diffusion_backward_m: out %r / %r, expected %r / %r' % (tuple(dr.shape), tuple(dtheta.shape), (S, csr.n_cols), (C, K1)))
+    _check(lib.uds_diffusion_backward_m(csr.ptr, ht.ptr, _dev_i32(perm, 'perm_t'), _dev(a, 'a'), _dev(theta, 'theta'), _dev(r, 'r'),
+                                        _dev(tot, 'tot'), _dev(y, 'y'), _dev(gy, 'gy'), S, C, K1, ACT[act], ws.data_ptr(),
+                                        _dev(dr, 'dr'), _dev(dtheta, 'dtheta'), _stream()), 'uds_diffusion_backward_m')
     return dr, dtheta
 
 

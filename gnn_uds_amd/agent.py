@@ -17,7 +17,7 @@ from torch import nn
 
 from . import _lib
 from . import autograd as _ag
-from .graph import DrainageGraph, csr_from_dense
+from .graph import DrainageGraph, csr_from_dense, edge_based_adj_csr, node_based_adj_csr
 from .layers import Dense, DiffusionConv, GCNConv, GraphBaseBlock, SpatialBlock, _glorot_uniform, _param
 
 
@@ -72,14 +72,25 @@ class ConvNet(nn.Module):
         self.embed_x = Dense(d, a, in_features=self.n_in + self.b_in, generator=gen)       # agent.py:78
         self.embed_e = Dense(d, a, in_features=self.e_in, generator=gen)                   # agent.py:79
         graph = g('graph')
-        if self.graph_base:
+        if self.graph_base and isinstance(graph, DrainageGraph):
+            # `args.graph`: the combined (N+E) x (N+E) matrix in CSR from the link list (never dense); GCN / Diffusion normalise it there
+            build = node_based_adj_csr if self.graph_base == 1 else edge_based_adj_csr
+            filt = build(graph.edges, graph.n_node, bool(g('directed', False)), int(g('order', 1)), g('length', 0), g('lengths', None))
+            if kind != 'GAT':
+                filt = pre(filt)                    # a pattern without values counts as ones
+            self.block = GraphBaseBlock(self.n_node, self.n_edge, filt, d, self.n_sp_layer, a, generator=gen, conv=kind, precision=precision,
+                                        attn_heads=self.attn_heads)
+        elif self.graph_base:
             adj = np.asarray(g('adj'))
             filt = csr_from_dense((adj > 0).astype(int), add_self_loops=True) if kind == 'GAT' else pre(adj)
             self.block = GraphBaseBlock(self.n_node, self.n_edge, filt, d, self.n_sp_layer, a, generator=gen, conv=kind, precision=precision,
                                         attn_heads=self.attn_heads)
         else:
             if isinstance(graph, DrainageGraph):
-                filters = (None, None)
+                if kind != 'GAT' and (graph.raw_adj is None or graph.raw_edge_adj is None):
+                    raise ValueError('conv=%r from args.graph needs the raw adjacency matrices (graph.raw_adj / raw_edge_adj): build '
+                                     'the graph with DrainageGraph.from_edges or DrainageGraph.from_dense' % (conv,))
+                filters = (None, None) if kind == 'GAT' else (pre(graph.raw_adj), pre(graph.raw_edge_adj))
             else:
                 adj, edge_adj = np.asarray(g('adj', np.eye(self.n_node))), np.asarray(g('edge_adj', np.eye(self.n_edge)))
                 graph = DrainageGraph.from_dense(adj, edge_adj, np.asarray(g('node_edge'), dtype=np.float64), g('edges'))

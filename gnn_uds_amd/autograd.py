@@ -9,6 +9,7 @@ operator of the forward carries its own backward, so `loss.backward()` on an `Em
     GatFn          MixedGAT(GATConv)               uds_gat_backward (softmax / leaky-relu / aggregation), then Dense rules
     GatHeadsFn     GATConv(attn_heads=H, ..)       uds_gat_aggregate_heads / uds_gat_backward_heads, then the same Dense rules
     DiffusionFn    DiffusionConv on its support    uds_diffusion_backward: d r (transposed pattern) and d kernel, 3 launches
+    DiffusionMomentsFn  the same, no (nnz, C) table    uds_diffusion_backward_m: d kernel by the same launches, d r from row sums G_m
     AttnSumPoolFn  GlobalAttnSumPool(x | e)        uds_attn_sum_pool_backward: d x, d e and d attn_kernel in one pass, 2 launches
     CumsumActFn    relu(cumsum_T(x) + res)         reverse cumulative sum
     FlowBalanceFn  post_proc_tf incidence sums     gather along the link end nodes
@@ -416,6 +417,31 @@ class DiffusionFn(torch.autograd.Function):
             gy = gy.clone()
         dr, dk = _lib.diffusion_backward(ctx.handle, a, vals, c0, r, tot, out, gy, ctx.K1, ctx.act)
         return (dr if ctx.needs_input_grad[0] else None), (dk if ctx.needs_input_grad[1] else None), None, None, None, None, None
+
+
+class DiffusionMomentsFn(torch.autograd.Function):
+    """DiffusionFn without the (nnz, C) table of polynomial values: the kernels expand the polynomial per row from `kernel`
+    (C, K1) and the filter's support values `a` (uds_diffusion_forward_m / uds_diffusion_backward_m).  What a model built from
+    a CSR graph runs (layers.DiffusionConv(moments=True))."""
+
+    @staticmethod
+    def forward(ctx, r, kernel, handle, a, act):
+        r = r.contiguous()
+        tot = r.sum(dim=-1).contiguous()
+        theta = kernel.detach().contiguous()
+        out = _lib.diffusion_forward_m(handle, a, theta, r, tot, act)
+        ctx.save_for_backward(r, tot, a, theta, out)
+        ctx.handle, ctx.act = handle, act
+        return out
+
+    @staticmethod
+    def backward(ctx, gy):
+        r, tot, a, theta, out = ctx.saved_tensors
+        gy = gy.contiguous()
+        if gy.data_ptr() % 16:                   # a view at an odd offset: the kernel reads 16-byte vectors
+            gy = gy.clone()
+        dr, dk = _lib.diffusion_backward_m(ctx.handle, a, theta, r, tot, out, gy, ctx.act)
+        return (dr if ctx.needs_input_grad[0] else None), (dk if ctx.needs_input_grad[1] else None), None, None, None
 
 
 class AttnSumPoolFn(torch.autograd.Function):

@@ -1098,6 +1098,7 @@ struct DiffusionBwdArgs {
   const float *a, *vals, *c0, *r, *tot, *y, *gy;
   float *gz, *pth, *pg, *g0, *dr, *dtheta;
   int n_rows, n_cols, S, c4, lr, K1, act, gx, sy;
+  int c0s = 1;      // stride of c0 in floats: 1 = a (C,) vector, K1 = the last column of theta (C, K1) (the table-free entry)
 };
 
 struct DiffusionBwdPlan {
@@ -1138,7 +1139,11 @@ __global__ __launch_bounds__(256) void k_diffusion_bwd_rows(DiffusionBwdArgs a) 
   const int tid = threadIdx.x, q = tid % a.lr, rpb = 256 / a.lr, wave = tid >> 6, wl = tid & 63;
   const bool qok = q < a.c4;
   const int s0 = blockIdx.y * DIFF_SCH;
-  const float4 c = qok ? reinterpret_cast<const float4 *>(a.c0)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (qok) {
+    if (a.c0s == 1) c = reinterpret_cast<const float4 *>(a.c0)[q];
+    else c = make_float4(a.c0[(4 * q) * a.c0s], a.c0[(4 * q + 1) * a.c0s], a.c0[(4 * q + 2) * a.c0s], a.c0[(4 * q + 3) * a.c0s]);
+  }
   float4 acc[KMAX];
 #pragma unroll
   for (int m = 0; m < KMAX; ++m) acc[m] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1274,6 +1279,166 @@ inline hipError_t launch_diffusion_backward(const DiffusionBwdArgs &a, hipStream
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const int rpb = 256 / a.lr;
   hipLaunchKernelGGL(k_diffusion_bwd_input, dim3((unsigned)((a.n_cols + rpb - 1) / rpb), (unsigned)a.S), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// DiffusionConv without the (nnz, C) table: the polynomial expanded per row.  With K = K1 - 1, M_0[s, i] = tot[s] and
+// M_m[s, i] = sum_{p in row i} a_p^m r[s, col p]:
+//     out[s, i, q] = act( sum_{m=0..K} theta[q][K-m] M_m[s, i] )
+// A row belongs to a lane group of lr lanes (lr = c4 rounded up to a power of two, 256 / lr rows per block).  With lr >= K lane
+// l < K walks the row for moment l + 1; with fewer lanes than moments every lane walks the row once, forms every power by the
+// running product and sums the moments l + 1, l + 1 + lr, .. it owns.  Either way a moment is the sum over the row's entries in
+// row order of r * a * a * .. (the same bits), left in LDS; after the barrier lane q reads the K moments (one LDS broadcast each)
+// and the float4 of theta it needs (theta transposed to [m][C] in LDS: consecutive lanes, consecutive banks), sums m upwards and
+// stores its float4 of the output row.  A block keeps theta for all the row tiles it visits (grid-stride), the moment buffer is
+// double-buffered so one barrier per tile is enough.  Reads per snapshot: a, col, r -- no table.
+struct DiffusionMArgs {
+  const int32_t *rowptr, *col;
+  const float *a, *theta, *r, *tot;
+  float *out;
+  int n_rows, n_cols, c4, lr, K1, act, ntiles;
+};
+
+inline size_t diffusion_m_lds_bytes(int c4, int lr, int K1) {
+  return sizeof(float) * ((size_t)K1 * c4 * 4 + 2 * (size_t)(256 / lr) * (K1 > 1 ? K1 - 1 : 1));
+}
+
+__device__ __forceinline__ void diffusion_m_load_theta(float *s_th, const float *theta, int C, int K1, int tid) {
+  for (int idx = tid; idx < C * K1; idx += 256) s_th[(K1 - 1 - idx % K1) * C + idx / K1] = theta[idx];     // s_th[m][c] = theta[c][K - m]
+}
+
+__global__ __launch_bounds__(256) void k_diffusion_m(DiffusionMArgs a) {
+  extern __shared__ float4 s_dyn4[];
+  float *s_th = reinterpret_cast<float *>(s_dyn4);
+  const int tid = threadIdx.x, C = a.c4 * 4, K = a.K1 - 1, rpb = 256 / a.lr, q = tid % a.lr, slot = tid / a.lr, s = blockIdx.y;
+  float *s_M = s_th + a.K1 * C;                         // [2][rpb][K]
+  diffusion_m_load_theta(s_th, a.theta, C, a.K1, tid);
+  const float t = a.tot[s];
+  const float *r = a.r + (int64_t)s * a.n_cols;
+  const float4 *th4 = reinterpret_cast<const float4 *>(s_th) + q;
+  int buf = 0;
+  for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x, buf ^= 1) {      // uniform trip count: the barrier is safe
+    const int i = tile * rpb + slot;
+    float *M = s_M + (buf * rpb + slot) * K;
+    if (i < a.n_rows) {
+      const int beg = a.rowptr[i], end = a.rowptr[i + 1];
+      if (a.lr >= K) {                   // one moment per lane (lanes K.. idle until the barrier): m multiplies per entry, sum in a register
+        const int m = q + 1;
+        if (m <= K) {
+          float acc = 0.f;
+          for (int p = beg; p < end; ++p) {
+            const float av = a.a[p];
+            float pw = r[a.col[p]];
+            for (int j = 0; j < m; ++j) pw *= av;
+            acc += pw;
+          }
+          M[m - 1] = acc;
+        }
+      } else {                           // fewer lanes than moments (C <= 32): ONE walk, every power once, lane q sums moments q + 1, q + 1 + lr, .. in LDS
+        for (int m = q; m < K; m += a.lr) M[m] = 0.f;
+        for (int p = beg; p < end; ++p) {
+          const float av = a.a[p];
+          float pw = r[a.col[p]];
+          for (int j = 0; j < K; ++j) {
+            pw *= av;
+            if ((j & (a.lr - 1)) == q) M[j] += pw;       // its own slots only: no other lane touches them before the barrier
+          }
+        }
+      }
+    }
+    __syncthreads();       // moments of this tile (and, first time round, theta) are in LDS
+    if (i < a.n_rows && q < a.c4) {
+      float4 th = th4[0];
+      float4 o = make_float4(th.x * t, th.y * t, th.z * t, th.w * t);
+      for (int m = 1; m <= K; ++m) {
+        const float Mm = M[m - 1];
+        th = th4[m * a.c4];
+        o.x = fmaf(th.x, Mm, o.x), o.y = fmaf(th.y, Mm, o.y), o.z = fmaf(th.z, Mm, o.z), o.w = fmaf(th.w, Mm, o.w);
+      }
+      o.x = apply_act(o.x, a.act), o.y = apply_act(o.y, a.act), o.z = apply_act(o.z, a.act), o.w = apply_act(o.w, a.act);
+      reinterpret_cast<float4 *>(a.out)[((int64_t)s * a.n_rows + i) * a.c4 + q] = o;
+    }
+  }
+}
+
+inline hipError_t launch_diffusion_m(DiffusionMArgs a, int S, hipStream_t st) {
+  const int rpb = 256 / a.lr;
+  a.ntiles = (a.n_rows + rpb - 1) / rpb;
+  const int cap = 2048 / S > 256 ? 2048 / S : 256;      // ~2048 blocks or more: a block amortises its theta load over its tiles
+  const int gx = a.ntiles < cap ? a.ntiles : cap;
+  hipLaunchKernelGGL(k_diffusion_m, dim3((unsigned)gx, (unsigned)S), dim3(256), diffusion_m_lds_bytes(a.c4, a.lr, a.K1), st, a);
+  return hipGetLastError();
+}
+
+// Reverse of k_diffusion_m.  dtheta needs the moments only: k_diffusion_bwd_rows / k_diffusion_bwd_reduce as they are (c0 read
+// from theta's last column), which also leave gz and g0[s] = sum_{i, q} theta[q][K] gz[s, i, q] = sum_i G_0[s, i].  The dr pass
+// replaces the table by
+//     G_m[s, i] = sum_q theta[q][K-m] gz[s, i, q]      (m = 1..K)       k_diffusion_bwd_gm: lane group per row, fixed xor tree
+//     dr[s, j]  = g0[s] + sum_{p : col p = j} sum_{m=1..K} a_p^m G_m[s, row p]      k_diffusion_bwd_input_m: thread per (j, s)
+// Every value has one writer and a fixed order: no atomics, bitwise repeatable.
+struct DiffusionBwdMArgs {
+  DiffusionBwdArgs b;
+  const float *theta;
+  float *G;               // (S, n_rows, K)
+};
+
+__global__ __launch_bounds__(256) void k_diffusion_bwd_gm(DiffusionBwdMArgs m) {
+  extern __shared__ float4 s_dyn4[];
+  float *s_th = reinterpret_cast<float *>(s_dyn4);
+  const DiffusionBwdArgs &a = m.b;
+  const int tid = threadIdx.x, C = a.c4 * 4, K = a.K1 - 1, rpb = 256 / a.lr, q = tid % a.lr, slot = tid / a.lr, s = blockIdx.y;
+  diffusion_m_load_theta(s_th, m.theta, C, a.K1, tid);
+  __syncthreads();
+  const bool qok = q < a.c4;
+  const float4 *th4 = reinterpret_cast<const float4 *>(s_th) + (qok ? q : 0);
+  const int ntiles = (a.n_rows + rpb - 1) / rpb;
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {      // uniform trip count: every lane reaches the shuffles
+    const int i = tile * rpb + slot;
+    const bool live = i < a.n_rows;
+    const float4 z = live && qok ? reinterpret_cast<const float4 *>(a.gz)[((int64_t)s * a.n_rows + i) * a.c4 + q] : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int mm = 1; mm <= K; ++mm) {
+      const float4 th = th4[mm * a.c4];
+      float v = fmaf(th.w, z.w, fmaf(th.z, z.z, fmaf(th.y, z.y, th.x * z.x)));
+      for (int o = a.lr >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
+      if (live && q == 0) m.G[((int64_t)s * a.n_rows + i) * K + (mm - 1)] = v;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void k_diffusion_bwd_input_m(DiffusionBwdMArgs m) {
+  const DiffusionBwdArgs &a = m.b;
+  const int j = blockIdx.x * 256 + threadIdx.x, s = blockIdx.y, K = a.K1 - 1;
+  if (j >= a.n_cols) return;
+  const float *G = m.G + (int64_t)s * a.n_rows * K;
+  float acc = 0.f;
+  for (int p = a.t_rowptr[j]; p < a.t_rowptr[j + 1]; ++p) {
+    const float av = a.a[a.perm_t[p]];
+    const float *g = G + (int64_t)a.t_col[p] * K;
+    float pw = 1.f;
+    for (int mm = 0; mm < K; ++mm) {
+      pw *= av;
+      acc = fmaf(pw, g[mm], acc);
+    }
+  }
+  a.dr[(int64_t)s * a.n_cols + j] = a.g0[s] + acc;
+}
+
+inline hipError_t launch_diffusion_backward_m(const DiffusionBwdMArgs &m, hipStream_t st) {
+  const DiffusionBwdArgs &a = m.b;
+  if (a.K1 <= 8) hipLaunchKernelGGL(k_diffusion_bwd_rows<8>, dim3((unsigned)a.gx, (unsigned)a.sy), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(k_diffusion_bwd_rows<DIFF_KMAX>, dim3((unsigned)a.gx, (unsigned)a.sy), dim3(256), 0, st, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_diffusion_bwd_reduce, dim3((unsigned)(a.K1 * a.c4 * 4 + a.S)), dim3(256), 0, st, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if (a.K1 > 1 && a.n_rows > 0) {
+    const int rpb = 256 / a.lr, ntiles = (a.n_rows + rpb - 1) / rpb;
+    const int cap = 2048 / a.S > 256 ? 2048 / a.S : 256;
+    hipLaunchKernelGGL(k_diffusion_bwd_gm, dim3((unsigned)(ntiles < cap ? ntiles : cap), (unsigned)a.S), dim3(256),
+                       sizeof(float) * (size_t)a.K1 * a.c4 * 4, st, m);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(k_diffusion_bwd_input_m, dim3((unsigned)((a.n_cols + 255) / 256), (unsigned)a.S), dim3(256), 0, st, m);
   return hipGetLastError();
 }
 

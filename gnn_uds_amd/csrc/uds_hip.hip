@@ -866,6 +866,61 @@ int uds_diffusion_backward(const uds_csr_t *csr, const uds_csr_t *csr_t, const i
   return UDS_OK;
 }
 
+int uds_diffusion_forward_m(const uds_csr_t *csr, const float *a, const float *theta, const float *r, const float *tot, int64_t S, int64_t C,
+                            int64_t K1, int act, float *out, uds_stream_t stream) {
+  UDS_REQUIRE(csr && theta && r && tot && out && (csr->nnz == 0 || a), "uds_diffusion_forward_m: NULL argument");
+  UDS_REQUIRE(S >= 0 && S <= 65535 && C > 0 && C % 4 == 0 && C <= 256 && K1 >= 1 && K1 <= uds::DIFF_KMAX,
+              "uds_diffusion_forward_m: S=%lld C=%lld K1=%lld (needs S <= 65535, C %% 4 == 0, C <= 256, 1 <= K1 <= %d)", (long long)S,
+              (long long)C, (long long)K1, uds::DIFF_KMAX);
+  UDS_REQUIRE(act >= 0 && act <= 4, "uds_diffusion_forward_m: unknown activation %d", act);
+  UDS_REQUIRE(aligned16(theta) && aligned16(out), "uds_diffusion_forward_m: theta / out must be 16-byte aligned");
+  if (S == 0 || csr->n_rows == 0) return UDS_OK;
+  int lr = 1;
+  while (lr < C / 4) lr <<= 1;
+  uds::DiffusionMArgs args{csr->d_rowptr, csr->d_col, a, theta, r, tot, out, (int)csr->n_rows, (int)csr->n_cols, (int)(C / 4), lr, (int)K1, act, 0};
+  hipError_t e = uds::launch_diffusion_m(args, (int)S, static_cast<hipStream_t>(stream));
+  if (e != hipSuccess) return fail(UDS_EHIP, "uds_diffusion_forward_m: launch -> %s", hipGetErrorString(e));
+  return UDS_OK;
+}
+
+static int64_t up4f(int64_t f) { return (f + 3) & ~int64_t(3); }
+
+int64_t uds_diffusion_backward_m_workspace_floats(int64_t n_rows, int64_t S, int64_t C, int64_t K1) {
+  if (n_rows < 0 || S < 0 || C <= 0 || C % 4 || C > 256 || K1 < 1 || K1 > uds::DIFF_KMAX) return -1;
+  return uds::diffusion_bwd_plan(n_rows, S, C, K1).total + up4f(S * n_rows * (K1 - 1));       // the table entry's carve, then G
+}
+
+int uds_diffusion_backward_m(const uds_csr_t *csr, const uds_csr_t *csr_t, const int32_t *perm_t, const float *a, const float *theta,
+                             const float *r, const float *tot, const float *y, const float *gy, int64_t S, int64_t C, int64_t K1, int act,
+                             float *workspace, float *dr, float *dtheta, uds_stream_t stream) {
+  UDS_REQUIRE(csr && csr_t && theta && dtheta, "uds_diffusion_backward_m: NULL argument");
+  UDS_REQUIRE(S >= 0 && S <= 65535 && C > 0 && C % 4 == 0 && C <= 256 && K1 >= 1 && K1 <= uds::DIFF_KMAX,
+              "uds_diffusion_backward_m: S=%lld C=%lld K1=%lld (needs S <= 65535, C %% 4 == 0, C <= 256, 1 <= K1 <= %d)", (long long)S,
+              (long long)C, (long long)K1, uds::DIFF_KMAX);
+  UDS_REQUIRE(act >= 0 && act <= 4, "uds_diffusion_backward_m: unknown activation %d", act);
+  UDS_REQUIRE(csr_t->n_rows == csr->n_cols && csr_t->n_cols == csr->n_rows && csr_t->nnz == csr->nnz,
+              "uds_diffusion_backward_m: csr_t (%lld x %lld, %lld entries) is not the transpose of a %lld x %lld pattern with %lld entries",
+              (long long)csr_t->n_rows, (long long)csr_t->n_cols, (long long)csr_t->nnz, (long long)csr->n_rows, (long long)csr->n_cols,
+              (long long)csr->nnz);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (S == 0 || csr->n_cols == 0) {           // no dr to write; dtheta = 0 (no snapshot, or no column to sum over)
+    UDS_HIP_TRY(hipMemsetAsync(dtheta, 0, sizeof(float) * C * K1, st));
+    return UDS_OK;
+  }
+  UDS_REQUIRE(r && tot && workspace && dr && (csr->nnz == 0 || (perm_t && a)) && (csr->n_rows == 0 || (y && gy)),
+              "uds_diffusion_backward_m: NULL argument");
+  UDS_REQUIRE(aligned16(theta) && aligned16(y) && aligned16(gy) && aligned16(workspace),
+              "uds_diffusion_backward_m: theta / y / gy / workspace must be 16-byte aligned");
+  const uds::DiffusionBwdPlan p = uds::diffusion_bwd_plan(csr->n_rows, S, C, K1);
+  uds::DiffusionBwdMArgs args{{csr->d_rowptr, csr->d_col, csr_t->d_rowptr, csr_t->d_col, perm_t, a, nullptr, theta + (K1 - 1), r, tot, y, gy,
+                               workspace, workspace + p.off_pth, workspace + p.off_pg, workspace + p.off_g0, dr, dtheta,
+                               (int)csr->n_rows, (int)csr->n_cols, (int)S, (int)(C / 4), p.lr, (int)K1, act, p.gx, p.sy, (int)K1},
+                              theta, workspace + p.total};
+  hipError_t e = uds::launch_diffusion_backward_m(args, st);
+  if (e != hipSuccess) return fail(UDS_EHIP, "uds_diffusion_backward_m: launch -> %s", hipGetErrorString(e));
+  return UDS_OK;
+}
+
 static int halo_rows(const char *what, bool pack, float *x, int64_t n_x, float *e, int64_t n_e, int64_t S, int64_t F, const int32_t *idx_x,
                      int64_t nx, const int32_t *idx_e, int64_t ne, float *buf, uds_stream_t stream) {
   UDS_REQUIRE(S >= 0 && nx >= 0 && ne >= 0 && n_x >= 0 && n_e >= 0 && F > 0 && F % 4 == 0, "%s: bad sizes (S=%lld nx=%lld ne=%lld F=%lld)", what,

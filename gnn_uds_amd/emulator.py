@@ -32,7 +32,7 @@ from . import _lib
 from .graph import DrainageGraph, csr_from_dense
 from . import autograd as _ag
 from .graph import csr_from_dense, edge_based_adj_csr, node_based_adj_csr
-from .layers import Dense, Dropout, DropoutStream, GraphBaseBlock, SpatialBlock, _glorot_uniform, _packed_kernel, _param
+from .layers import Dense, DiffusionConv, Dropout, DropoutStream, GCNConv, GraphBaseBlock, SpatialBlock, _glorot_uniform, _packed_kernel, _param
 
 
 class Conv1D(nn.Module):
@@ -313,22 +313,27 @@ class Emulator(nn.Module):
                 if adj.shape != (self.n_node + self.n_edge,) * 2:
                     raise ValueError('graph_base needs the combined (N+E, N+E) adjacency, got %r' % (adj.shape,))
                 if self.conv_kind != 'GAT':
-                    from .layers import DiffusionConv, GCNConv
                     self._base_filter = (GCNConv if self.conv_kind == 'GCN' else DiffusionConv).preprocess(adj)
                 else:
                     self._base_filter = csr_from_dense((adj > 0).astype(int), add_self_loops=True)
             else:
-                if self.conv_kind != 'GAT':
-                    raise NotImplementedError('graph_base with a CSR graph is built for conv=GAT')
                 build = node_based_adj_csr if self.graph_base == 1 else edge_based_adj_csr
                 self._base_filter = build(self.edges, self.n_node, bool(g('directed', False)), int(g('order', 1)), g('length', 0), g('lengths', None))
+                if self.conv_kind != 'GAT':       # the builders carry their values (none = ones, or the Gaussian kernel): normalised on the CSR
+                    self._base_filter = (GCNConv if self.conv_kind == 'GCN' else DiffusionConv).preprocess(self._base_filter)
             self.filter = self.edge_filter = None
         elif isinstance(graph, DrainageGraph):
             # large networks: `args.graph` (CSR, e.g. DrainageGraph.from_edges) instead of the dense (N,N) / (E,E) / (N,E)
             # matrices of `args.adj`, `args.edge_adj`, `args.node_edge`, which cannot exist at N >= 50k
-            if self.conv_kind != 'GAT':
-                raise NotImplementedError('args.graph (CSR input) is built for conv=GAT')
             self.graph, self.filter, self.edge_filter, node_edge = graph, None, None, None
+            if self.conv_kind != 'GAT':
+                # GCN / Diffusion normalise the RAW matrices (values kept, no forced diagonal) on their CSR pattern; the Diffusion
+                # layers then run their table-free form (layers.DiffusionConv)
+                if graph.raw_adj is None or graph.raw_edge_adj is None:
+                    raise ValueError('conv=%r from args.graph needs the raw adjacency matrices (graph.raw_adj / raw_edge_adj): build '
+                                     'the graph with DrainageGraph.from_edges or DrainageGraph.from_dense' % (conv,))
+                pre = (GCNConv if self.conv_kind == 'GCN' else DiffusionConv).preprocess
+                self.filter, self.edge_filter = pre(graph.raw_adj), pre(graph.raw_edge_adj)
         else:
             adj = np.asarray(g('adj', np.eye(self.n_node)))
             edge_adj = np.asarray(g('edge_adj', np.eye(self.n_edge)))
@@ -342,7 +347,6 @@ class Emulator(nn.Module):
                 rows = np.repeat(np.arange(ga.n_rows), np.diff(ga.rowptr))
                 self._adj_raw = np.asarray(adj, dtype=np.float64)[rows, np.asarray(ga.col, dtype=np.int64)]
             if self.conv_kind != 'GAT':
-                from .layers import DiffusionConv, GCNConv
                 pre = (GCNConv if self.conv_kind == 'GCN' else DiffusionConv).preprocess
                 self.filter, self.edge_filter = pre(adj), pre(edge_adj)                                   # emulator.py:133-134,137-138
             else:

@@ -450,7 +450,10 @@ class DrainageGraph:
     """Everything the spatial layers need about one network, in CSR.
 
     adj / edge_adj carry the forced self loops (GAT's set_diag); inc_n is (N x E) and
-    inc_e its transpose, values are the signed incidence (the layers use |value|)."""
+    inc_e its transpose, values are the signed incidence (the layers use |value|).
+    raw_adj / raw_edge_adj are what `get_adj` / `get_edge_adj` return, with values (ones for `length = 0`, the Gaussian
+    kernel for `length > 0`): what GCNConv.preprocess / DiffusionConv.preprocess normalise.  `from_edges` and `from_dense`
+    fill them; None on a graph built field by field."""
     n_node: int
     n_edge: int
     edges: np.ndarray
@@ -459,6 +462,8 @@ class DrainageGraph:
     inc_n: CSR
     inc_e: CSR
     meta: dict = field(default_factory=dict)
+    raw_adj: Optional[CSR] = None
+    raw_edge_adj: Optional[CSR] = None
 
     def replicated(self, k):
         """k disjoint copies of this network as ONE network (block-diagonal patterns: node c*N + n, link c*E + e of copy c).
@@ -474,7 +479,8 @@ class DrainageGraph:
             return CSR(rowptr.astype(I32), col.astype(I32), k * c.n_rows, k * c.n_cols, val)
         edges = np.concatenate([np.asarray(self.edges, dtype=np.int64) + i * self.n_node for i in range(k)]).astype(I32)
         return DrainageGraph(k * self.n_node, k * self.n_edge, edges, rep(self.adj), rep(self.edge_adj), rep(self.inc_n), rep(self.inc_e),
-                             dict(self.meta, copies=k))
+                             dict(self.meta, copies=k), None if self.raw_adj is None else rep(self.raw_adj),
+                             None if self.raw_edge_adj is None else rep(self.raw_edge_adj))
 
     @classmethod
     def from_edges(cls, edges, n_node=None, directed=False, order=1, length=0, lengths=None):
@@ -485,13 +491,14 @@ class DrainageGraph:
             n_node = int(edges.max()) + 1
         adj = adjacency_csr(edges, n_node, directed, order, length, lengths)
         eadj = edge_adjacency_csr(edges, directed, order, length, lengths)
+        raw = [CSR(c.rowptr, c.col, c.n_rows, c.n_cols, np.ones(c.nnz) if c.val is None else c.val) for c in (adj, eadj)]
         me_n, me_e = np.arange(n_node, dtype=np.int64), np.arange(edges.shape[0], dtype=np.int64)
         adj = _csr_from_pairs(np.concatenate([adj.rows(), me_n]), np.concatenate([adj.col.astype(np.int64), me_n]), n_node, n_node)
         eadj = _csr_from_pairs(np.concatenate([eadj.rows(), me_e]), np.concatenate([eadj.col.astype(np.int64), me_e]),
                                edges.shape[0], edges.shape[0])
         inc_n, inc_e = incidence_csr(n_node, edges)
         return cls(n_node, edges.shape[0], edges.astype(I32), adj, eadj, inc_n, inc_e,
-                   dict(directed=directed, order=order, length=length))
+                   dict(directed=directed, order=order, length=length), raw[0], raw[1])
 
     @classmethod
     def from_inp(cls, path):
@@ -511,7 +518,8 @@ class DrainageGraph:
         inc_e = csr_from_dense(node_edge.T, keep_values=True)
         if edges is None:
             edges = np.zeros((n_edge, 2), dtype=I32)
-        return cls(n_node, n_edge, np.asarray(edges, dtype=I32), a, ea, inc_n, inc_e, {})
+        return cls(n_node, n_edge, np.asarray(edges, dtype=I32), a, ea, inc_n, inc_e, {},
+                   csr_from_dense(adj, keep_values=True), csr_from_dense(edge_adj, keep_values=True))
 
 
 def synthetic_drainage_network(n_node, n_edge, seed=0, window=64, max_degree=6, loop_hops=8):

@@ -288,7 +288,23 @@ class GCNConv(nn.Module):
 
     @staticmethod
     def preprocess(adj):
-        """gcn_filter: D^-1/2 (A + I) D^-1/2, row-sum degrees, inf -> 0 (`emulator.py:133`)."""
+        """gcn_filter: D^-1/2 (A + I) D^-1/2, row-sum degrees, inf -> 0 (`emulator.py:133`).  A square `graph.CSR` (values, or
+        ones when it has none) gives a `graph.CSR` with the normalised values on the pattern of A united with the diagonal."""
+        if isinstance(adj, CSR):
+            n = adj.n_rows
+            val = np.ones(adj.nnz) if adj.val is None else np.asarray(adj.val, dtype=np.float64)
+            rows, cols = adj.rows(), adj.col.astype(np.int64)
+            diag = rows == cols
+            miss = np.setdiff1d(np.arange(n, dtype=np.int64), rows[diag])            # rows whose diagonal A does not store
+            from .graph import _csr_from_pairs
+            ai = _csr_from_pairs(np.concatenate([rows, miss]), np.concatenate([cols, miss]), n, adj.n_cols,
+                                 np.concatenate([val + diag, np.ones(miss.shape[0])]))
+            rows, cols = ai.rows(), ai.col.astype(np.int64)
+            deg = np.bincount(rows, weights=ai.val, minlength=n)
+            with np.errstate(divide='ignore'):
+                dinv = np.power(deg, -0.5)
+            dinv[np.isinf(dinv)] = 0.0
+            return CSR(ai.rowptr, ai.col, n, adj.n_cols, dinv[rows] * ai.val * dinv[cols])
         a = np.asarray(adj, dtype=np.float64) + np.eye(len(adj))
         deg = a.sum(axis=1)
         with np.errstate(divide='ignore'):
@@ -304,8 +320,13 @@ class GCNConv(nn.Module):
         hit = self._cache.get(id(a))
         if hit is not None and hit[0] is a:
             return hit[1], hit[2]
-        dense = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
-        csr = csr_from_dense(dense, keep_values=True)
+        if isinstance(a, CSR):
+            if a.val is None:
+                raise ValueError('GCNConv: a CSR filter must carry its values (GCNConv.preprocess(csr))')
+            csr = a
+        else:
+            dense = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+            csr = csr_from_dense(dense, keep_values=True)
         h = _lib.CsrHandle(csr)
         val = torch.as_tensor(csr.val, dtype=torch.float32, device=device)
         self._cache[id(a)] = (a, h, val)
@@ -340,9 +361,17 @@ class DiffusionConv(nn.Module):
     takes the constant coefficient theta_q[K]; with r = x.sum(-1) the dense (N, N) product collapses to the support of a_hat
     plus a rank-one term (uds_diffusion_forward).  a_hat = DiffusionConv.preprocess(adj): a dense array, or a `graph.CSR`
     carrying its values (no N x N array on the host).  Training: `autograd.DiffusionFn` (uds_diffusion_backward gives d r and
-    d kernel; the feature sum r = x.sum(-1) stays a torch op in front, its backward broadcasts d r over the features)."""
+    d kernel; the feature sum r = x.sum(-1) stays a torch op in front, its backward broadcasts d r over the features).
 
-    def __init__(self, channels, K=6, activation='tanh', in_channels=None, generator=None):
+    Two forms of the same layer (same parameters, names and shapes).  The table form (the default) prepares
+    vals[p, q] = polyval(theta_q, a_p) - c0_q, (nnz, C), once per parameter version and the kernels read it per snapshot.
+    `moments=True` never builds it: uds_diffusion_forward_m / uds_diffusion_backward_m expand the polynomial per row from the
+    (nnz,) support values and `kernel` (`autograd.DiffusionMomentsFn`).  The caller that builds the layer picks the form from
+    what it was given: SpatialLayer / GraphBaseBlock pass moments=True when their filter is a `graph.CSR` (a model built from
+    `args.graph`, where nnz * C floats per layer is what does not fit).  `moments` is an argument of whoever constructs the layer:
+    no `args` key or model option reaches it."""
+
+    def __init__(self, channels, K=6, activation='tanh', in_channels=None, generator=None, moments=False):
         super().__init__()
         self.channels, self.K, self.activation = int(channels), int(K) + 1, activation or 'linear'      # spektral: self.K = K + 1
         if self.channels % 4:
@@ -350,6 +379,7 @@ class DiffusionConv(nn.Module):
         lim = math.sqrt(6.0 / (2 * self.K))         # glorot_uniform on shape (K + 1,): fan_in = fan_out = K + 1
         self.kernel = _param((torch.rand((self.channels, self.K), generator=generator) * 2 - 1) * lim)
         self._cache, self._vals = {}, None
+        self.moments = bool(moments)
 
     @staticmethod
     def preprocess(adj):
@@ -382,6 +412,8 @@ class DiffusionConv(nn.Module):
                 csr = csr_from_dense(dense, keep_values=True)
             hit = self._cache[id(a)] = (a, _lib.CsrHandle(csr), torch.as_tensor(csr.val, dtype=torch.float32, device=device))
             self._vals = None
+        if self.moments:
+            return hit[1], None, None, hit[2]
         key = (self.kernel._version, self.kernel.data_ptr(), id(a))
         if self._vals is None or self._vals[0] != key:
             av = hit[2].double()[:, None]
@@ -397,6 +429,13 @@ class DiffusionConv(nn.Module):
         h, vals, c0, a_sup = self._filter(a, x.device)
         xs, lead = _flatten_snapshots(x)
         r = xs.sum(dim=-1)
+        if self.moments:
+            if _ag.grad_on(x, self.kernel):
+                out = _ag.DiffusionMomentsFn.apply(r, self.kernel, h, a_sup, self.activation)
+            else:
+                out = _lib.diffusion_forward_m(h, a_sup, self.kernel.detach().contiguous(), r.contiguous(), r.sum(dim=-1).contiguous(),
+                                               self.activation)
+            return out.reshape(lead + out.shape[-2:])
         if _ag.grad_on(x, self.kernel):
             out = _ag.DiffusionFn.apply(r, self.kernel, h, a_sup, vals, c0, self.activation)
             return out.reshape(lead + out.shape[-2:])
@@ -572,8 +611,9 @@ class SpatialLayer(nn.Module):
             self.gcn_x = GCNConv(self.d, activation=activation, in_channels=fx + self.h, generator=g)
             self.gcn_e = GCNConv(self.d, activation=activation, in_channels=fe + self.h, generator=g)
         else:
-            self.gcn_x = DiffusionConv(self.d, activation=activation, generator=g)        # emulator.py:229-230 with net = DiffusionConv
-            self.gcn_e = DiffusionConv(self.d, activation=activation, generator=g)
+            # emulator.py:229-230 with net = DiffusionConv; CSR filters (a model built from args.graph): the table-free form
+            self.gcn_x = DiffusionConv(self.d, activation=activation, generator=g, moments=isinstance(filters[0], CSR))
+            self.gcn_e = DiffusionConv(self.d, activation=activation, generator=g, moments=isinstance(filters[1], CSR))
         self._net = net
         self._packed = None       # (parameter versions, packed bf16 hi/lo fragments) of the four GEMM kernels
         self.last_path = None     # which kernels the last forward ran: 'fused', 'fused+remainder', 'unfused' (tests, bench)
@@ -816,8 +856,8 @@ class SpatialLayer(nn.Module):
 class GraphBaseBlock(nn.Module):
     """The spatial block of the `graph_base` variants (`emulator.py:220-223,273-276`): ONE graph over the N nodes and the
     E links (`get_node_based_adj` / `get_edge_based_adj`), one conv per layer over `concat([x, e], axis=-2)`, split back into
-    node and link rows.  `filt`: the combined (N+E) x (N+E) pattern as a `graph.CSR` with self loops (GAT) or the dense
-    normalised filter (GCN)."""
+    node and link rows.  `filt`: the combined (N+E) x (N+E) pattern as a `graph.CSR` with self loops (GAT), or the normalised
+    filter of GCN / Diffusion: dense, or a `graph.CSR` with values (then the Diffusion layers run their table-free form)."""
 
     def __init__(self, n_node, n_edge, filt, embed_size, n_sp_layer, activation='relu', f_in=None, generator=None, conv='GAT',
                  precision='bf16x3', attn_heads=1):
@@ -832,6 +872,8 @@ class GraphBaseBlock(nn.Module):
             raise ValueError('attn_heads=%d needs conv=GAT, got %r' % (self.attn_heads, conv))
         f_in = int(embed_size) if f_in is None else int(f_in)
         mk = {'GAT': GATConv, 'GCN': GCNConv, 'Diffusion': DiffusionConv}[conv]
+        if conv == 'Diffusion' and isinstance(filt, CSR):
+            mk = lambda d, **kw: DiffusionConv(d, moments=True, **kw)
         if self.attn_heads > 1:      # H heads of d / H channels, concatenated: the same width d (not a reference key)
             mk = lambda d, **kw: GATConv(int(d) // self.attn_heads, attn_heads=self.attn_heads, **kw)
         self.layers = nn.ModuleList([mk(embed_size, activation=activation, in_channels=(f_in if i == 0 else embed_size), generator=generator)

@@ -202,6 +202,26 @@ int uds_diffusion_backward(const uds_csr_t *csr, const uds_csr_t *csr_t, const i
                            const float *c0, const float *r, const float *tot, const float *y, const float *gy, int64_t S, int64_t C,
                            int64_t K1, int act, float *workspace, float *dr, float *dtheta, uds_stream_t stream);
 
+/* uds_diffusion_forward / uds_diffusion_backward without the (nnz, C) table `vals` (spektral DiffusionConv, emulator.py:135-138,229):
+ * the polynomial is expanded per ROW instead of per entry.  theta (C, K1): the layer's kernel, row q = theta_q, highest power
+ * first (K = K1 - 1, c0[q] = theta[q][K]); a (nnz): the values a_hat takes on the support.  With the row moments
+ *   M_0[s, i] = tot[s],   M_m[s, i] = sum_{p in row i} a[p]^m r[s, col[p]]   (m = 1..K; powers by running product, p ascending)
+ *   out[s, i, q] = act( sum_{m = 0..K} theta[q][K - m] * M_m[s, i] )          (m ascending)
+ * and in reverse, with gz = act'(y) * gy and G_m[s, i] = sum_q theta[q][K - m] gz[s, i, q]:
+ *   dtheta[q, k] = sum_{s, i} gz[s, i, q] * M_{K-k}[s, i]          -- the launches of uds_diffusion_backward: the same bits
+ *   dr[s, j]     = sum_i G_0[s, i] + sum_{p : col[p] = j} sum_{m = 1..K} a[p]^m G_m[s, row(p)]
+ * Reads a, r and theta (held in LDS) where the table entries read nnz * C floats per snapshot.  Same contract as the table
+ * entries: C % 4 == 0, C <= 256, 1 <= K1 <= 16, S <= 65535; theta, out, y, gy and workspace 16-byte aligned; exact fp32, no
+ * atomics (two calls give the same bits), no allocation or synchronisation.  csr_t / perm_t as uds_diffusion_backward;
+ * workspace: uds_diffusion_backward_m_workspace_floats(n_rows, S, C, K1) floats (-1 for sizes the kernels do not take). */
+int uds_diffusion_forward_m(const uds_csr_t *csr, const float *a, const float *theta, const float *r, const float *tot,
+                            int64_t S, int64_t C, int64_t K1, int act, float *out, uds_stream_t stream);
+int64_t uds_diffusion_backward_m_workspace_floats(int64_t n_rows, int64_t S, int64_t C, int64_t K1);
+int uds_diffusion_backward_m(const uds_csr_t *csr, const uds_csr_t *csr_t, const int32_t *perm_t, const float *a,
+                             const float *theta, const float *r, const float *tot, const float *y, const float *gy,
+                             int64_t S, int64_t C, int64_t K1, int act, float *workspace, float *dr, float *dtheta,
+                             uds_stream_t stream);
+
 /* Message buffers of the graph-sharded spatial block (one 200k-node network node-cut over the GPUs; the reference holds
  * whole graphs on one device, SURVEY.md F5 / 8e -- the exchange itself is torch.distributed isend / irecv over RCCL).
  *   pack:   buf[s, i, :] = i < nx ? x[s, idx_x[i], :] : e[s, idx_e[i - nx], :]     one buffer per peer, node rows then link rows
