@@ -19,6 +19,7 @@ FLAG_EXACT_FP32, FLAG_REQUIRE_FUSED = 1, 2
 PRECISION_FLAGS = {'bf16x3': 0, 'fp32': FLAG_EXACT_FP32}
 
 ACT = {None: 0, 'linear': 0, 'relu': 1, 'tanh': 2, 'sigmoid': 3, 'hard_sigmoid': 4}
+_KIND = {'GRU': 0, 'LSTM': 1}           # the `kind` argument of the recurrent entries
 
 _c_i64 = ctypes.c_int64
 _c_int = ctypes.c_int
@@ -211,6 +212,13 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _nothing_to_launch(t, name, result):
+    """`result` for a call whose output is empty: no launch (an empty tensor has no device pointer), but the operand `t`
+    is still checked."""
+    _dev(t, name)
+    return result
+
+
 def _out(out, shape, like, name):
     """The caller's output tensor (checked: shape, fp32, contiguous, same device) or a new one."""
     if out is None:
@@ -376,9 +384,8 @@ def dense_act(xa, kernel, bias=None, act='linear', xb=None, attn=None):
     if attn is not None:
         s_self = torch.empty(xa.shape[:-1], device=xa.device, dtype=torch.float32)
         s_nbr = torch.empty_like(s_self)
-    if rows == 0:                       # nothing to launch (an empty tensor has no device pointer)
-        _dev(xa, 'xa')
-        return (out, s_self, s_nbr) if attn is not None else out
+    if rows == 0:
+        return _nothing_to_launch(xa, 'xa', (out, s_self, s_nbr) if attn is not None else out)
     _check(lib.uds_dense_act(_dev(xa, 'xa'), fa, _dev(xb, 'xb', True), fb, rows, _dev(kernel, 'kernel'),
                              _dev(bias, 'bias', True), fo, ACT[act],
                              _dev(attn[0], 'a_self') if attn else None, _dev(attn[1], 'a_nbr') if attn else None,
@@ -396,8 +403,7 @@ def conv1d_causal(x, kernel, bias=None, dilation=1, act='linear'):
     taps, _, H = kernel.shape
     out = torch.empty((B, T, R, H), device=x.device, dtype=torch.float32)
     if out.numel() == 0:
-        _dev(x, 'x')
-        return out
+        return _nothing_to_launch(x, 'x', out)
     _check(lib.uds_conv1d_causal(_dev(x, 'x'), B, T, R, F, _dev(kernel, 'kernel'), _dev(bias, 'bias', True), taps, dilation, H,
                                  ACT[act], _dev(out, 'out'), _stream()), 'uds_conv1d_causal')
     return out
@@ -405,7 +411,7 @@ def conv1d_causal(x, kernel, bias=None, dilation=1, act='linear'):
 
 def recurrent_fused_supported(F, kind):
     """Input forms uds_recurrent_fused takes: F = 64 / 128 input rows (W + U must fit the LDS), F = 0 = given projection."""
-    return bool(load().uds_recurrent_fused_supported(int(F), 0 if kind == 'GRU' else 1))
+    return bool(load().uds_recurrent_fused_supported(int(F), _KIND[kind]))
 
 
 def recurrent_pack(kernel, recurrent_kernel):
@@ -427,7 +433,7 @@ def recurrent_fused(x, packed, b_in, b_rec, kind, projected=False):
     out = torch.empty((B, T, R, 64), device=x.device, dtype=torch.float32)
     if out.numel():
         _check(lib.uds_recurrent_fused(_dev(x, 'x'), 0 if projected else F, packed.data_ptr(), _dev(b_in, 'b_in', True), _dev(b_rec, 'b_rec', True),
-                                       B, T, R, 0 if kind == 'GRU' else 1, _dev(out, 'out'), _stream()), 'uds_recurrent_fused')
+                                       B, T, R, _KIND[kind], _dev(out, 'out'), _stream()), 'uds_recurrent_fused')
     return out
 
 
@@ -497,9 +503,9 @@ def dropout(x, rate, seed, offset):
     return out
 
 
-def recurrent_forward_train(xp, recurrent_kernel, recurrent_bias, kind):
-    """(h, c): hidden states (B, T, R, H) as recurrent_forward, plus the LSTM's cell states (None for the GRU) -- what
-    recurrent_backward needs from the forward pass."""
+def _recurrent_forward(xp, recurrent_kernel, recurrent_bias, kind, train):
+    """(h, c) through uds_recurrent_forward_train (c: the LSTM's cell states, None for the GRU) or, train False, (h, None)
+    through uds_recurrent_forward."""
     lib = load()
     B, T, R, GH = xp.shape
     G = {'GRU': 3, 'LSTM': 4}[kind]
@@ -507,12 +513,18 @@ def recurrent_forward_train(xp, recurrent_kernel, recurrent_bias, kind):
     if GH != G * H or tuple(recurrent_kernel.shape) != (H, GH):
         raise UdsError('recurrent_forward: xp %r, recurrent kernel %r for a %s' % (tuple(xp.shape), tuple(recurrent_kernel.shape), kind))
     out = torch.empty((B, T, R, H), device=xp.device, dtype=torch.float32)
-    c = torch.empty_like(out) if kind == 'LSTM' else None
+    c = torch.empty_like(out) if train and kind == 'LSTM' else None
     if out.numel():
-        _check(lib.uds_recurrent_forward_train(_dev(xp, 'xp'), _dev(recurrent_kernel, 'recurrent_kernel'), _dev(recurrent_bias, 'recurrent_bias', True),
-                                               B, T, R, H, 0 if kind == 'GRU' else 1, _dev(out, 'out'), _dev(c, 'c', True), _stream()),
-               'uds_recurrent_forward_train')
+        entry = 'uds_recurrent_forward_train' if train else 'uds_recurrent_forward'
+        _check(getattr(lib, entry)(_dev(xp, 'xp'), _dev(recurrent_kernel, 'recurrent_kernel'), _dev(recurrent_bias, 'recurrent_bias', True),
+                                   B, T, R, H, _KIND[kind], _dev(out, 'out'), *([_dev(c, 'c', True)] if train else []), _stream()), entry)
     return out, c
+
+
+def recurrent_forward_train(xp, recurrent_kernel, recurrent_bias, kind):
+    """(h, c): hidden states (B, T, R, H) as recurrent_forward, plus the LSTM's cell states (None for the GRU) -- what
+    recurrent_backward needs from the forward pass."""
+    return _recurrent_forward(xp, recurrent_kernel, recurrent_bias, kind, True)
 
 
 RECURRENT_TRAIN_WIDTHS = tuple(range(16, 129, 16))      # units the back-propagation-through-time kernels are built for
@@ -573,30 +585,16 @@ def recurrent_backward(xp, packed, recurrent_bias, h, c, gh, kind):
     dxp = torch.empty_like(xp)
     darec = torch.empty((G, B, T, R, H), device=xp.device, dtype=torch.float32)
     if dxp.numel():
-        if route == 'uds_recurrent_backward':
-            _check(lib.uds_recurrent_backward(_dev(xp, 'xp'), packed.data_ptr(), _dev(recurrent_bias, 'recurrent_bias', True), _dev(h, 'h'),
-                                              _dev(c, 'c', True), _dev(gh, 'gh'), B, T, R, 0 if kind == 'GRU' else 1, _dev(dxp, 'dxp'),
-                                              _dev(darec, 'darec'), _stream()), 'uds_recurrent_backward')
-        else:
-            _check(lib.uds_recurrent_backward_h(_dev(xp, 'xp'), packed.data_ptr(), _dev(recurrent_bias, 'recurrent_bias', True), _dev(h, 'h'),
-                                                _dev(c, 'c', True), _dev(gh, 'gh'), B, T, R, H, 0 if kind == 'GRU' else 1, _dev(dxp, 'dxp'),
-                                                _dev(darec, 'darec'), _stream()), 'uds_recurrent_backward_h')
+        width = [] if route == 'uds_recurrent_backward' else [H]      # the 64-unit entry takes no width
+        _check(getattr(lib, route)(_dev(xp, 'xp'), packed.data_ptr(), _dev(recurrent_bias, 'recurrent_bias', True), _dev(h, 'h'),
+                                   _dev(c, 'c', True), _dev(gh, 'gh'), B, T, R, *width, _KIND[kind], _dev(dxp, 'dxp'), _dev(darec, 'darec'),
+                                   _stream()), route)
     return dxp, darec
 
 
 def recurrent_forward(xp, recurrent_kernel, recurrent_bias, kind):
     """Hidden states (B, T, R, H) of a GRU (kind 'GRU') or LSTM from the input projections xp (B, T, R, G*H)."""
-    lib = load()
-    B, T, R, GH = xp.shape
-    G = {'GRU': 3, 'LSTM': 4}[kind]
-    H = GH // G
-    if GH != G * H or tuple(recurrent_kernel.shape) != (H, GH):
-        raise UdsError('recurrent_forward: xp %r, recurrent kernel %r for a %s' % (tuple(xp.shape), tuple(recurrent_kernel.shape), kind))
-    out = torch.empty((B, T, R, H), device=xp.device, dtype=torch.float32)
-    if out.numel():
-        _check(lib.uds_recurrent_forward(_dev(xp, 'xp'), _dev(recurrent_kernel, 'recurrent_kernel'), _dev(recurrent_bias, 'recurrent_bias', True),
-                                         B, T, R, H, 0 if kind == 'GRU' else 1, _dev(out, 'out'), _stream()), 'uds_recurrent_forward')
-    return out
+    return _recurrent_forward(xp, recurrent_kernel, recurrent_bias, kind, False)[0]
 
 
 def rowgemm_supported(k_total, f_in, f_out):
@@ -739,19 +737,24 @@ def _halo_all_args(x, e, idx_x, idx_e, off_x, off_e, what):
     return P, int(idx_x.numel()), int(idx_e.numel())
 
 
+def _halo_pack_all(entry, x, e, idx_x, idx_e, off_x, off_e):
+    """uds_halo_pack_all or uds_halo_pack_clear_all: the same arguments, the same buffer."""
+    lib = load()
+    P, nx, ne = _halo_all_args(x, e, idx_x, idx_e, off_x, off_e, entry[4:])
+    S, n_x, F = x.shape
+    buf = torch.empty(S * (nx + ne) * F, device=x.device, dtype=torch.float32)
+    if buf.numel():
+        _check(getattr(lib, entry)(_dev(x, 'x') if nx else None, n_x, _dev(e, 'e') if ne else None, e.shape[1], S, F,
+                                   _dev_i32(idx_x, 'idx_x') if nx else None, nx, _dev_i32(idx_e, 'idx_e') if ne else None, ne,
+                                   _dev_i32(off_x, 'off_x'), _dev_i32(off_e, 'off_e'), P, _dev(buf, 'buf'), _stream()), entry)
+    return buf
+
+
 def halo_pack_all(x, e, idx_x, idx_e, off_x, off_e):
     """The messages of all P peers, ONE launch (uds_halo_pack_all): a flat buffer in which peer q's message is the (S, nx_q + ne_q, F)
     block [x[:, idx_x[off_x[q]:off_x[q+1]]] | e[:, idx_e[off_e[q]:off_e[q+1]]]] at element offset S F (off_x[q] + off_e[q]).
     idx_* / off_* are int32 device tensors (off_*: P + 1 offsets); any F >= 1."""
-    lib = load()
-    P, nx, ne = _halo_all_args(x, e, idx_x, idx_e, off_x, off_e, 'halo_pack_all')
-    S, n_x, F = x.shape
-    buf = torch.empty(S * (nx + ne) * F, device=x.device, dtype=torch.float32)
-    if buf.numel():
-        _check(lib.uds_halo_pack_all(_dev(x, 'x') if nx else None, n_x, _dev(e, 'e') if ne else None, e.shape[1], S, F,
-                                     _dev_i32(idx_x, 'idx_x') if nx else None, nx, _dev_i32(idx_e, 'idx_e') if ne else None, ne,
-                                     _dev_i32(off_x, 'off_x'), _dev_i32(off_e, 'off_e'), P, _dev(buf, 'buf'), _stream()), 'uds_halo_pack_all')
-    return buf
+    return _halo_pack_all('uds_halo_pack_all', x, e, idx_x, idx_e, off_x, off_e)
 
 
 def halo_unpack_all(buf, x, e, idx_x, idx_e, off_x, off_e):
@@ -771,16 +774,7 @@ def halo_unpack_all(buf, x, e, idx_x, idx_e, off_x, off_e):
 def halo_pack_clear_all(x, e, idx_x, idx_e, off_x, off_e):
     """halo_pack_all, and every row it reads is then zeroed in x / e (in place), ONE launch (uds_halo_pack_clear_all): the
     first half of the exchange's adjoint.  The rows listed across all peers must be distinct."""
-    lib = load()
-    P, nx, ne = _halo_all_args(x, e, idx_x, idx_e, off_x, off_e, 'halo_pack_clear_all')
-    S, n_x, F = x.shape
-    buf = torch.empty(S * (nx + ne) * F, device=x.device, dtype=torch.float32)
-    if buf.numel():
-        _check(lib.uds_halo_pack_clear_all(_dev(x, 'x') if nx else None, n_x, _dev(e, 'e') if ne else None, e.shape[1], S, F,
-                                           _dev_i32(idx_x, 'idx_x') if nx else None, nx, _dev_i32(idx_e, 'idx_e') if ne else None, ne,
-                                           _dev_i32(off_x, 'off_x'), _dev_i32(off_e, 'off_e'), P, _dev(buf, 'buf'), _stream()),
-               'uds_halo_pack_clear_all')
-    return buf
+    return _halo_pack_all('uds_halo_pack_clear_all', x, e, idx_x, idx_e, off_x, off_e)
 
 
 def halo_accumulate_all(buf, x, e, off_x, off_e, tgt_x, tgt_e, ptr, src):
@@ -812,42 +806,36 @@ def remainder_pack(rest):
     return out
 
 
+def _remainder_forward(entry, packed, shape, t, name, h=None, dense=None):
+    """uds_remainder_forward on t = x (..., M, h), or uds_remainder_forward_dense on t = e (..., M, F) with dense =
+    (packed_w, bias, act) and the output width h."""
+    lib = load()
+    R, M = shape
+    if t.dim() < 2 or t.shape[-2] != M:
+        raise UdsError('%s: %s %r against rest (%d, %d)' % (entry[4:], name, tuple(t.shape), R, M))
+    F = t.shape[-1]
+    h = F if dense is None else h
+    S = t.numel() // (M * F) if M * F else 0
+    out = torch.empty(tuple(t.shape[:-2]) + (R, h), device=t.device, dtype=torch.float32)
+    if S == 0:
+        return _nothing_to_launch(t, name, out)
+    ws = torch.empty(lib.uds_remainder_workspace_bytes(R, M, S, h) // 4, device=t.device, dtype=torch.float32)
+    _check(getattr(lib, entry)(packed.data_ptr(), R, M, _dev(t, name),
+                               *([] if dense is None else [F, dense[0].data_ptr(), _dev(dense[1], 'bias', True), ACT[dense[2]]]),
+                               S, h, ws.data_ptr(), _dev(out, 'out'), _stream()), entry)
+    return out
+
+
 def remainder_forward(packed, shape, x):
     """out[..., r, :] = sum_m rest[r, m] x[..., m, :] on the matrix cores (split-bf16): `packed` = remainder_pack(rest),
     shape = rest.shape, x (..., M, h) with h % 4 == 0, h <= 64."""
-    lib = load()
-    R, M = shape
-    if x.dim() < 2 or x.shape[-2] != M:
-        raise UdsError('remainder_forward: x %r against rest (%d, %d)' % (tuple(x.shape), R, M))
-    h = x.shape[-1]
-    S = x.numel() // (M * h) if M * h else 0
-    out = torch.empty(tuple(x.shape[:-2]) + (R, h), device=x.device, dtype=torch.float32)
-    if S == 0:
-        _dev(x, 'x')
-        return out
-    ws = torch.empty(lib.uds_remainder_workspace_bytes(R, M, S, h) // 4, device=x.device, dtype=torch.float32)
-    _check(lib.uds_remainder_forward(packed.data_ptr(), R, M, _dev(x, 'x'), S, h, ws.data_ptr(), _dev(out, 'out'), _stream()),
-           'uds_remainder_forward')
-    return out
+    return _remainder_forward('uds_remainder_forward', packed, shape, x, 'x')
 
 
 def remainder_forward_dense(packed, shape, e, packed_w, bias, act, h):
     """rest @ act(e W + b) without the fp32 x_e in between (uds_remainder_forward_dense): e (..., M, F) with F 64 or 128, packed_w =
     rowgemm_pack(W (F, h)), h 32 or 64 -> (..., R, h)."""
-    lib = load()
-    R, M = shape
-    if e.dim() < 2 or e.shape[-2] != M:
-        raise UdsError('remainder_forward_dense: e %r against rest (%d, %d)' % (tuple(e.shape), R, M))
-    F = e.shape[-1]
-    S = e.numel() // (M * F) if M * F else 0
-    out = torch.empty(tuple(e.shape[:-2]) + (R, h), device=e.device, dtype=torch.float32)
-    if S == 0:
-        _dev(e, 'e')
-        return out
-    ws = torch.empty(lib.uds_remainder_workspace_bytes(R, M, S, h) // 4, device=e.device, dtype=torch.float32)
-    _check(lib.uds_remainder_forward_dense(packed.data_ptr(), R, M, _dev(e, 'e'), F, packed_w.data_ptr(), _dev(bias, 'bias', True), ACT[act], S, h,
-                                           ws.data_ptr(), _dev(out, 'out'), _stream()), 'uds_remainder_forward_dense')
-    return out
+    return _remainder_forward('uds_remainder_forward_dense', packed, shape, e, 'e', h, (packed_w, bias, act))
 
 
 def rowgemm_forward(x, packed, bias, f_out, act='linear', taps=1, dilation=1, out=None):
@@ -865,8 +853,7 @@ def rowgemm_forward(x, packed, bias, f_out, act='linear', taps=1, dilation=1, ou
         out_shape = (B, T, R, f_out)
     out = _out(out, out_shape, x, 'out')
     if out.numel() == 0:
-        _dev(x, 'x')
-        return out
+        return _nothing_to_launch(x, 'x', out)
     _check(lib.uds_rowgemm_forward(_dev(x, 'x'), B, T, R, F, packed.data_ptr(), _dev(bias, 'bias', True), taps, dilation, f_out,
                                    ACT[act], _dev(out, 'out'), _stream()), 'uds_rowgemm_forward')
     return out
@@ -904,8 +891,7 @@ def rowgemm_cat(x, x2, packed, bias, f_out, act='linear', out=None, col0=0):
     if out.numel() // ldo != rows:
         raise UdsError('rowgemm_cat: out %r does not have %d rows' % (tuple(out.shape), rows))
     if rows == 0:
-        _dev(x, 'x')
-        return out
+        return _nothing_to_launch(x, 'x', out)
     _check(lib.uds_rowgemm_forward_cat(_dev(x, 'x'), F1, _dev(x2, 'x2', True), F2, 1, 1, rows, packed.data_ptr(), _dev(bias, 'bias', True),
                                        1, 1, f_out, ACT[act], _dev(out, 'out'), ldo, col0, _stream()), 'uds_rowgemm_forward_cat')
     return out
@@ -923,8 +909,7 @@ def dense_cumsum(x, packed, bias=None, res=None, act='linear', out=None):
         raise UdsError('dense_cumsum: res must be %r, got %r' % ((B, 1, R, 64), tuple(res.shape)))
     out = _out(out, (B, T, R, 64), x, 'out')
     if out.numel() == 0:
-        _dev(x, 'x')
-        return out
+        return _nothing_to_launch(x, 'x', out)
     _check(lib.uds_dense_cumsum(_dev(x, 'x'), B, T, R, packed.data_ptr(), _dev(bias, 'bias', True), _dev(res, 'res', True), ACT[act],
                                 _dev(out, 'out'), _stream()), 'uds_dense_cumsum')
     return out
@@ -972,8 +957,7 @@ def cumsum_act(x, res=None, act='linear'):
         raise UdsError('cumsum_act: res must be %r, got %r' % ((B, 1, R, F), tuple(res.shape)))
     out = torch.empty_like(x)
     if out.numel() == 0:
-        _dev(x, 'x')
-        return out
+        return _nothing_to_launch(x, 'x', out)
     _check(lib.uds_cumsum_act(_dev(x, 'x'), _dev(res, 'res', True), B, T, R, F, ACT[act], _dev(out, 'out'), _stream()),
            'uds_cumsum_act')
     return out
@@ -1024,8 +1008,7 @@ def csr_spmm(handle, val, x, bias=None, act='linear', out=None):
     S, _, F = x.shape
     out = _out(out, (S, handle.n_rows, F), x, 'out')
     if out.numel() == 0:
-        _dev(x, 'x')
-        return out
+        return _nothing_to_launch(x, 'x', out)
     _check(lib.uds_csr_spmm(handle.ptr, _dev(val, 'val', True), _dev(x, 'x'), S, F, _dev(bias, 'bias', True), ACT[act],
                             _dev(out, 'out'), _stream()), 'uds_csr_spmm')
     return out
@@ -1045,8 +1028,7 @@ def gat_forward(handle, xa, kernel, a_self, a_nbr, bias=None, act='relu', xb=Non
         raise UdsError('kernel %r does not match %d input features' % (tuple(kernel.shape), fa + fb))
     out = torch.empty((S, n, d), device=xa.device, dtype=torch.float32)
     if out.numel() == 0:
-        _dev(xa, 'xa')
-        return out
+        return _nothing_to_launch(xa, 'xa', out)
     ws = torch.empty(lib.uds_gat_workspace_floats(n, S, d), device=xa.device, dtype=torch.float32)
     _check(lib.uds_gat_forward(handle.ptr, _dev(xa, 'xa'), fa, _dev(xb, 'xb', True), fb, S, _dev(kernel, 'kernel'),
                                _dev(a_self, 'a_self'), _dev(a_nbr, 'a_nbr'), _dev(bias, 'bias', True), d, ACT[act],
@@ -1057,44 +1039,40 @@ def gat_forward(handle, xa, kernel, a_self, a_nbr, bias=None, act='relu', xb=Non
     return out
 
 
+def _gat_aggregate(entry, handle, hx, s_self, s_nbr, bias, act, extra, out):
+    """One of the four single-head aggregate entries; extra: its (tensor, name, optional) operands between bias and S."""
+    S, _, d = hx.shape
+    out = _out(out, hx.shape, hx, 'out')
+    if out.numel() == 0:
+        return _nothing_to_launch(hx, 'hx', out)
+    _check(getattr(load(), entry)(handle.ptr, _dev(hx, 'hx'), _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(bias, 'bias', True),
+                                  *[_dev(*op) for op in extra], S, d, ACT[act], _dev(out, 'out'), _stream()), entry)
+    return out
+
+
 def gat_aggregate(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask=None, coef=None, out=None):
     """Attention softmax + neighbour sum of a GATConv from precomputed hx (S,n,d), s_self / s_nbr (S,n); out: the caller's result tensor.
     edge_mask (S, nnz): per-snapshot 0/1 over the pattern's entries (`use_adj`; the diagonal always takes part).
     coef (S, nnz): multiplier of the normalised coefficients (Spektral's attention dropout in training, uds_gat_aggregate_coef)."""
-    lib = load()
     S, n, d = hx.shape
+    rows_ok = n == handle.n_rows and tuple(s_self.shape) == (S, n) and tuple(s_nbr.shape) == (S, n)
     if coef is not None:
         if edge_mask is not None:
             raise UdsError('gat_aggregate: edge_mask and coef together are not built')
-        if tuple(coef.shape) != (S, handle.nnz) or n != handle.n_rows or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
+        if tuple(coef.shape) != (S, handle.nnz) or not rows_ok:
             raise UdsError('gat_aggregate: coef %r / hx %r for %d snapshots of a %d-row, %d-entry pattern' %
                            (tuple(coef.shape), tuple(hx.shape), S, handle.n_rows, handle.nnz))
-        out = _out(out, hx.shape, hx, 'out')
-        if out.numel():
-            _check(lib.uds_gat_aggregate_coef(handle.ptr, _dev(hx, 'hx'), _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(bias, 'bias', True),
-                                              _dev(coef, 'coef'), S, d, ACT[act], _dev(out, 'out'), _stream()), 'uds_gat_aggregate_coef')
-        return out
+        return _gat_aggregate('uds_gat_aggregate_coef', handle, hx, s_self, s_nbr, bias, act, [(coef, 'coef')], out)
     if edge_mask is not None:
         if tuple(edge_mask.shape) != (S, handle.nnz):
             raise UdsError('gat_aggregate: edge_mask %r for %d snapshots of a %d-entry pattern' % (tuple(edge_mask.shape), S, handle.nnz))
-        if n != handle.n_rows or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
+        if not rows_ok:
             raise UdsError('gat_aggregate: hx %r does not match a %d-row pattern' % (tuple(hx.shape), handle.n_rows))
-        out = _out(out, hx.shape, hx, 'out')
-        if out.numel():
-            _check(lib.uds_gat_aggregate_masked(handle.ptr, _dev(hx, 'hx'), _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(bias, 'bias', True),
-                                                _dev(edge_mask, 'edge_mask'), S, d, ACT[act], _dev(out, 'out'), _stream()),
-                   'uds_gat_aggregate_masked')
-        return out
-    if n != handle.n_rows or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
+        return _gat_aggregate('uds_gat_aggregate_masked', handle, hx, s_self, s_nbr, bias, act, [(edge_mask, 'edge_mask')], out)
+    if not rows_ok:
         raise UdsError('gat_aggregate: hx %r, s_self %r, s_nbr %r do not match a %d-row pattern' %
                        (tuple(hx.shape), tuple(s_self.shape), tuple(s_nbr.shape), handle.n_rows))
-    out = _out(out, hx.shape, hx, 'out')
-    if out.numel() == 0:
-        _dev(hx, 'hx')
-        return out
-    _check(lib.uds_gat_aggregate(handle.ptr, _dev(hx, 'hx'), _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(bias, 'bias', True), S, d,
-                                 ACT[act], _dev(out, 'out'), _stream()), 'uds_gat_aggregate')
-    return out
+    return _gat_aggregate('uds_gat_aggregate', handle, hx, s_self, s_nbr, bias, act, [], out)
 
 
 def _gat_backward_outputs(grad, out):
@@ -1104,22 +1082,26 @@ def _gat_backward_outputs(grad, out):
     return _out(o[0], grad.shape, grad, 'd_hx'), _out(o[1], (S, n), grad, 'ds_self'), _out(o[2], (S, n), grad, 'ds_nbr')
 
 
+def _gat_backward(entry, handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, extra, out, workspace):
+    """uds_gat_backward_coef or uds_gat_backward_ex; extra: its (tensor, name, optional) operands between a_nbr and S."""
+    S, n, d = grad.shape
+    d_hx, ds_self, ds_nbr = _gat_backward_outputs(grad, out)
+    if grad.numel() == 0:
+        return _nothing_to_launch(grad, 'grad', (d_hx, ds_self, ds_nbr))
+    ws = _out(workspace, (2, S, max(handle.nnz, 1)), grad, 'workspace')      # alpha and de per pattern entry
+    _check(getattr(load(), entry)(handle.ptr, handle_t.ptr, _dev_i32(perm_t, 'perm_t'), _dev(grad, 'grad'), _dev(hx, 'hx'),
+                                  _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(a_self, 'a_self'), _dev(a_nbr, 'a_nbr'),
+                                  *[_dev(*op) for op in extra], S, d, _dev(ws[0], 'alpha_ws'), _dev(ws[1], 'de_ws'), _dev(d_hx, 'd_hx'),
+                                  _dev(ds_self, 'ds_self'), _dev(ds_nbr, 'ds_nbr'), _stream()), entry)
+    return d_hx, ds_self, ds_nbr
+
+
 def gat_backward(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, coef=None, out=None, workspace=None):
     """Reverse mode of the attention / aggregation part of gat_forward (uds_gat_backward): grad = dL/d(pre-activation)
     (S,n,d) -> d_hx (S,n,d), ds_self (S,n), ds_nbr (S,n).  coef: the attention-dropout multiplier of the forward pass, if any.
     out: the caller's (d_hx, ds_self, ds_nbr); workspace: the caller's (2, S, max(nnz, 1)) alpha / de scratch."""
-    lib = load()
-    S, n, d = grad.shape
-    d_hx, ds_self, ds_nbr = _gat_backward_outputs(grad, out)
-    if grad.numel() == 0:
-        _dev(grad, 'grad')
-        return d_hx, ds_self, ds_nbr
-    ws = _out(workspace, (2, S, max(handle.nnz, 1)), grad, 'workspace')      # alpha and de per pattern entry
-    _check(lib.uds_gat_backward_coef(handle.ptr, handle_t.ptr, _dev_i32(perm_t, 'perm_t'), _dev(grad, 'grad'), _dev(hx, 'hx'),
-                                     _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(a_self, 'a_self'), _dev(a_nbr, 'a_nbr'),
-                                     _dev(coef, 'coef', True), S, d, _dev(ws[0], 'alpha_ws'), _dev(ws[1], 'de_ws'), _dev(d_hx, 'd_hx'),
-                                     _dev(ds_self, 'ds_self'), _dev(ds_nbr, 'ds_nbr'), _stream()), 'uds_gat_backward_coef')
-    return d_hx, ds_self, ds_nbr
+    return _gat_backward('uds_gat_backward_coef', handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, [(coef, 'coef', True)],
+                         out, workspace)
 
 
 def _check_entry_operand(name, t, S, handle):
@@ -1131,44 +1113,26 @@ def gat_aggregate_ex(handle, hx, s_self, s_nbr, bias=None, act='relu', edge_mask
     """gat_aggregate with an optional per-snapshot edge_mask (S, nnz) AND an optional attention-dropout coef (S, nnz) on the
     grouped kernels (uds_gat_aggregate_ex): the training path of `use_adj` GAT layers.  A masked entry leaves the softmax; the
     diagonal always takes part.  With edge_mask = all ones and coef None the result is bitwise that of gat_aggregate."""
-    lib = load()
     S, n, d = hx.shape
     if n != handle.n_rows or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
         raise UdsError('gat_aggregate_ex: hx %r, s_self %r, s_nbr %r do not match a %d-row pattern' %
                        (tuple(hx.shape), tuple(s_self.shape), tuple(s_nbr.shape), handle.n_rows))
     _check_entry_operand('gat_aggregate_ex: edge_mask', edge_mask, S, handle)
     _check_entry_operand('gat_aggregate_ex: coef', coef, S, handle)
-    out = _out(out, hx.shape, hx, 'out')
-    if out.numel() == 0:
-        _dev(hx, 'hx')
-        return out
-    _check(lib.uds_gat_aggregate_ex(handle.ptr, _dev(hx, 'hx'), _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(bias, 'bias', True),
-                                    _dev(edge_mask, 'edge_mask', True), _dev(coef, 'coef', True), S, d, ACT[act], _dev(out, 'out'),
-                                    _stream()), 'uds_gat_aggregate_ex')
-    return out
+    return _gat_aggregate('uds_gat_aggregate_ex', handle, hx, s_self, s_nbr, bias, act, [(edge_mask, 'edge_mask', True), (coef, 'coef', True)], out)
 
 
 def gat_backward_ex(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, edge_mask=None, coef=None, out=None, workspace=None):
     """Reverse mode of gat_aggregate_ex (uds_gat_backward_ex): outputs, out and workspace as gat_backward.  A masked entry
     contributes nothing."""
-    lib = load()
     S, n, d = grad.shape
     if n != handle.n_rows or tuple(hx.shape) != (S, n, d) or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
         raise UdsError('gat_backward_ex: grad %r, hx %r, s_self %r, s_nbr %r do not match a %d-row pattern' %
                        (tuple(grad.shape), tuple(hx.shape), tuple(s_self.shape), tuple(s_nbr.shape), handle.n_rows))
     _check_entry_operand('gat_backward_ex: edge_mask', edge_mask, S, handle)
     _check_entry_operand('gat_backward_ex: coef', coef, S, handle)
-    d_hx, ds_self, ds_nbr = _gat_backward_outputs(grad, out)
-    if grad.numel() == 0:
-        _dev(grad, 'grad')
-        return d_hx, ds_self, ds_nbr
-    ws = _out(workspace, (2, S, max(handle.nnz, 1)), grad, 'workspace')      # alpha and de per pattern entry
-    _check(lib.uds_gat_backward_ex(handle.ptr, handle_t.ptr, _dev_i32(perm_t, 'perm_t'), _dev(grad, 'grad'), _dev(hx, 'hx'),
-                                   _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(a_self, 'a_self'), _dev(a_nbr, 'a_nbr'),
-                                   _dev(edge_mask, 'edge_mask', True), _dev(coef, 'coef', True), S, d, _dev(ws[0], 'alpha_ws'),
-                                   _dev(ws[1], 'de_ws'), _dev(d_hx, 'd_hx'), _dev(ds_self, 'ds_self'), _dev(ds_nbr, 'ds_nbr'),
-                                   _stream()), 'uds_gat_backward_ex')
-    return d_hx, ds_self, ds_nbr
+    return _gat_backward('uds_gat_backward_ex', handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr,
+                         [(edge_mask, 'edge_mask', True), (coef, 'coef', True)], out, workspace)
 
 
 def _check_heads_operands(name, handle, hx, s_self, s_nbr, edge_mask, coef):
@@ -1223,8 +1187,7 @@ def gat_backward_heads(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self
     o = out if out is not None else (None, None, None)
     d_hx, ds_self, ds_nbr = _out(o[0], hx.shape, grad, 'd_hx'), _out(o[1], (S, n, H), grad, 'ds_self'), _out(o[2], (S, n, H), grad, 'ds_nbr')
     if grad.numel() == 0:
-        _dev(grad, 'grad')
-        return d_hx, ds_self, ds_nbr
+        return _nothing_to_launch(grad, 'grad', (d_hx, ds_self, ds_nbr))
     ws = _out(workspace, (2, S, H, max(handle.nnz, 1)), grad, 'workspace')      # alpha and de per head and pattern entry
     _check(lib.uds_gat_backward_heads(handle.ptr, handle_t.ptr, _dev_i32(perm_t, 'perm_t'), _dev(grad, 'grad'), _dev(hx, 'hx'),
                                       _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(a_self, 'a_self'), _dev(a_nbr, 'a_nbr'),
@@ -1314,9 +1277,8 @@ def spatial_layer_forward(net, p, x, e, h, d, act='relu', flags=0, xb=None, eb=N
         raise UdsError('x %r / e %r do not match the network (N=%d, E=%d)' % (tuple(x.shape), tuple(e.shape),
                                                                             net.graph.n_node, net.graph.n_edge))
     if S == 0:
-        _dev(x, 'x')
-        return (torch.empty((0, N, d), device=x.device, dtype=torch.float32),
-                torch.empty((0, E, d), device=x.device, dtype=torch.float32))
+        return _nothing_to_launch(x, 'x', (torch.empty((0, N, d), device=x.device, dtype=torch.float32),
+                                           torch.empty((0, E, d), device=x.device, dtype=torch.float32)))
     sp = _spatial_params(p)
     ws = torch.empty(lib.uds_spatial_workspace_floats(net.ptr, S, h, d), device=x.device, dtype=torch.float32)
     out_x = torch.empty((S, N, d), device=x.device, dtype=torch.float32)

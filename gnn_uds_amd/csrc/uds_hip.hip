@@ -44,7 +44,13 @@ int fail(int code, const char *fmt, ...) {
   return code;
 }
 
-#define UDS_HIP_TRY(call)                                                              \
+// The tail of an entry that ends in a launch: UDS_OK, or UDS_EHIP with the entry's name and the runtime's text.
+int launched(const char *entry, hipError_t e) {
+  if (e != hipSuccess) return fail(UDS_EHIP, "%s: launch -> %s", entry, hipGetErrorString(e));
+  return UDS_OK;
+}
+
+#define UDS_HIP_TRY(call)                                                             \
   do {                                                                                 \
     hipError_t e_ = (call);                                                            \
     if (e_ != hipSuccess) return fail(UDS_EHIP, "%s -> %s", #call, hipGetErrorString(e_)); \
@@ -305,9 +311,7 @@ int uds_dense_act(const float *xa, int64_t fa, const float *xb, int64_t fb, int6
               "uds_dense_act: a_self/a_nbr/s_self/s_nbr must be given together");
   if (rows == 0) return UDS_OK;
   uds::DenseArgs a{xa, xb, W, bias, a_self, a_nbr, out, s_self, s_nbr, (int)fa, (int)fb, (int)f_out, act, rows};
-  hipError_t e = uds::launch_dense_act(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_dense_act: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_dense_act", uds::launch_dense_act(a, static_cast<hipStream_t>(stream)));
 }
 
 int uds_conv1d_causal(const float *x, int64_t B, int64_t T, int64_t R, int64_t F, const float *kernel, const float *bias,
@@ -324,9 +328,7 @@ int uds_conv1d_causal(const float *x, int64_t B, int64_t T, int64_t R, int64_t F
   a.dil = (int)dil;
   a.T = (int)T;
   a.t_rows = (int)R;
-  hipError_t e = uds::launch_dense_act(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_conv1d_causal: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_conv1d_causal", uds::launch_dense_act(a, static_cast<hipStream_t>(stream)));
 }
 
 int uds_recurrent_fused(const float *x, int64_t F, const void *packed, const float *b_in, const float *b_rec, int64_t B, int64_t T, int64_t R,
@@ -343,9 +345,7 @@ int uds_recurrent_fused(const float *x, int64_t F, const void *packed, const flo
   const int64_t n_blocks = (R + 15) / 16;
   UDS_REQUIRE(B * n_blocks < INT32_MAX && T < INT32_MAX, "uds_recurrent_fused: too many rows");
   uds::RecurrentMfmaArgs a{x, b_in, b_rec, reinterpret_cast<const uint4 *>(packed), out, (int)B, (int)T, (int)R, (int)n_blocks};
-  hipError_t e = uds::launch_recurrent_mfma(a, G, (int)F, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_recurrent_fused: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_recurrent_fused", uds::launch_recurrent_mfma(a, G, (int)F, static_cast<hipStream_t>(stream)));
 }
 
 int uds_recurrent_fused_supported(int64_t F, int kind) { return uds::recurrent_mfma_supported(kind == 0 ? 3 : 4, (int)F) ? 1 : 0; }
@@ -376,26 +376,32 @@ int uds_recurrent_forward_train(const float *xp, const float *U, const float *rb
     uds::RecurrentArgs a{xp, U, rb, out, c_out, (int)B, (int)T, (int)R, (int)H, G, srows};
     e = uds::launch_recurrent_stream(a, static_cast<hipStream_t>(stream));
   }
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_recurrent_forward: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_recurrent_forward", e);
+}
+
+// uds_recurrent_backward (64 units: `width` NULL) and uds_recurrent_backward_h (*width units): one set of checks, two launchers
+static int recurrent_backward(const char *what, const int64_t *width, const float *xp, const void *packed, const float *b_rec, const float *h,
+                              const float *c, const float *gh, int64_t B, int64_t T, int64_t R, int kind, float *dxp, float *darec,
+                              uds_stream_t stream) {
+  UDS_REQUIRE(xp && packed && h && gh && dxp && darec, "%s: NULL argument", what);
+  UDS_REQUIRE(kind == 0 || kind == 1, "%s: kind %d (0 = GRU, 1 = LSTM)", what, kind);
+  UDS_REQUIRE(!width || uds::recurrent_bwd_width_ok(*width), "%s: %lld units (a multiple of 16 from 16 to 128)", what, (long long)*width);
+  UDS_REQUIRE(kind == 0 || c, "%s: the LSTM needs the cell states of the forward pass (uds_recurrent_forward_train)", what);
+  UDS_REQUIRE(B >= 0 && T >= 0 && R >= 0, "%s: bad sizes B=%lld T=%lld R=%lld", what, (long long)B, (long long)T, (long long)R);
+  UDS_REQUIRE(aligned16(xp) && aligned16(packed) && aligned16(b_rec) && aligned16(h) && aligned16(c) && aligned16(gh) && aligned16(dxp) &&
+                  aligned16(darec), "%s: buffers must be 16-byte aligned", what);
+  if (B == 0 || T == 0 || R == 0) return UDS_OK;
+  const int64_t n_blocks = (R + 15) / 16;
+  UDS_REQUIRE(B * n_blocks < INT32_MAX && T < INT32_MAX, "%s: too many rows", what);
+  uds::RecurrentBwdArgs a{xp, b_rec, reinterpret_cast<const uint4 *>(packed), h, c, gh, dxp, darec, (int)B, (int)T, (int)R, (int)n_blocks};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!width) return launched(what, kind == 0 ? uds::launch_recurrent_bwd_t<3>(a, st) : uds::launch_recurrent_bwd_t<4>(a, st));
+  return launched(what, kind == 0 ? uds::launch_recurrent_bwd_h<3>(a, (int)*width, st) : uds::launch_recurrent_bwd_h<4>(a, (int)*width, st));
 }
 
 int uds_recurrent_backward(const float *xp, const void *packed, const float *b_rec, const float *h, const float *c, const float *gh,
                            int64_t B, int64_t T, int64_t R, int kind, float *dxp, float *darec, uds_stream_t stream) {
-  UDS_REQUIRE(xp && packed && h && gh && dxp && darec, "uds_recurrent_backward: NULL argument");
-  UDS_REQUIRE(kind == 0 || kind == 1, "uds_recurrent_backward: kind %d (0 = GRU, 1 = LSTM)", kind);
-  UDS_REQUIRE(kind == 0 || c, "uds_recurrent_backward: the LSTM needs the cell states of the forward pass (uds_recurrent_forward_train)");
-  UDS_REQUIRE(B >= 0 && T >= 0 && R >= 0, "uds_recurrent_backward: bad sizes B=%lld T=%lld R=%lld", (long long)B, (long long)T, (long long)R);
-  UDS_REQUIRE(aligned16(xp) && aligned16(packed) && aligned16(b_rec) && aligned16(h) && aligned16(c) && aligned16(gh) && aligned16(dxp) &&
-                  aligned16(darec), "uds_recurrent_backward: buffers must be 16-byte aligned");
-  if (B == 0 || T == 0 || R == 0) return UDS_OK;
-  const int64_t n_blocks = (R + 15) / 16;
-  UDS_REQUIRE(B * n_blocks < INT32_MAX && T < INT32_MAX, "uds_recurrent_backward: too many rows");
-  uds::RecurrentBwdArgs a{xp, b_rec, reinterpret_cast<const uint4 *>(packed), h, c, gh, dxp, darec, (int)B, (int)T, (int)R, (int)n_blocks};
-  hipError_t e = kind == 0 ? uds::launch_recurrent_bwd_t<3>(a, static_cast<hipStream_t>(stream))
-                           : uds::launch_recurrent_bwd_t<4>(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_recurrent_backward: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return recurrent_backward("uds_recurrent_backward", nullptr, xp, packed, b_rec, h, c, gh, B, T, R, kind, dxp, darec, stream);
 }
 
 int64_t uds_recurrent_bwd_packed_bytes(int64_t H, int kind) {
@@ -410,28 +416,12 @@ int uds_recurrent_pack_bwd(const float *U, int64_t H, int kind, void *packed, ud
   const int total = (int)(bytes / 16 / 2);      // one thread per (slice, k-step, block, lane): a hi and a lo fragment
   hipLaunchKernelGGL(uds::k_pack_recurrent_bwd, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), U, (int)H,
                      kind == 0 ? 3 : 4, reinterpret_cast<uint4 *>(packed));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_recurrent_pack_bwd: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_recurrent_pack_bwd", hipGetLastError());
 }
 
 int uds_recurrent_backward_h(const float *xp, const void *packed, const float *b_rec, const float *h, const float *c, const float *gh,
                              int64_t B, int64_t T, int64_t R, int64_t H, int kind, float *dxp, float *darec, uds_stream_t stream) {
-  UDS_REQUIRE(xp && packed && h && gh && dxp && darec, "uds_recurrent_backward_h: NULL argument");
-  UDS_REQUIRE(kind == 0 || kind == 1, "uds_recurrent_backward_h: kind %d (0 = GRU, 1 = LSTM)", kind);
-  UDS_REQUIRE(uds::recurrent_bwd_width_ok(H), "uds_recurrent_backward_h: %lld units (a multiple of 16 from 16 to 128)", (long long)H);
-  UDS_REQUIRE(kind == 0 || c, "uds_recurrent_backward_h: the LSTM needs the cell states of the forward pass (uds_recurrent_forward_train)");
-  UDS_REQUIRE(B >= 0 && T >= 0 && R >= 0, "uds_recurrent_backward_h: bad sizes B=%lld T=%lld R=%lld", (long long)B, (long long)T, (long long)R);
-  UDS_REQUIRE(aligned16(xp) && aligned16(packed) && aligned16(b_rec) && aligned16(h) && aligned16(c) && aligned16(gh) && aligned16(dxp) &&
-                  aligned16(darec), "uds_recurrent_backward_h: buffers must be 16-byte aligned");
-  if (B == 0 || T == 0 || R == 0) return UDS_OK;
-  const int64_t n_blocks = (R + 15) / 16;
-  UDS_REQUIRE(B * n_blocks < INT32_MAX && T < INT32_MAX, "uds_recurrent_backward_h: too many rows");
-  uds::RecurrentBwdArgs a{xp, b_rec, reinterpret_cast<const uint4 *>(packed), h, c, gh, dxp, darec, (int)B, (int)T, (int)R, (int)n_blocks};
-  hipError_t e = kind == 0 ? uds::launch_recurrent_bwd_h<3>(a, (int)H, static_cast<hipStream_t>(stream))
-                           : uds::launch_recurrent_bwd_h<4>(a, (int)H, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_recurrent_backward_h: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return recurrent_backward("uds_recurrent_backward_h", &H, xp, packed, b_rec, h, c, gh, B, T, R, kind, dxp, darec, stream);
 }
 
 int64_t uds_rowgemm_packed_bytes(int64_t k_total, int64_t f_out) {
@@ -447,9 +437,7 @@ int uds_rowgemm_pack(const float *W, int64_t k_total, int64_t f_out, void *packe
   const int total = (int)(k_total / 32) * mb * 64;
   hipLaunchKernelGGL(uds::k_pack_weight_frags_padded, dim3((total + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), W,
                      (int)k_total, (int)f_out, mb, reinterpret_cast<uint4 *>(packed));
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_rowgemm_pack: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_rowgemm_pack", hipGetLastError());
 }
 
 static int64_t pad_k(int64_t k) { return (k + 63) / 64 * 64; }      // the remainder GEMM's k-step
@@ -468,9 +456,7 @@ int uds_remainder_pack(const float *rest, int64_t R, int64_t M, void *packed, ud
   __bf16 *hi = reinterpret_cast<__bf16 *>(packed), *lo = hi + R * Kp;
   hipLaunchKernelGGL(uds::k_split_rows_bf16, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), rest, R, M,
                      Kp, hi, lo);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_remainder_pack: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_remainder_pack", hipGetLastError());
 }
 
 namespace {
@@ -547,17 +533,14 @@ int remainder_gemm_from_planes(const void *packed, int64_t R, int64_t Kp, int64_
     if (t_rest)
       hipLaunchKernelGGL((uds::k_remainder_gemm2_reduce<2, M32>), dim3((unsigned)t_rest), dim3(512), 0, st, partial, (int)ks, (int)t_main, Nc, R, (int)h,
                          (int)n_ctile, out);
-    if ((e = hipGetLastError()) != hipSuccess) return fail(UDS_EHIP, "uds_remainder_forward: launch -> %s", hipGetErrorString(e));
-    return UDS_OK;
+    return launched("uds_remainder_forward", hipGetLastError());
   }
   {
     const int64_t n_ctile = (Nc + 127) / 128, n_rtile = (R + 127) / 128;
     hipLaunchKernelGGL(uds::k_remainder_gemm, dim3((unsigned)(n_ctile * n_rtile)), dim3(256), 0, st, xh, xl, wh, wl, Nc, R, Kp, (int)h,
                        (int)n_ctile, out);
   }
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_remainder_forward: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_remainder_forward", hipGetLastError());
 }
 }  // namespace
 
@@ -597,7 +580,7 @@ int uds_remainder_forward_dense(const void *packed, int64_t R, int64_t M, const 
     hipLaunchKernelGGL(uds::k_dense_split_planes<2>, grid, dim3(256), 0, st, e, M, (int)h, Kp, reinterpret_cast<const uint4 *>(packed_w), bias, act, xh, xl);
   else
     hipLaunchKernelGGL(uds::k_dense_split_planes<4>, grid, dim3(256), 0, st, e, M, (int)h, Kp, reinterpret_cast<const uint4 *>(packed_w), bias, act, xh, xl);
-  if (hipError_t er = hipGetLastError(); er != hipSuccess) return fail(UDS_EHIP, "uds_remainder_forward_dense: launch -> %s", hipGetErrorString(er));
+  if (int rc = launched("uds_remainder_forward_dense", hipGetLastError())) return rc;
   return remainder_gemm_from_planes(packed, R, Kp, Nc, h, workspace, out, st);
 }
 
@@ -637,9 +620,7 @@ int uds_rowgemm_forward_cat(const float *x, int64_t F1, const float *x2, int64_t
   }
   uds::RowGemmArgs a{x, bias, reinterpret_cast<const uint4 *>(packed), out, B * T * R, (int)F, (int)taps, (int)dil, (int)T, (int)R,
                      (int)f_out, act, 0, x2, (int)F1, (int)ldo, (int)col0};
-  hipError_t e = uds::launch_rowgemm(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_rowgemm_forward: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_rowgemm_forward", uds::launch_rowgemm(a, static_cast<hipStream_t>(stream)));
 }
 
 int uds_rowgemm_forward_pair(const float *x0, int64_t R0, const void *packed0, const float *bias0, float *out0, const float *x1, int64_t R1,
@@ -668,41 +649,31 @@ int uds_rowgemm_forward_pair(const float *x0, int64_t R0, const void *packed0, c
     if (rc != UDS_OK) return rc;
     return uds_rowgemm_forward(x1, B, T, R1, F, packed1, bias1, taps, dil, f_out, act, out1, stream);
   }
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_rowgemm_forward_pair: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_rowgemm_forward_pair", e);
 }
 
-int uds_dense_cumsum(const float *x, int64_t B, int64_t T, int64_t R, const void *packed, const float *bias, const float *res, int act,
-                     float *out, uds_stream_t stream) {
-  UDS_REQUIRE(x && packed && out, "uds_dense_cumsum: NULL x/packed/out");
-  UDS_REQUIRE(B >= 0 && T > 0 && R > 0, "uds_dense_cumsum: bad sizes B=%lld T=%lld R=%lld", (long long)B, (long long)T, (long long)R);
-  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "uds_dense_cumsum: unknown activation %d", act);
-  UDS_REQUIRE(aligned16(x) && aligned16(packed) && aligned16(out) && aligned16(bias) && aligned16(res),
-              "uds_dense_cumsum: pointers must be 16-byte aligned");
-  UDS_REQUIRE(B * T * R < INT32_MAX, "uds_dense_cumsum: %lld rows exceed the int32 row index", (long long)(B * T * R));
+// uds_dense_cumsum and uds_dense_cumsum_heads (with_heads): the same checks around those of the heads, one DenseCumsumArgs
+static int dense_cumsum(const char *what, bool with_heads, const float *x, int64_t B, int64_t T, int64_t R, const void *packed, const float *bias,
+                        const float *res, int act, const uds_heads_t *heads, float *out, uds_stream_t stream) {
+  UDS_REQUIRE(x && packed && out && (!with_heads || heads), "%s: NULL x/packed/%sout", what, with_heads ? "heads/" : "");
+  UDS_REQUIRE(B >= 0 && T > 0 && R > 0, "%s: bad sizes B=%lld T=%lld R=%lld", what, (long long)B, (long long)T, (long long)R);
+  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "%s: unknown activation %d", what, act);
+  if (with_heads) {
+    UDS_REQUIRE(heads->a_packed && heads->n_a >= 1 && heads->n_a <= 4, "%s: first head needs 1..4 outputs (got %d)", what, heads->n_a);
+    UDS_REQUIRE(heads->n_hidden >= 0 && heads->n_hidden <= 5, "%s: 0..5 hidden layers in the second head (got %d)", what, heads->n_hidden);
+    for (int i = 0; i < heads->n_hidden; ++i) UDS_REQUIRE(heads->h_packed[i], "%s: hidden layer %d has no weights", what, i);
+    UDS_REQUIRE(heads->n_hidden == 0 || heads->f_packed, "%s: the second head has no output layer", what);
+    for (int v : {heads->act_a, heads->act_h, heads->act_f})
+      UDS_REQUIRE(v >= UDS_ACT_LINEAR && v <= UDS_ACT_HARD_SIGMOID, "%s: unknown head activation %d", what, v);
+  }
+  // with heads, `out` holds rows of n_a (+ 1) floats and its alignment is not asked for; the heads' packed weights are
+  UDS_REQUIRE(aligned16(x) && aligned16(packed) && aligned16(bias) && aligned16(res) &&
+                  (with_heads ? aligned16(heads->a_packed) && aligned16(heads->f_packed) : aligned16(out)),
+              "%s: pointers must be 16-byte aligned", what);
+  UDS_REQUIRE(B * T * R < INT32_MAX, "%s: %lld rows exceed the int32 row index", what, (long long)(B * T * R));
   if (B == 0) return UDS_OK;
   uds::DenseCumsumArgs a{x, bias, res, reinterpret_cast<const uint4 *>(packed), out, (int)B, (int)T, (int)R, act, (int)((R + 15) / 16)};
-  hipError_t e = uds::launch_dense_cumsum(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_dense_cumsum: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
-}
-
-int uds_dense_cumsum_heads(const float *x, int64_t B, int64_t T, int64_t R, const void *packed, const float *bias, const float *res, int act,
-                           const uds_heads_t *heads, float *out, uds_stream_t stream) {
-  UDS_REQUIRE(x && packed && out && heads, "uds_dense_cumsum_heads: NULL x/packed/heads/out");
-  UDS_REQUIRE(B >= 0 && T > 0 && R > 0, "uds_dense_cumsum_heads: bad sizes B=%lld T=%lld R=%lld", (long long)B, (long long)T, (long long)R);
-  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "uds_dense_cumsum_heads: unknown activation %d", act);
-  UDS_REQUIRE(heads->a_packed && heads->n_a >= 1 && heads->n_a <= 4, "uds_dense_cumsum_heads: first head needs 1..4 outputs (got %d)", heads->n_a);
-  UDS_REQUIRE(heads->n_hidden >= 0 && heads->n_hidden <= 5, "uds_dense_cumsum_heads: 0..5 hidden layers in the second head (got %d)", heads->n_hidden);
-  for (int i = 0; i < heads->n_hidden; ++i) UDS_REQUIRE(heads->h_packed[i], "uds_dense_cumsum_heads: hidden layer %d has no weights", i);
-  UDS_REQUIRE(heads->n_hidden == 0 || heads->f_packed, "uds_dense_cumsum_heads: the second head has no output layer");
-  for (int v : {heads->act_a, heads->act_h, heads->act_f})
-    UDS_REQUIRE(v >= UDS_ACT_LINEAR && v <= UDS_ACT_HARD_SIGMOID, "uds_dense_cumsum_heads: unknown head activation %d", v);
-  UDS_REQUIRE(aligned16(x) && aligned16(packed) && aligned16(bias) && aligned16(res) && aligned16(heads->a_packed) && aligned16(heads->f_packed),
-              "uds_dense_cumsum_heads: pointers must be 16-byte aligned");
-  UDS_REQUIRE(B * T * R < INT32_MAX, "uds_dense_cumsum_heads: %lld rows exceed the int32 row index", (long long)(B * T * R));
-  if (B == 0) return UDS_OK;
-  uds::DenseCumsumArgs a{x, bias, res, reinterpret_cast<const uint4 *>(packed), out, (int)B, (int)T, (int)R, act, (int)((R + 15) / 16)};
+  if (!with_heads) return launched(what, uds::launch_dense_cumsum(a, static_cast<hipStream_t>(stream)));
   uds::HeadsArgs hd{};
   hd.a_packed = reinterpret_cast<const uint4 *>(heads->a_packed);
   hd.a_bias = heads->a_bias;
@@ -713,9 +684,17 @@ int uds_dense_cumsum_heads(const float *x, int64_t B, int64_t T, int64_t R, cons
   hd.f_packed = reinterpret_cast<const uint4 *>(heads->f_packed);
   hd.f_bias = heads->f_bias;
   hd.n_a = heads->n_a, hd.act_a = heads->act_a, hd.n_hidden = heads->n_hidden, hd.act_h = heads->act_h, hd.act_f = heads->act_f;
-  hipError_t e = uds::launch_dense_cumsum_heads(a, hd, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_dense_cumsum_heads: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched(what, uds::launch_dense_cumsum_heads(a, hd, static_cast<hipStream_t>(stream)));
+}
+
+int uds_dense_cumsum(const float *x, int64_t B, int64_t T, int64_t R, const void *packed, const float *bias, const float *res, int act,
+                     float *out, uds_stream_t stream) {
+  return dense_cumsum("uds_dense_cumsum", false, x, B, T, R, packed, bias, res, act, nullptr, out, stream);
+}
+
+int uds_dense_cumsum_heads(const float *x, int64_t B, int64_t T, int64_t R, const void *packed, const float *bias, const float *res, int act,
+                           const uds_heads_t *heads, float *out, uds_stream_t stream) {
+  return dense_cumsum("uds_dense_cumsum_heads", true, x, B, T, R, packed, bias, res, act, heads, out, stream);
 }
 
 int uds_cumsum_act(const float *x, const float *res, int64_t B, int64_t T, int64_t R, int64_t F, int act, float *out,
@@ -726,9 +705,7 @@ int uds_cumsum_act(const float *x, const float *res, int64_t B, int64_t T, int64
   UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "uds_cumsum_act: unknown activation %d", act);
   if (B == 0) return UDS_OK;
   uds::CumsumArgs a{x, res, out, (int)B, (int)T, (int)R, (int)(F / 4), act};
-  hipError_t e = uds::launch_cumsum(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_cumsum_act: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_cumsum_act", uds::launch_cumsum(a, static_cast<hipStream_t>(stream)));
 }
 
 int uds_attn_sum_pool(const float *x, const float *k, int64_t B, int64_t R, int64_t F, float *out, uds_stream_t stream) {
@@ -740,9 +717,7 @@ int uds_attn_sum_pool(const float *x, const float *k, int64_t B, int64_t R, int6
   if (B == 0) return UDS_OK;
   uds::AttnPoolArgs a{x, k, out, (int)R, (int)(F / 4)};
   hipLaunchKernelGGL(uds::k_attn_sum_pool, dim3((unsigned)B), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_attn_sum_pool: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_attn_sum_pool", hipGetLastError());
 }
 
 int uds_attn_sum_pool_pair(const float *x, int64_t Rx, const float *e, int64_t Re, const float *k, int64_t B, int64_t F, float *out, float *stat,
@@ -755,9 +730,7 @@ int uds_attn_sum_pool_pair(const float *x, int64_t Rx, const float *e, int64_t R
   if (B == 0) return UDS_OK;
   uds::AttnPoolPairArgs a{x, Re ? e : nullptr, k, out, stat, (int)Rx, (int)Re, (int)(F / 4)};
   hipLaunchKernelGGL(uds::k_attn_sum_pool_pair, dim3((unsigned)B), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail(UDS_EHIP, "uds_attn_sum_pool_pair: launch -> %s", hipGetErrorString(err));
-  return UDS_OK;
+  return launched("uds_attn_sum_pool_pair", hipGetLastError());
 }
 
 int uds_attn_sum_pool_backward(const float *x, int64_t Rx, const float *e, int64_t Re, const float *k, const float *out, const float *stat,
@@ -778,8 +751,7 @@ int uds_attn_sum_pool_backward(const float *x, int64_t Rx, const float *e, int64
   if (B > 0) {
     uds::AttnPoolBwdArgs a{x, Re ? e : nullptr, k, out, stat, grad, dx, de, dk ? dk_ws : nullptr, (int)Rx, (int)Re, f4};
     hipLaunchKernelGGL(uds::k_attn_sum_pool_bwd, dim3((unsigned)B), dim3(256), 0, st, a);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return fail(UDS_EHIP, "uds_attn_sum_pool_backward: launch -> %s", hipGetErrorString(err));
+    if (int rc = launched("uds_attn_sum_pool_backward", hipGetLastError())) return rc;
   }
   if (dk) {                                           // B = 0: the sum over no samples, zeros
     const int cw = std::min(f4, 16);
@@ -800,9 +772,7 @@ int uds_dropout(const float *x, int64_t n, float rate, uint64_t seed, uint64_t o
   uds::DropoutArgs a{x, out, n, (unsigned long long)seed, (unsigned long long)offset,
                      (unsigned)std::min<double>(4294967295.0, std::ceil((double)rate * 4294967296.0)), 1.0f / (1.0f - rate)};
   hipLaunchKernelGGL(uds::k_dropout, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_dropout: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_dropout", hipGetLastError());
 }
 
 int uds_flow_balance(const uds_csr_t *inc_n, const float *sign, const float *flow, int64_t S, const float *scale_in,
@@ -812,9 +782,7 @@ int uds_flow_balance(const uds_csr_t *inc_n, const float *sign, const float *flo
   if (S == 0 || inc_n->n_rows == 0) return UDS_OK;
   uds::FlowArgs a{inc_n->d_rowptr, inc_n->d_col, sign, flow, scale_in, scale_out, q_in, q_out, (int)inc_n->n_rows,
                   (int)inc_n->n_cols, (int)S};
-  hipError_t e = uds::launch_flow_balance(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_flow_balance: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_flow_balance", uds::launch_flow_balance(a, static_cast<hipStream_t>(stream)));
 }
 
 int uds_diffusion_forward(const uds_csr_t *csr, const float *vals, const float *c0, const float *r, const float *tot, int64_t S, int64_t C,
@@ -826,9 +794,7 @@ int uds_diffusion_forward(const uds_csr_t *csr, const float *vals, const float *
   UDS_REQUIRE(aligned16(vals) && aligned16(c0) && aligned16(out), "uds_diffusion_forward: vals / c0 / out must be 16-byte aligned");
   if (S == 0 || csr->n_rows == 0) return UDS_OK;
   uds::DiffusionArgs a{csr->d_rowptr, csr->d_col, vals, c0, r, tot, out, (int)csr->n_rows, (int)csr->n_cols, (int)(C / 4), act};
-  hipError_t e = uds::launch_diffusion(a, (int)S, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_diffusion_forward: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_diffusion_forward", uds::launch_diffusion(a, (int)S, static_cast<hipStream_t>(stream)));
 }
 
 int64_t uds_diffusion_backward_workspace_floats(int64_t n_rows, int64_t S, int64_t C, int64_t K1) {
@@ -836,16 +802,24 @@ int64_t uds_diffusion_backward_workspace_floats(int64_t n_rows, int64_t S, int64
   return uds::diffusion_bwd_plan(n_rows, S, C, K1).total;
 }
 
-int uds_diffusion_backward(const uds_csr_t *csr, const uds_csr_t *csr_t, const int32_t *perm_t, const float *a, const float *vals,
-                           const float *c0, const float *r, const float *tot, const float *y, const float *gy, int64_t S, int64_t C,
-                           int64_t K1, int act, float *workspace, float *dr, float *dtheta, uds_stream_t stream) {
-  UDS_REQUIRE(csr && csr_t && c0 && dtheta, "uds_diffusion_backward: NULL argument");
+// The S / C / K1 ranges and the activation of the Diffusion entries that take the layer's (C, K1) kernel
+static int diffusion_check_ranges(const char *what, int64_t S, int64_t C, int64_t K1, int act) {
   UDS_REQUIRE(S >= 0 && S <= 65535 && C > 0 && C % 4 == 0 && C <= 256 && K1 >= 1 && K1 <= uds::DIFF_KMAX,
-              "uds_diffusion_backward: S=%lld C=%lld K1=%lld (needs S <= 65535, C %% 4 == 0, C <= 256, 1 <= K1 <= %d)", (long long)S,
-              (long long)C, (long long)K1, uds::DIFF_KMAX);
-  UDS_REQUIRE(act >= 0 && act <= 4, "uds_diffusion_backward: unknown activation %d", act);
+              "%s: S=%lld C=%lld K1=%lld (needs S <= 65535, C %% 4 == 0, C <= 256, 1 <= K1 <= %d)", what, (long long)S, (long long)C,
+              (long long)K1, uds::DIFF_KMAX);
+  UDS_REQUIRE(act >= 0 && act <= 4, "%s: unknown activation %d", what, act);
+  return UDS_OK;
+}
+
+// uds_diffusion_backward (table: the (nnz, C) table `vals` and c0 (C,)) and uds_diffusion_backward_m (theta (C, K1) alone)
+static int diffusion_backward(const char *what, bool table, const uds_csr_t *csr, const uds_csr_t *csr_t, const int32_t *perm_t, const float *a,
+                              const float *vals, const float *c0, const float *theta, const float *r, const float *tot, const float *y,
+                              const float *gy, int64_t S, int64_t C, int64_t K1, int act, float *workspace, float *dr, float *dtheta,
+                              uds_stream_t stream) {
+  UDS_REQUIRE(csr && csr_t && (table ? c0 : theta) && dtheta, "%s: NULL argument", what);
+  if (int rc = diffusion_check_ranges(what, S, C, K1, act)) return rc;
   UDS_REQUIRE(csr_t->n_rows == csr->n_cols && csr_t->n_cols == csr->n_rows && csr_t->nnz == csr->nnz,
-              "uds_diffusion_backward: csr_t (%lld x %lld, %lld entries) is not the transpose of a %lld x %lld pattern with %lld entries",
+              "%s: csr_t (%lld x %lld, %lld entries) is not the transpose of a %lld x %lld pattern with %lld entries", what,
               (long long)csr_t->n_rows, (long long)csr_t->n_cols, (long long)csr_t->nnz, (long long)csr->n_rows, (long long)csr->n_cols,
               (long long)csr->nnz);
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -853,34 +827,37 @@ int uds_diffusion_backward(const uds_csr_t *csr, const uds_csr_t *csr_t, const i
     UDS_HIP_TRY(hipMemsetAsync(dtheta, 0, sizeof(float) * C * K1, st));
     return UDS_OK;
   }
-  UDS_REQUIRE(r && tot && workspace && dr && (csr->nnz == 0 || (perm_t && a && vals)) && (csr->n_rows == 0 || (y && gy)),
-              "uds_diffusion_backward: NULL argument");
-  UDS_REQUIRE(aligned16(vals) && aligned16(c0) && aligned16(y) && aligned16(gy) && aligned16(workspace),
-              "uds_diffusion_backward: vals / c0 / y / gy / workspace must be 16-byte aligned");
+  UDS_REQUIRE(r && tot && workspace && dr && (csr->nnz == 0 || (perm_t && a && (!table || vals))) && (csr->n_rows == 0 || (y && gy)),
+              "%s: NULL argument", what);
+  UDS_REQUIRE((table ? aligned16(vals) && aligned16(c0) : aligned16(theta)) && aligned16(y) && aligned16(gy) && aligned16(workspace),
+              "%s: %s / y / gy / workspace must be 16-byte aligned", what, table ? "vals / c0" : "theta");
   const uds::DiffusionBwdPlan p = uds::diffusion_bwd_plan(csr->n_rows, S, C, K1);
-  uds::DiffusionBwdArgs args{csr->d_rowptr, csr->d_col, csr_t->d_rowptr, csr_t->d_col, perm_t, a, vals, c0, r, tot, y, gy,
+  uds::DiffusionBwdArgs args{csr->d_rowptr, csr->d_col, csr_t->d_rowptr, csr_t->d_col, perm_t, a, table ? vals : nullptr,
+                             table ? c0 : theta + (K1 - 1), r, tot, y, gy,
                              workspace, workspace + p.off_pth, workspace + p.off_pg, workspace + p.off_g0, dr, dtheta,
                              (int)csr->n_rows, (int)csr->n_cols, (int)S, (int)(C / 4), p.lr, (int)K1, act, p.gx, p.sy};
-  hipError_t e = uds::launch_diffusion_backward(args, st);
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_diffusion_backward: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  if (table) return launched(what, uds::launch_diffusion_backward(args, st));
+  args.c0s = (int)K1;      // c0 = the last column of theta; G goes behind the table entry's carve
+  return launched(what, uds::launch_diffusion_backward_m(uds::DiffusionBwdMArgs{args, theta, workspace + p.total}, st));
+}
+
+int uds_diffusion_backward(const uds_csr_t *csr, const uds_csr_t *csr_t, const int32_t *perm_t, const float *a, const float *vals,
+                           const float *c0, const float *r, const float *tot, const float *y, const float *gy, int64_t S, int64_t C,
+                           int64_t K1, int act, float *workspace, float *dr, float *dtheta, uds_stream_t stream) {
+  return diffusion_backward("uds_diffusion_backward", true, csr, csr_t, perm_t, a, vals, c0, nullptr, r, tot, y, gy, S, C, K1, act, workspace, dr,
+                            dtheta, stream);
 }
 
 int uds_diffusion_forward_m(const uds_csr_t *csr, const float *a, const float *theta, const float *r, const float *tot, int64_t S, int64_t C,
                             int64_t K1, int act, float *out, uds_stream_t stream) {
   UDS_REQUIRE(csr && theta && r && tot && out && (csr->nnz == 0 || a), "uds_diffusion_forward_m: NULL argument");
-  UDS_REQUIRE(S >= 0 && S <= 65535 && C > 0 && C % 4 == 0 && C <= 256 && K1 >= 1 && K1 <= uds::DIFF_KMAX,
-              "uds_diffusion_forward_m: S=%lld C=%lld K1=%lld (needs S <= 65535, C %% 4 == 0, C <= 256, 1 <= K1 <= %d)", (long long)S,
-              (long long)C, (long long)K1, uds::DIFF_KMAX);
-  UDS_REQUIRE(act >= 0 && act <= 4, "uds_diffusion_forward_m: unknown activation %d", act);
+  if (int rc = diffusion_check_ranges("uds_diffusion_forward_m", S, C, K1, act)) return rc;
   UDS_REQUIRE(aligned16(theta) && aligned16(out), "uds_diffusion_forward_m: theta / out must be 16-byte aligned");
   if (S == 0 || csr->n_rows == 0) return UDS_OK;
   int lr = 1;
   while (lr < C / 4) lr <<= 1;
   uds::DiffusionMArgs args{csr->d_rowptr, csr->d_col, a, theta, r, tot, out, (int)csr->n_rows, (int)csr->n_cols, (int)(C / 4), lr, (int)K1, act, 0};
-  hipError_t e = uds::launch_diffusion_m(args, (int)S, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_diffusion_forward_m: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_diffusion_forward_m", uds::launch_diffusion_m(args, (int)S, static_cast<hipStream_t>(stream)));
 }
 
 static int64_t up4f(int64_t f) { return (f + 3) & ~int64_t(3); }
@@ -893,32 +870,8 @@ int64_t uds_diffusion_backward_m_workspace_floats(int64_t n_rows, int64_t S, int
 int uds_diffusion_backward_m(const uds_csr_t *csr, const uds_csr_t *csr_t, const int32_t *perm_t, const float *a, const float *theta,
                              const float *r, const float *tot, const float *y, const float *gy, int64_t S, int64_t C, int64_t K1, int act,
                              float *workspace, float *dr, float *dtheta, uds_stream_t stream) {
-  UDS_REQUIRE(csr && csr_t && theta && dtheta, "uds_diffusion_backward_m: NULL argument");
-  UDS_REQUIRE(S >= 0 && S <= 65535 && C > 0 && C % 4 == 0 && C <= 256 && K1 >= 1 && K1 <= uds::DIFF_KMAX,
-              "uds_diffusion_backward_m: S=%lld C=%lld K1=%lld (needs S <= 65535, C %% 4 == 0, C <= 256, 1 <= K1 <= %d)", (long long)S,
-              (long long)C, (long long)K1, uds::DIFF_KMAX);
-  UDS_REQUIRE(act >= 0 && act <= 4, "uds_diffusion_backward_m: unknown activation %d", act);
-  UDS_REQUIRE(csr_t->n_rows == csr->n_cols && csr_t->n_cols == csr->n_rows && csr_t->nnz == csr->nnz,
-              "uds_diffusion_backward_m: csr_t (%lld x %lld, %lld entries) is not the transpose of a %lld x %lld pattern with %lld entries",
-              (long long)csr_t->n_rows, (long long)csr_t->n_cols, (long long)csr_t->nnz, (long long)csr->n_rows, (long long)csr->n_cols,
-              (long long)csr->nnz);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  if (S == 0 || csr->n_cols == 0) {           // no dr to write; dtheta = 0 (no snapshot, or no column to sum over)
-    UDS_HIP_TRY(hipMemsetAsync(dtheta, 0, sizeof(float) * C * K1, st));
-    return UDS_OK;
-  }
-  UDS_REQUIRE(r && tot && workspace && dr && (csr->nnz == 0 || (perm_t && a)) && (csr->n_rows == 0 || (y && gy)),
-              "uds_diffusion_backward_m: NULL argument");
-  UDS_REQUIRE(aligned16(theta) && aligned16(y) && aligned16(gy) && aligned16(workspace),
-              "uds_diffusion_backward_m: theta / y / gy / workspace must be 16-byte aligned");
-  const uds::DiffusionBwdPlan p = uds::diffusion_bwd_plan(csr->n_rows, S, C, K1);
-  uds::DiffusionBwdMArgs args{{csr->d_rowptr, csr->d_col, csr_t->d_rowptr, csr_t->d_col, perm_t, a, nullptr, theta + (K1 - 1), r, tot, y, gy,
-                               workspace, workspace + p.off_pth, workspace + p.off_pg, workspace + p.off_g0, dr, dtheta,
-                               (int)csr->n_rows, (int)csr->n_cols, (int)S, (int)(C / 4), p.lr, (int)K1, act, p.gx, p.sy, (int)K1},
-                              theta, workspace + p.total};
-  hipError_t e = uds::launch_diffusion_backward_m(args, st);
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_diffusion_backward_m: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return diffusion_backward("uds_diffusion_backward_m", false, csr, csr_t, perm_t, a, nullptr, nullptr, theta, r, tot, y, gy, S, C, K1, act,
+                            workspace, dr, dtheta, stream);
 }
 
 static int halo_rows(const char *what, bool pack, float *x, int64_t n_x, float *e, int64_t n_e, int64_t S, int64_t F, const int32_t *idx_x,
@@ -930,9 +883,7 @@ static int halo_rows(const char *what, bool pack, float *x, int64_t n_x, float *
   UDS_REQUIRE(aligned16(buf) && aligned16(x) && aligned16(e), "%s: buffers must be 16-byte aligned", what);
   UDS_REQUIRE(nx + ne < INT32_MAX && S * (nx + ne) * (F / 4) < (int64_t)INT32_MAX * 256, "%s: message too large", what);
   uds::HaloArgs a{x, e, buf, idx_x, idx_e, n_x, n_e, S * (nx + ne) * (F / 4), (int)nx, (int)ne, (int)(F / 4)};
-  hipError_t err = uds::launch_halo_rows(a, pack, static_cast<hipStream_t>(stream));
-  if (err != hipSuccess) return fail(UDS_EHIP, "%s: launch -> %s", what, hipGetErrorString(err));
-  return UDS_OK;
+  return launched(what, uds::launch_halo_rows(a, pack, static_cast<hipStream_t>(stream)));
 }
 
 int uds_halo_pack(const float *x, int64_t n_x, const float *e, int64_t n_e, int64_t S, int64_t F, const int32_t *idx_x, int64_t nx,
@@ -945,7 +896,9 @@ int uds_halo_unpack(const float *buf, int64_t S, int64_t F, const int32_t *idx_x
   return halo_rows("uds_halo_unpack", false, x, n_x, e, n_e, S, F, idx_x, nx, idx_e, ne, const_cast<float *>(buf), stream);
 }
 
-static int halo_rows_all(const char *what, bool pack, float *x, int64_t n_x, float *e, int64_t n_e, int64_t S, int64_t F,
+enum HaloAllOp { HALO_UNPACK, HALO_PACK, HALO_PACK_CLEAR };
+
+static int halo_rows_all(const char *what, HaloAllOp op, float *x, int64_t n_x, float *e, int64_t n_e, int64_t S, int64_t F,
                          const int32_t *idx_x, int64_t nx, const int32_t *idx_e, int64_t ne, const int32_t *off_x, const int32_t *off_e,
                          int64_t P, float *buf, uds_stream_t stream) {
   UDS_REQUIRE(S >= 0 && S <= 65535 && nx >= 0 && ne >= 0 && n_x >= 0 && n_e >= 0 && F >= 1 && P >= 1,
@@ -956,40 +909,29 @@ static int halo_rows_all(const char *what, bool pack, float *x, int64_t n_x, flo
   UDS_REQUIRE(nx + ne < INT32_MAX && P < INT32_MAX && F < INT32_MAX && (nx + ne) * F < (int64_t)INT32_MAX * 256, "%s: messages too large", what);
   const bool vec = F % 4 == 0 && aligned16(buf) && aligned16(x) && aligned16(e);
   uds::HaloAllArgs a{x, e, buf, idx_x, idx_e, off_x, off_e, n_x, n_e, (int)(nx + ne), (int)P, (int)F, (int)(vec ? F / 4 : F)};
-  hipError_t err = uds::launch_halo_rows_all(a, (int)S, pack, vec, static_cast<hipStream_t>(stream));
-  if (err != hipSuccess) return fail(UDS_EHIP, "%s: launch -> %s", what, hipGetErrorString(err));
-  return UDS_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (op == HALO_PACK_CLEAR) return launched(what, uds::launch_halo_pack_clear_all(a, (int)S, vec, st));
+  return launched(what, uds::launch_halo_rows_all(a, (int)S, op == HALO_PACK, vec, st));
 }
 
 int uds_halo_pack_all(const float *x, int64_t n_x, const float *e, int64_t n_e, int64_t S, int64_t F, const int32_t *idx_x, int64_t nx,
                       const int32_t *idx_e, int64_t ne, const int32_t *off_x, const int32_t *off_e, int64_t P, float *buf,
                       uds_stream_t stream) {
-  return halo_rows_all("uds_halo_pack_all", true, const_cast<float *>(x), n_x, const_cast<float *>(e), n_e, S, F, idx_x, nx, idx_e, ne, off_x,
+  return halo_rows_all("uds_halo_pack_all", HALO_PACK, const_cast<float *>(x), n_x, const_cast<float *>(e), n_e, S, F, idx_x, nx, idx_e, ne, off_x,
                        off_e, P, buf, stream);
 }
 
 int uds_halo_unpack_all(const float *buf, int64_t S, int64_t F, const int32_t *idx_x, int64_t nx, const int32_t *idx_e, int64_t ne,
                         const int32_t *off_x, const int32_t *off_e, int64_t P, float *x, int64_t n_x, float *e, int64_t n_e,
                         uds_stream_t stream) {
-  return halo_rows_all("uds_halo_unpack_all", false, x, n_x, e, n_e, S, F, idx_x, nx, idx_e, ne, off_x, off_e, P, const_cast<float *>(buf),
+  return halo_rows_all("uds_halo_unpack_all", HALO_UNPACK, x, n_x, e, n_e, S, F, idx_x, nx, idx_e, ne, off_x, off_e, P, const_cast<float *>(buf),
                        stream);
 }
 
 int uds_halo_pack_clear_all(float *x, int64_t n_x, float *e, int64_t n_e, int64_t S, int64_t F, const int32_t *idx_x, int64_t nx,
                             const int32_t *idx_e, int64_t ne, const int32_t *off_x, const int32_t *off_e, int64_t P, float *buf,
                             uds_stream_t stream) {
-  const char *what = "uds_halo_pack_clear_all";
-  UDS_REQUIRE(S >= 0 && S <= 65535 && nx >= 0 && ne >= 0 && n_x >= 0 && n_e >= 0 && F >= 1 && P >= 1,
-              "%s: bad sizes (S=%lld nx=%lld ne=%lld F=%lld P=%lld; needs S <= 65535, F >= 1, P >= 1)", what, (long long)S, (long long)nx,
-              (long long)ne, (long long)F, (long long)P);
-  if (S == 0 || nx + ne == 0) return UDS_OK;
-  UDS_REQUIRE(buf && off_x && off_e && (nx == 0 || (x && idx_x)) && (ne == 0 || (e && idx_e)), "%s: NULL argument", what);
-  UDS_REQUIRE(nx + ne < INT32_MAX && P < INT32_MAX && F < INT32_MAX && (nx + ne) * F < (int64_t)INT32_MAX * 256, "%s: messages too large", what);
-  const bool vec = F % 4 == 0 && aligned16(buf) && aligned16(x) && aligned16(e);
-  uds::HaloAllArgs a{x, e, buf, idx_x, idx_e, off_x, off_e, n_x, n_e, (int)(nx + ne), (int)P, (int)F, (int)(vec ? F / 4 : F)};
-  hipError_t err = uds::launch_halo_pack_clear_all(a, (int)S, vec, static_cast<hipStream_t>(stream));
-  if (err != hipSuccess) return fail(UDS_EHIP, "%s: launch -> %s", what, hipGetErrorString(err));
-  return UDS_OK;
+  return halo_rows_all("uds_halo_pack_clear_all", HALO_PACK_CLEAR, x, n_x, e, n_e, S, F, idx_x, nx, idx_e, ne, off_x, off_e, P, buf, stream);
 }
 
 int uds_halo_accumulate_all(const float *buf, int64_t S, int64_t F, const int32_t *off_x, const int32_t *off_e, int64_t P,
@@ -1006,9 +948,7 @@ int uds_halo_accumulate_all(const float *buf, int64_t S, int64_t F, const int32_
               "%s: too many rows", what);
   const bool vec = F % 4 == 0 && aligned16(buf) && aligned16(x) && aligned16(e);
   uds::HaloAccArgs a{buf, x, e, off_x, off_e, tgt_x, tgt_e, ptr, src, n_x, n_e, (int)tx, (int)(tx + te), (int)P, (int)F, (int)(vec ? F / 4 : F)};
-  hipError_t err = uds::launch_halo_accumulate_all(a, (int)S, vec, static_cast<hipStream_t>(stream));
-  if (err != hipSuccess) return fail(UDS_EHIP, "%s: launch -> %s", what, hipGetErrorString(err));
-  return UDS_OK;
+  return launched(what, uds::launch_halo_accumulate_all(a, (int)S, vec, static_cast<hipStream_t>(stream)));
 }
 
 int uds_roll_update(const uds_csr_t *inc_n, const float *sign, const float *span_e, const float *mini_e, const float *scale_in,
@@ -1021,9 +961,7 @@ int uds_roll_update(const uds_csr_t *inc_n, const float *sign, const float *span
   if (B == 0) return UDS_OK;
   uds::RollArgs a{inc_n->d_rowptr, inc_n->d_col, sign, span_e, mini_e, scale_in, scale_out, y, ey, b, x, ex, preds,
                   (int)B, (int)so, (int)T, (int)inc_n->n_rows, (int)inc_n->n_cols, (int)cy, (int)ce, flood};
-  hipError_t e = uds::launch_roll_update(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_roll_update: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_roll_update", uds::launch_roll_update(a, static_cast<hipStream_t>(stream)));
 }
 
 int uds_csr_spmm(const uds_csr_t *csr, const float *val, const float *x, int64_t S, int64_t F, const float *bias,
@@ -1037,12 +975,64 @@ int uds_csr_spmm(const uds_csr_t *csr, const float *val, const float *x, int64_t
   if (S == 0 || csr->n_rows == 0) return UDS_OK;
   uds::SpmmArgs a{csr->d_rowptr, csr->d_col, csr->d_order, val, x, bias, out,
                   (int)csr->n_rows, (int)csr->n_cols, (int)(F / 4), act, (int)S};
-  hipError_t e = uds::launch_csr_spmm(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_csr_spmm: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_csr_spmm", uds::launch_csr_spmm(a, static_cast<hipStream_t>(stream)));
 }
 
 int64_t uds_gat_workspace_floats(int64_t n, int64_t S, int64_t d) { return align4(S * n * (d + 2)); }
+
+// ---- GATConv.  The forward aggregate entries share gat_aggregate_check, the backward entries gat_backward_check; `heads`
+// selects the multi-head form of either (H checked, the per-head width called C instead of d).
+static int gat_aggregate_check(const char *what, bool ptrs, const uds_csr_t *g, bool heads, int64_t H, int64_t d, int64_t S, int act,
+                               const float *hx, const float *out, const float *bias) {
+  UDS_REQUIRE(g && ptrs, "%s: NULL argument", what);
+  UDS_REQUIRE(g->n_rows == g->n_cols, "%s: pattern must be square", what);
+  if (heads) UDS_REQUIRE(H > 0 && H <= 64, "%s: H=%lld outside [1,64]", what, (long long)H);
+  UDS_REQUIRE(d > 0 && d % 4 == 0 && d <= 256, "%s: %c=%lld must be a multiple of 4, at most 256", what, heads ? 'C' : 'd', (long long)d);
+  UDS_REQUIRE(S >= 0 && S <= 65535, "%s: S=%lld outside [0,65535]", what, (long long)S);
+  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "%s: unknown activation %d", what, act);
+  UDS_REQUIRE(aligned16(hx) && aligned16(out) && aligned16(bias), "%s: hx/out/bias must be 16-byte aligned", what);
+  return UDS_OK;
+}
+
+static int gat_backward_check(const char *what, bool ptrs, const uds_csr_t *g, const uds_csr_t *gt, bool heads, int64_t H, int64_t d, int64_t S,
+                              const float *grad, const float *hx, const float *d_hx, const float *a_self, const float *a_nbr) {
+  UDS_REQUIRE(g && gt && ptrs, "%s: NULL argument", what);
+  UDS_REQUIRE(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_cols && gt->nnz == g->nnz,
+              "%s: the pattern and its transpose must be square with the same shape and entry count", what);
+  if (heads) UDS_REQUIRE(H > 0 && H <= 64, "%s: H=%lld outside [1,64]", what, (long long)H);
+  UDS_REQUIRE(d > 0 && d % 4 == 0 && d <= 256, "%s: %c=%lld must be a multiple of 4, at most 256", what, heads ? 'C' : 'd', (long long)d);
+  UDS_REQUIRE(S >= 0 && S <= 65535, "%s: S=%lld outside [0,65535]", what, (long long)S);
+  UDS_REQUIRE(aligned16(grad) && aligned16(hx) && aligned16(d_hx) && aligned16(a_self) && aligned16(a_nbr),
+              "%s: grad/hx/d_hx/a_self/a_nbr must be 16-byte aligned", what);
+  return UDS_OK;
+}
+
+// which single-head aggregate kernel an entry launches: each keeps its own (kernels_sparse.hpp)
+enum GatKernel { GAT_PLAIN, GAT_COEF, GAT_MASKED, GAT_EX };
+
+// the launch of the four single-head aggregate entries, and of uds_gat_forward after its projection
+static int gat_aggregate_launch(const char *what, GatKernel k, const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr,
+                                const float *bias, const float *edge_mask, const float *coef, int64_t S, int64_t d, int act, float *out,
+                                uds_stream_t stream) {
+  uds::GatArgs a{g->d_rowptr, g->d_col, g->d_order, hx, s_self, s_nbr, bias, out, (int)g->n_rows, (int)(d / 4), act, (int)S};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  switch (k) {
+    case GAT_COEF: return launched(what, uds::launch_gat_aggregate_coef(a, coef, g->nnz, st));
+    case GAT_MASKED: return launched(what, uds::launch_gat_aggregate_masked(a, edge_mask, g->nnz, st));
+    case GAT_EX: return launched(what, uds::launch_gat_aggregate_ex(a, uds::GatEx{edge_mask, coef, g->nnz}, st));
+    default: return launched(what, uds::launch_gat_aggregate(a, st));
+  }
+}
+
+// uds_gat_aggregate, _coef (coef required), _masked (edge_mask required) and _ex (both optional)
+static int gat_aggregate(const char *what, GatKernel k, const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr,
+                         const float *bias, const float *edge_mask, const float *coef, int64_t S, int64_t d, int act, float *out,
+                         uds_stream_t stream) {
+  const bool ptrs = hx && s_self && s_nbr && out && (k != GAT_COEF || coef) && (k != GAT_MASKED || edge_mask);
+  if (int rc = gat_aggregate_check(what, ptrs, g, false, 1, d, S, act, hx, out, bias)) return rc;
+  if (S == 0 || g->n_rows == 0) return UDS_OK;
+  return gat_aggregate_launch(what, k, g, hx, s_self, s_nbr, bias, edge_mask, coef, S, d, act, out, stream);
+}
 
 int uds_gat_forward(const uds_csr_t *g, const float *xa, int64_t fa, const float *xb, int64_t fb, int64_t S,
                     const float *W, const float *a_self, const float *a_nbr, const float *bias, int64_t d, int act,
@@ -1060,54 +1050,48 @@ int uds_gat_forward(const uds_csr_t *g, const float *xa, int64_t fa, const float
   float *s_nbr = s_self + S * n;
   int rc = uds_dense_act(xa, fa, xb, fb, S * n, W, nullptr, d, UDS_ACT_LINEAR, a_self, a_nbr, hx, s_self, s_nbr, stream);
   if (rc != UDS_OK) return rc;
-  uds::GatArgs a{g->d_rowptr, g->d_col, g->d_order, hx, s_self, s_nbr, bias, out, (int)n, (int)(d / 4), act, (int)S};
-  hipError_t e = uds::launch_gat_aggregate(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_forward: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return gat_aggregate_launch("uds_gat_forward", GAT_PLAIN, g, hx, s_self, s_nbr, bias, nullptr, nullptr, S, d, act, out, stream);
 }
 
 int uds_gat_aggregate(const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr, const float *bias, int64_t S,
                       int64_t d, int act, float *out, uds_stream_t stream) {
-  UDS_REQUIRE(g && hx && s_self && s_nbr && out, "uds_gat_aggregate: NULL argument");
-  UDS_REQUIRE(g->n_rows == g->n_cols, "uds_gat_aggregate: pattern must be square");
-  UDS_REQUIRE(d > 0 && d % 4 == 0 && d <= 256, "uds_gat_aggregate: d=%lld must be a multiple of 4, at most 256", (long long)d);
-  UDS_REQUIRE(S >= 0 && S <= 65535, "uds_gat_aggregate: S=%lld outside [0,65535]", (long long)S);
-  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "uds_gat_aggregate: unknown activation %d", act);
-  UDS_REQUIRE(aligned16(hx) && aligned16(out) && aligned16(bias), "uds_gat_aggregate: hx/out/bias must be 16-byte aligned");
-  if (S == 0 || g->n_rows == 0) return UDS_OK;
-  uds::GatArgs a{g->d_rowptr, g->d_col, g->d_order, hx, s_self, s_nbr, bias, out, (int)g->n_rows, (int)(d / 4), act, (int)S};
-  hipError_t e = uds::launch_gat_aggregate(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_aggregate: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return gat_aggregate("uds_gat_aggregate", GAT_PLAIN, g, hx, s_self, s_nbr, bias, nullptr, nullptr, S, d, act, out, stream);
 }
 
 int uds_gat_aggregate_coef(const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr, const float *bias,
                            const float *coef, int64_t S, int64_t d, int act, float *out, uds_stream_t stream) {
-  UDS_REQUIRE(g && hx && s_self && s_nbr && coef && out, "uds_gat_aggregate_coef: NULL argument");
-  UDS_REQUIRE(g->n_rows == g->n_cols, "uds_gat_aggregate_coef: pattern must be square");
-  UDS_REQUIRE(d > 0 && d % 4 == 0 && d <= 256, "uds_gat_aggregate_coef: d=%lld must be a multiple of 4, at most 256", (long long)d);
-  UDS_REQUIRE(S >= 0 && S <= 65535, "uds_gat_aggregate_coef: S=%lld outside [0,65535]", (long long)S);
-  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "uds_gat_aggregate_coef: unknown activation %d", act);
-  UDS_REQUIRE(aligned16(hx) && aligned16(out) && aligned16(bias), "uds_gat_aggregate_coef: hx/out/bias must be 16-byte aligned");
-  if (S == 0 || g->n_rows == 0) return UDS_OK;
-  uds::GatArgs a{g->d_rowptr, g->d_col, g->d_order, hx, s_self, s_nbr, bias, out, (int)g->n_rows, (int)(d / 4), act, (int)S};
-  hipError_t e = uds::launch_gat_aggregate_coef(a, coef, g->nnz, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_aggregate_coef: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return gat_aggregate("uds_gat_aggregate_coef", GAT_COEF, g, hx, s_self, s_nbr, bias, nullptr, coef, S, d, act, out, stream);
 }
 
 int uds_gat_aggregate_masked(const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr, const float *bias,
                              const float *edge_mask, int64_t S, int64_t d, int act, float *out, uds_stream_t stream) {
-  UDS_REQUIRE(g && hx && s_self && s_nbr && edge_mask && out, "uds_gat_aggregate_masked: NULL argument");
-  UDS_REQUIRE(g->n_rows == g->n_cols, "uds_gat_aggregate_masked: pattern must be square");
-  UDS_REQUIRE(d > 0 && d % 4 == 0 && d <= 256, "uds_gat_aggregate_masked: d=%lld must be a multiple of 4, at most 256", (long long)d);
-  UDS_REQUIRE(S >= 0 && S <= 65535, "uds_gat_aggregate_masked: S=%lld outside [0,65535]", (long long)S);
-  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "uds_gat_aggregate_masked: unknown activation %d", act);
-  UDS_REQUIRE(aligned16(hx) && aligned16(out) && aligned16(bias), "uds_gat_aggregate_masked: hx/out/bias must be 16-byte aligned");
+  return gat_aggregate("uds_gat_aggregate_masked", GAT_MASKED, g, hx, s_self, s_nbr, bias, edge_mask, nullptr, S, d, act, out, stream);
+}
+
+int uds_gat_aggregate_ex(const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr, const float *bias,
+                         const float *edge_mask, const float *coef, int64_t S, int64_t d, int act, float *out, uds_stream_t stream) {
+  return gat_aggregate("uds_gat_aggregate_ex", GAT_EX, g, hx, s_self, s_nbr, bias, edge_mask, coef, S, d, act, out, stream);
+}
+
+// uds_gat_backward_coef (what = "uds_gat_backward", the entry it grew out of) and uds_gat_backward_ex (ex: the row pass that
+// takes the edge mask)
+static int gat_backward(const char *what, bool ex, const uds_csr_t *g, const uds_csr_t *gt, const int32_t *perm_t, const float *grad,
+                        const float *hx, const float *s_self, const float *s_nbr, const float *a_self, const float *a_nbr,
+                        const float *edge_mask, const float *coef, int64_t S, int64_t d, float *alpha_ws, float *de_ws, float *d_hx,
+                        float *ds_self, float *ds_nbr, uds_stream_t stream) {
+  const bool ptrs = perm_t && grad && hx && s_self && s_nbr && a_self && a_nbr && alpha_ws && de_ws && d_hx && ds_self && ds_nbr;
+  if (int rc = gat_backward_check(what, ptrs, g, gt, false, 1, d, S, grad, hx, d_hx, a_self, a_nbr)) return rc;
   if (S == 0 || g->n_rows == 0) return UDS_OK;
-  uds::GatArgs a{g->d_rowptr, g->d_col, g->d_order, hx, s_self, s_nbr, bias, out, (int)g->n_rows, (int)(d / 4), act, (int)S};
-  hipError_t e = uds::launch_gat_aggregate_masked(a, edge_mask, g->nnz, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_aggregate_masked: launch -> %s", hipGetErrorString(e));
+  const int d4 = (int)(d / 4);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  uds::GatBwdRowsArgs ra{g->d_rowptr, g->d_col, grad, hx, s_self, s_nbr, alpha_ws, de_ws, ds_self,
+                         (int)g->n_rows, d4, (int)S, uds::lanes_per_item(d4), g->nnz, coef, edge_mask};
+  hipError_t e = ex ? uds::launch_gat_bwd_rows_ex(ra, st) : uds::launch_gat_bwd_rows(ra, st);
+  if (e != hipSuccess) return fail(UDS_EHIP, "%s: row pass launch -> %s", what, hipGetErrorString(e));
+  uds::GatBwdColsArgs ca{gt->d_rowptr, gt->d_col, perm_t, grad, alpha_ws, de_ws, ds_self, a_self, a_nbr, d_hx, ds_nbr,
+                         (int)g->n_rows, d4, (int)S, g->nnz};
+  e = uds::launch_gat_bwd_cols(ca, st);
+  if (e != hipSuccess) return fail(UDS_EHIP, "%s: column pass launch -> %s", what, hipGetErrorString(e));
   return UDS_OK;
 }
 
@@ -1120,106 +1104,40 @@ int uds_gat_backward(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *per
 int uds_gat_backward_coef(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *perm_t, const float *grad, const float *hx,
                           const float *s_self, const float *s_nbr, const float *a_self, const float *a_nbr, const float *coef, int64_t S,
                           int64_t d, float *alpha_ws, float *de_ws, float *d_hx, float *ds_self, float *ds_nbr, uds_stream_t stream) {
-  UDS_REQUIRE(g && gt && perm_t && grad && hx && s_self && s_nbr && a_self && a_nbr && alpha_ws && de_ws && d_hx && ds_self && ds_nbr,
-              "uds_gat_backward: NULL argument");
-  UDS_REQUIRE(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_cols && gt->nnz == g->nnz,
-              "uds_gat_backward: the pattern and its transpose must be square with the same shape and entry count");
-  UDS_REQUIRE(d > 0 && d % 4 == 0 && d <= 256, "uds_gat_backward: d=%lld must be a multiple of 4, at most 256", (long long)d);
-  UDS_REQUIRE(S >= 0 && S <= 65535, "uds_gat_backward: S=%lld outside [0,65535]", (long long)S);
-  UDS_REQUIRE(aligned16(grad) && aligned16(hx) && aligned16(d_hx) && aligned16(a_self) && aligned16(a_nbr),
-              "uds_gat_backward: grad/hx/d_hx/a_self/a_nbr must be 16-byte aligned");
-  if (S == 0 || g->n_rows == 0) return UDS_OK;
-  const int d4 = (int)(d / 4);
-  uds::GatBwdRowsArgs ra{g->d_rowptr, g->d_col, grad, hx, s_self, s_nbr, alpha_ws, de_ws, ds_self,
-                         (int)g->n_rows, d4, (int)S, uds::lanes_per_item(d4), g->nnz, coef};
-  hipError_t e = uds::launch_gat_bwd_rows(ra, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_backward: row pass launch -> %s", hipGetErrorString(e));
-  uds::GatBwdColsArgs ca{gt->d_rowptr, gt->d_col, perm_t, grad, alpha_ws, de_ws, ds_self, a_self, a_nbr, d_hx, ds_nbr,
-                         (int)g->n_rows, d4, (int)S, g->nnz};
-  e = uds::launch_gat_bwd_cols(ca, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_backward: column pass launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
-}
-
-int uds_gat_aggregate_ex(const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr, const float *bias,
-                         const float *edge_mask, const float *coef, int64_t S, int64_t d, int act, float *out, uds_stream_t stream) {
-  UDS_REQUIRE(g && hx && s_self && s_nbr && out, "uds_gat_aggregate_ex: NULL argument");
-  UDS_REQUIRE(g->n_rows == g->n_cols, "uds_gat_aggregate_ex: pattern must be square");
-  UDS_REQUIRE(d > 0 && d % 4 == 0 && d <= 256, "uds_gat_aggregate_ex: d=%lld must be a multiple of 4, at most 256", (long long)d);
-  UDS_REQUIRE(S >= 0 && S <= 65535, "uds_gat_aggregate_ex: S=%lld outside [0,65535]", (long long)S);
-  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "uds_gat_aggregate_ex: unknown activation %d", act);
-  UDS_REQUIRE(aligned16(hx) && aligned16(out) && aligned16(bias), "uds_gat_aggregate_ex: hx/out/bias must be 16-byte aligned");
-  if (S == 0 || g->n_rows == 0) return UDS_OK;
-  uds::GatArgs a{g->d_rowptr, g->d_col, g->d_order, hx, s_self, s_nbr, bias, out, (int)g->n_rows, (int)(d / 4), act, (int)S};
-  hipError_t e = uds::launch_gat_aggregate_ex(a, uds::GatEx{edge_mask, coef, g->nnz}, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_aggregate_ex: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return gat_backward("uds_gat_backward", false, g, gt, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, nullptr, coef, S, d, alpha_ws, de_ws, d_hx,
+                      ds_self, ds_nbr, stream);
 }
 
 int uds_gat_backward_ex(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *perm_t, const float *grad, const float *hx,
                         const float *s_self, const float *s_nbr, const float *a_self, const float *a_nbr, const float *edge_mask,
                         const float *coef, int64_t S, int64_t d, float *alpha_ws, float *de_ws, float *d_hx, float *ds_self,
                         float *ds_nbr, uds_stream_t stream) {
-  UDS_REQUIRE(g && gt && perm_t && grad && hx && s_self && s_nbr && a_self && a_nbr && alpha_ws && de_ws && d_hx && ds_self && ds_nbr,
-              "uds_gat_backward_ex: NULL argument");
-  UDS_REQUIRE(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_cols && gt->nnz == g->nnz,
-              "uds_gat_backward_ex: the pattern and its transpose must be square with the same shape and entry count");
-  UDS_REQUIRE(d > 0 && d % 4 == 0 && d <= 256, "uds_gat_backward_ex: d=%lld must be a multiple of 4, at most 256", (long long)d);
-  UDS_REQUIRE(S >= 0 && S <= 65535, "uds_gat_backward_ex: S=%lld outside [0,65535]", (long long)S);
-  UDS_REQUIRE(aligned16(grad) && aligned16(hx) && aligned16(d_hx) && aligned16(a_self) && aligned16(a_nbr),
-              "uds_gat_backward_ex: grad/hx/d_hx/a_self/a_nbr must be 16-byte aligned");
-  if (S == 0 || g->n_rows == 0) return UDS_OK;
-  const int d4 = (int)(d / 4);
-  uds::GatBwdRowsArgs ra{g->d_rowptr, g->d_col, grad, hx, s_self, s_nbr, alpha_ws, de_ws, ds_self,
-                         (int)g->n_rows, d4, (int)S, uds::lanes_per_item(d4), g->nnz, coef, edge_mask};
-  hipError_t e = uds::launch_gat_bwd_rows_ex(ra, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_backward_ex: row pass launch -> %s", hipGetErrorString(e));
-  uds::GatBwdColsArgs ca{gt->d_rowptr, gt->d_col, perm_t, grad, alpha_ws, de_ws, ds_self, a_self, a_nbr, d_hx, ds_nbr,
-                         (int)g->n_rows, d4, (int)S, g->nnz};
-  e = uds::launch_gat_bwd_cols(ca, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_backward_ex: column pass launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return gat_backward("uds_gat_backward_ex", true, g, gt, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, edge_mask, coef, S, d, alpha_ws, de_ws,
+                      d_hx, ds_self, ds_nbr, stream);
 }
 
 int uds_gat_aggregate_heads(const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr, const float *bias,
                             const float *edge_mask, const float *coef, int64_t S, int64_t H, int64_t C, int concat, int act,
                             float *out, float *alpha_out, uds_stream_t stream) {
-  UDS_REQUIRE(g && hx && s_self && s_nbr && out, "uds_gat_aggregate_heads: NULL argument");
-  UDS_REQUIRE(g->n_rows == g->n_cols, "uds_gat_aggregate_heads: pattern must be square");
-  UDS_REQUIRE(H > 0 && H <= 64, "uds_gat_aggregate_heads: H=%lld outside [1,64]", (long long)H);
-  UDS_REQUIRE(C > 0 && C % 4 == 0 && C <= 256, "uds_gat_aggregate_heads: C=%lld must be a multiple of 4, at most 256", (long long)C);
-  UDS_REQUIRE(S >= 0 && S <= 65535, "uds_gat_aggregate_heads: S=%lld outside [0,65535]", (long long)S);
-  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "uds_gat_aggregate_heads: unknown activation %d", act);
-  UDS_REQUIRE(aligned16(hx) && aligned16(out) && aligned16(bias), "uds_gat_aggregate_heads: hx/out/bias must be 16-byte aligned");
+  if (int rc = gat_aggregate_check("uds_gat_aggregate_heads", hx && s_self && s_nbr && out, g, true, H, C, S, act, hx, out, bias)) return rc;
   if (S == 0 || g->n_rows == 0) return UDS_OK;
   uds::GatHeadsArgs a{g->d_rowptr, g->d_col, g->d_order, hx, s_self, s_nbr, bias, edge_mask, coef, out, alpha_out,
                       (int)g->n_rows, (int)H, (int)(C / 4), act, (int)S, concat ? 0 : 1, g->nnz};
-  hipError_t e = uds::launch_gat_aggregate_heads(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_aggregate_heads: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_gat_aggregate_heads", uds::launch_gat_aggregate_heads(a, static_cast<hipStream_t>(stream)));
 }
 
 int uds_gat_backward_heads(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *perm_t, const float *grad, const float *hx,
                            const float *s_self, const float *s_nbr, const float *a_self, const float *a_nbr,
                            const float *edge_mask, const float *coef, int64_t S, int64_t H, int64_t C, int concat,
                            float *alpha_ws, float *de_ws, float *d_hx, float *ds_self, float *ds_nbr, uds_stream_t stream) {
-  UDS_REQUIRE(g && gt && perm_t && grad && hx && s_self && s_nbr && a_self && a_nbr && alpha_ws && de_ws && d_hx && ds_self && ds_nbr,
-              "uds_gat_backward_heads: NULL argument");
-  UDS_REQUIRE(g->n_rows == g->n_cols && gt->n_rows == g->n_rows && gt->n_cols == g->n_cols && gt->nnz == g->nnz,
-              "uds_gat_backward_heads: the pattern and its transpose must be square with the same shape and entry count");
-  UDS_REQUIRE(H > 0 && H <= 64, "uds_gat_backward_heads: H=%lld outside [1,64]", (long long)H);
-  UDS_REQUIRE(C > 0 && C % 4 == 0 && C <= 256, "uds_gat_backward_heads: C=%lld must be a multiple of 4, at most 256", (long long)C);
-  UDS_REQUIRE(S >= 0 && S <= 65535, "uds_gat_backward_heads: S=%lld outside [0,65535]", (long long)S);
-  UDS_REQUIRE(aligned16(grad) && aligned16(hx) && aligned16(d_hx) && aligned16(a_self) && aligned16(a_nbr),
-              "uds_gat_backward_heads: grad/hx/d_hx/a_self/a_nbr must be 16-byte aligned");
+  const bool ptrs = perm_t && grad && hx && s_self && s_nbr && a_self && a_nbr && alpha_ws && de_ws && d_hx && ds_self && ds_nbr;
+  if (int rc = gat_backward_check("uds_gat_backward_heads", ptrs, g, gt, true, H, C, S, grad, hx, d_hx, a_self, a_nbr)) return rc;
   if (S == 0 || g->n_rows == 0) return UDS_OK;
   const int c4 = (int)(C / 4);
   uds::GatBwdHeadsArgs a{g->d_rowptr, g->d_col, gt->d_rowptr, gt->d_col, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr, edge_mask, coef,
                          alpha_ws, de_ws, d_hx, ds_self, ds_nbr, (int)g->n_rows, (int)H, c4, (int)S, uds::lanes_per_item(c4),
                          concat ? 0 : 1, g->nnz};
-  hipError_t e = uds::launch_gat_bwd_heads(a, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_gat_backward_heads: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_gat_backward_heads", uds::launch_gat_bwd_heads(a, static_cast<hipStream_t>(stream)));
 }
 
 int uds_csr_sddmm(const uds_csr_t *csr, const float *a, const float *b, int64_t S, int64_t F, float *out, uds_stream_t stream) {
@@ -1231,9 +1149,7 @@ int uds_csr_sddmm(const uds_csr_t *csr, const float *a, const float *b, int64_t 
   const int f4 = (int)(F / 4);
   uds::SddmmArgs sa{csr->d_rowidx, csr->d_col, a, b, out, (int)csr->n_rows, (int)csr->n_cols, f4, (int)S, uds::lanes_per_item(f4),
                     csr->nnz};
-  hipError_t e = uds::launch_csr_sddmm(sa, static_cast<hipStream_t>(stream));
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_csr_sddmm: launch -> %s", hipGetErrorString(e));
-  return UDS_OK;
+  return launched("uds_csr_sddmm", uds::launch_csr_sddmm(sa, static_cast<hipStream_t>(stream)));
 }
 
 int64_t uds_wgrad_workspace_floats(int64_t rows, int64_t F, int64_t H, int with_bias) {
@@ -1263,14 +1179,13 @@ int uds_wgrad(const float *a, const float *g, int64_t B, int64_t T, int64_t R, i
   int64_t rpw = (rows + (int64_t)grid * 4 - 1) / ((int64_t)grid * 4);
   rpw = (rpw + 31) / 32 * 32;
   uds::WgradArgs wa{a, g, workspace, rows, (int)F, (int)H, with_bias ? (int)F : -1, (int)shift, (int)T, (int)R, (int)rpw};
-  hipError_t e = uds::launch_wgrad(wa, mt, nt, grid, st);
-  if (e != hipSuccess) return fail(UDS_EHIP, "uds_wgrad: launch -> %s", hipGetErrorString(e));
+  if (int rc = launched("uds_wgrad", uds::launch_wgrad(wa, mt, nt, grid, st))) return rc;
   hipLaunchKernelGGL(uds::k_wgrad_reduce, dim3((unsigned)((F * H + 15) / 16)), dim3(256), 0, st, workspace, grid, mt * 16, nt * 16,
                      (int)F, (int)H, d_kernel);
   if (with_bias)
     hipLaunchKernelGGL(uds::k_wgrad_reduce, dim3((unsigned)((H + 15) / 16)), dim3(256), 0, st, workspace + F * (nt * 16), grid,
                        mt * 16, nt * 16, 1, (int)H, d_bias);
-  e = hipGetLastError();
+  hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(UDS_EHIP, "uds_wgrad: reduce launch -> %s", hipGetErrorString(e));
   return UDS_OK;
 }
@@ -1487,7 +1402,7 @@ int uds_spatial_pack_weights(const uds_spatial_params_t *p, int64_t fx, int64_t 
     const int ts = (int)(fe / 16) * (int)(h / 32) * 64;
     hipLaunchKernelGGL(uds::k_pack_weight_frags32, dim3((ts + 255) / 256), dim3(256), 0, st, p->xe_k, (int)fe, (int)h, wq + WS_SMALL32_OFF);
     hipLaunchKernelGGL(uds::k_pack_weight_frags32, dim3((ts + 255) / 256), dim3(256), 0, st, p->ex_k, (int)fx, (int)h, wq + WS_SMALL32_OFF + WS_SMALL32_LEN);
-    if ((he = hipGetLastError()) != hipSuccess) return fail(UDS_EHIP, "uds_spatial_pack_weights: launch -> %s", hipGetErrorString(he));
+    return launched("uds_spatial_pack_weights", hipGetLastError());
   }
   return UDS_OK;
 }
