@@ -68,7 +68,7 @@ __device__ __forceinline__ void rowgemm_epilogue(const RowGemmArgs &a, f32x4 (&a
   const int r16 = lane & 15, qd = lane >> 4;
   with_act(a.act, [&](auto act_) {
     constexpr int ACT_ = decltype(act_)::value;
-  if (a.fo == 16 * MB && MB >= 2) {
+  if (STAGE && a.fo == 16 * MB && MB >= 2) {      // STAGE = false: no tile was allocated, the direct stores below
     // turn each 16 x 32 accumulator pair through the wave's tile so that one store instruction writes 8 rows x 128 B
     // (whole cache lines; 1 KiB contiguous when fo = 32) instead of sixteen 64-byte pieces
 #pragma unroll

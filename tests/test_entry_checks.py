@@ -326,7 +326,9 @@ def null_args(entry):
 
 
 def _id(case):
-    return '%s-%s' % (case[0], '-'.join('%s=%s' % (k, 'Q' if v == Q else v) for k, v in case[1].items()))
+    """Addresses differ from one process to the next, so an id names them: the same test keeps the same id in every run."""
+    names = {P: 'P', Q: 'Q', ctypes.addressof(_HEADS): 'HEADS', ctypes.addressof(_HEADS5): 'HEADS5'}
+    return '%s-%s' % (case[0], '-'.join('%s=%s' % (k, names.get(v, v) if isinstance(v, int) else v) for k, v in case[1].items()))
 
 
 @pytest.mark.parametrize('case', CASES, ids=_id)
