@@ -332,12 +332,17 @@ inline hipError_t launch_recurrent(const RecurrentArgs &a, hipStream_t st) {
   const int64_t total = (int64_t)a.B * a.R;
   const unsigned grid = (unsigned)((total + a.rows - 1) / a.rows);
   const size_t lds = ((size_t)a.H * a.G * a.H + (size_t)a.rows * a.H) * sizeof(float);
-  static size_t attr_lds[2] = {0, 0};                 // raise the dynamic-LDS limit once per size (not inside a stream capture)
-  if (lds > attr_lds[a.G - 3]) {
+  // raise the dynamic-LDS limit once per size (not inside a stream capture) and, as set_max_lds_once, per device ordinal: the
+  // attribute is per device, a limit raised on one GPU leaves the launch on the next one of the same process refused
+  static size_t attr_lds[2][64] = {};
+  int dev = 0;
+  if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return e;
+  size_t &raised = attr_lds[a.G - 3][dev & 63];
+  if (lds > raised) {
     hipError_t e = hipFuncSetAttribute(a.G == 3 ? reinterpret_cast<const void *>(k_recurrent<3>) : reinterpret_cast<const void *>(k_recurrent<4>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    attr_lds[a.G - 3] = lds;
+    raised = lds;
   }
   if (a.G == 3) hipLaunchKernelGGL(k_recurrent<3>, dim3(grid), dim3(a.rows * a.H), lds, st, a);
   else hipLaunchKernelGGL(k_recurrent<4>, dim3(grid), dim3(a.rows * a.H), lds, st, a);
