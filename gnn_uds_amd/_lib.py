@@ -117,6 +117,9 @@ SYMBOLS = {
     'uds_tile_plan_copy': (_c_int, [_c_ptr, _c_ptr, _c_ptr]),
     'uds_tile_plan_blocks': (_c_int, [_c_ptr, _c_ptr, ctypes.POINTER(_c_i64)]),
     'uds_roll_update': (_c_int, [_c_ptr] * 7 + [_c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_predict_tail': (_c_int, [_c_ptr] * 9 + [_c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_predict_tail_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    'uds_predict_tail_backward': (_c_int, [_c_ptr] * 9 + [_c_i64, _c_i64] + [_c_ptr] * 8),
     'uds_spatial_workspace_floats': (_c_i64, [_c_ptr, _c_i64, _c_i64, _c_i64]),
     'uds_spatial_packed_bytes': (_c_i64, []),
     'uds_spatial_pack_weights': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr]),
@@ -996,6 +999,97 @@ def roll_update(handle, sign, span_e, mini_e, scale_in, scale_out, y, ey, b, x, 
                                _dev(scale_out, 'scale_out'), _dev(y.contiguous(), 'y'), cy, _dev(ey.contiguous(), 'ey'), ce, _dev(b.contiguous(), 'b'),
                                B, so, T, int(bool(flood)), _dev(x, 'x'), _dev(ex, 'ex'), _dev(preds, 'preds'), _stream()), 'uds_roll_update')
     return preds
+
+
+class TailParams(ctypes.Structure):
+    """uds_tail_t"""
+    SIZES = ('N', 'E', 'cy', 'ce', 'n_act', 'b_channels')
+    SWITCHES = ('edge_fusion', 'tide', 'has_offset', 'act', 'pump_override', 'any_pump', 'if_flood')
+    FLOAT_TABLES = ('is_outfall', 'hmin', 'hmax', 'area_eps', 'ps', 'pump_in', 'pump_out', 'ny_in', 'ny_out', 'scale_in', 'scale_out',
+                    'span_y', 'mini_y', 'offset', 'pump', 'pump_mask', 'pump_den', 'ehmax', 'from_ok', 'span_e', 'mini_e', 'link_sign')
+    INT_TABLES = ('from_node', 'act_link', 'act_in', 'act_out', 'link_node', 'al_ptr', 'al_idx', 'ai_ptr', 'ai_idx', 'ao_ptr', 'ao_idx')
+    _fields_ = ([(n, ctypes.c_int32) for n in SIZES + SWITCHES] + [('depth_gate', ctypes.c_float), ('epsilon', ctypes.c_float)] +
+                [(n, _c_ptr) for n in ('is_outfall', 'hmin', 'hmax', 'area_eps', 'ps', 'pump_in', 'pump_out', 'ny_in', 'ny_out', 'scale_in',
+                                       'scale_out', 'span_y', 'mini_y', 'offset', 'pump', 'pump_mask', 'pump_den', 'ehmax', 'from_ok',
+                                       'span_e', 'mini_e', 'from_node', 'act_link', 'act_in', 'act_out', 'link_node', 'link_sign',
+                                       'al_ptr', 'al_idx', 'ai_ptr', 'ai_idx', 'ao_ptr', 'ao_idx')])
+
+
+class TailSpec:
+    """The constants of one model's predict tail on one device: `tables` name -> device tensor (fp32, or int32 for
+    TailParams.INT_TABLES; the tensors are kept alive here), `scalars` the sizes and switches.  struct(depth_gate, pump_override)
+    fills a uds_tail_t for one mode."""
+
+    def __init__(self, tables, **scalars):
+        self.tables, self.scalars = dict(tables), dict(scalars)
+        for n in TailParams.FLOAT_TABLES:
+            _dev(self.tables[n], n)
+        for n in TailParams.INT_TABLES:
+            _dev_i32(self.tables[n], n)
+
+    def struct(self, depth_gate, pump_override):
+        p = TailParams()
+        for n in TailParams.SIZES + TailParams.SWITCHES:
+            if n != 'pump_override':
+                setattr(p, n, int(self.scalars[n]))
+        p.pump_override, p.depth_gate, p.epsilon = int(bool(pump_override)), float(depth_gate), float(self.scalars['epsilon'])
+        for n in TailParams.FLOAT_TABLES + TailParams.INT_TABLES:
+            t = self.tables[n]
+            setattr(p, n, t.data_ptr() if t.numel() else None)
+        return p
+
+
+def _tail_operands(handle, spec, y, ey, a, b_norm, runoff, h0):
+    s = spec.scalars
+    B, T = y.shape[:2]
+    N, E = s['N'], s['E']
+    want = dict(y=(B, T, N, s['cy']), ey=(B, T, E, s['ce']), b_norm=(B, T, N, s['b_channels']), runoff=(B, T, N), h0=(B, N))
+    if s['act']:
+        want['a'] = (B, T, s['n_act'])
+    got = dict(y=y, ey=ey, a=a, b_norm=b_norm, runoff=runoff, h0=h0)
+    for name, shape in want.items():
+        if got[name] is None or tuple(got[name].shape) != shape:
+            raise UdsError('predict_tail: %s must be %r, got %r' % (name, shape, None if got[name] is None else tuple(got[name].shape)))
+    if handle.n_rows != N or handle.n_cols != E:
+        raise UdsError('predict_tail: the incidence pattern is %d x %d, the model has %d nodes and %d links' % (handle.n_rows, handle.n_cols, N, E))
+    return B, T
+
+
+def predict_tail(handle, sign, spec, y, ey, a, b_norm, runoff, h0, depth_gate=0.0, pump_override=False, out_y=None, out_ey=None):
+    """Everything after the network forward of Emulator.predict_tf / predict (include/uds_hip.h: uds_predict_tail): returns
+    out_y (B,T,N,4 or 5) and out_ey (B,T,E,ce).  spec: a TailSpec."""
+    lib = load()
+    B, T = _tail_operands(handle, spec, y, ey, a, b_norm, runoff, h0)
+    s = spec.scalars
+    out_y = _out(out_y, (B, T, s['N'], 4 + int(bool(s['if_flood']))), y, 'out_y')
+    out_ey = _out(out_ey, (B, T, s['E'], s['ce']), y, 'out_ey')
+    if out_y.numel() == 0:
+        return out_y, out_ey
+    p = spec.struct(depth_gate, pump_override)
+    _check(lib.uds_predict_tail(handle.ptr, _dev(sign, 'sign'), ctypes.addressof(p), _dev(y, 'y'), _dev(ey, 'ey'), _dev(a, 'a', not s['act']),
+                                _dev(b_norm, 'b_norm'), _dev(runoff, 'runoff'), _dev(h0, 'h0'), B, T, _dev(out_y, 'out_y'), _dev(out_ey, 'out_ey'),
+                                _stream()), 'uds_predict_tail')
+    return out_y, out_ey
+
+
+def predict_tail_backward(handle, sign, spec, y, ey, a, b_norm, runoff, h0, g_out_y, g_out_ey, depth_gate=0.0, pump_override=False):
+    """Reverse mode of predict_tail: (dy, dey, da or None, dh0) for the upstream gradients of both outputs."""
+    lib = load()
+    B, T = _tail_operands(handle, spec, y, ey, a, b_norm, runoff, h0)
+    s = spec.scalars
+    if tuple(g_out_y.shape) != (B, T, s['N'], 4 + int(bool(s['if_flood']))) or tuple(g_out_ey.shape) != tuple(ey.shape):
+        raise UdsError('predict_tail_backward: gradients %r / %r do not have the shapes of the outputs' % (tuple(g_out_y.shape), tuple(g_out_ey.shape)))
+    dy, dey, dh0 = torch.empty_like(y), torch.empty_like(ey), torch.empty_like(h0)
+    da = torch.empty_like(a) if s['act'] else None
+    if dy.numel() == 0:
+        return dy, dey, da, dh0
+    ws = torch.empty(int(lib.uds_predict_tail_workspace_floats(s['N'], s['E'], B, T)), device=y.device, dtype=torch.float32)
+    p = spec.struct(depth_gate, pump_override)
+    _check(lib.uds_predict_tail_backward(handle.ptr, _dev(sign, 'sign'), ctypes.addressof(p), _dev(y, 'y'), _dev(ey, 'ey'), _dev(a, 'a', not s['act']),
+                                         _dev(b_norm, 'b_norm'), _dev(runoff, 'runoff'), _dev(h0, 'h0'), B, T, _dev(g_out_y, 'g_out_y'),
+                                         _dev(g_out_ey, 'g_out_ey'), _dev(dy, 'dy'), _dev(dey, 'dey'), _dev(da, 'da', not s['act']), _dev(dh0, 'dh0'),
+                                         _dev(ws, 'workspace'), _stream()), 'uds_predict_tail_backward')
+    return dy, dey, da, dh0
 
 
 def csr_spmm(handle, val, x, bias=None, act='linear', out=None):

@@ -521,6 +521,30 @@ class FlowBalanceFn(torch.autograd.Function):
         return dflow, None, None, None, None, None
 
 
+class PredictTailFn(torch.autograd.Function):
+    """The tail of `Emulator.predict_tf` (everything after the network forward) as one HIP forward and one HIP backward
+    (include/uds_hip.h: uds_predict_tail / uds_predict_tail_backward).  Differentiable in y, ey, a and h0; b_norm and runoff
+    are constants here (the emulator keeps the tensor route when they need a gradient)."""
+
+    @staticmethod
+    def forward(ctx, y, ey, a, h0, b_norm, runoff, handle, sign, spec, depth_gate, pump_override):
+        y, ey, h0 = y.contiguous(), ey.contiguous(), h0.contiguous()
+        a = None if a is None else a.contiguous()
+        ctx.save_for_backward(y, ey, h0, b_norm, runoff, sign, *([] if a is None else [a]))
+        ctx.tail = (handle, spec, depth_gate, pump_override)
+        out_y, out_ey = _lib.predict_tail(handle, sign, spec, y, ey, a, b_norm, runoff, h0, depth_gate, pump_override)
+        return out_y, out_ey
+
+    @staticmethod
+    def backward(ctx, g_y, g_ey):
+        y, ey, h0, b_norm, runoff, sign, *rest = ctx.saved_tensors
+        a = rest[0] if rest else None
+        handle, spec, depth_gate, pump_override = ctx.tail
+        dy, dey, da, dh0 = _lib.predict_tail_backward(handle, sign, spec, y, ey, a, b_norm, runoff, h0, g_y.contiguous(), g_ey.contiguous(),
+                                                      depth_gate, pump_override)
+        return dy, dey, da, dh0, None, None, None, None, None, None, None
+
+
 def grad_on(*tensors):
     """True when autograd is recording and one of the tensors needs a gradient: the modules then take the Function path."""
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)

@@ -7,6 +7,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <numeric>
 #include <string>
@@ -28,6 +29,7 @@
 #include "kernels_gemm.hpp"
 #include "kernels_recurrent.hpp"
 #include "kernels_recurrent_bwd.hpp"
+#include "kernels_tail.hpp"
 #include "tile_plan.hpp"
 
 namespace {
@@ -962,6 +964,74 @@ int uds_roll_update(const uds_csr_t *inc_n, const float *sign, const float *span
   uds::RollArgs a{inc_n->d_rowptr, inc_n->d_col, sign, span_e, mini_e, scale_in, scale_out, y, ey, b, x, ex, preds,
                   (int)B, (int)so, (int)T, (int)inc_n->n_rows, (int)inc_n->n_cols, (int)cy, (int)ce, flood};
   return launched("uds_roll_update", uds::launch_roll_update(a, static_cast<hipStream_t>(stream)));
+}
+
+// ---- predict tail.  uds_predict_tail and uds_predict_tail_backward share tail_check: everything that needs no device first
+// (inc_n is only looked into once the rest has passed).
+static int tail_check(const char *what, const uds_csr_t *inc_n, const float *sign, const uds_tail_t *p, const float *y, const float *ey,
+                      const float *a, const float *b_norm, const float *runoff, const float *h0, int64_t B, int64_t T,
+                      std::initializer_list<const void *> more) {
+  UDS_REQUIRE(inc_n && sign && p, "%s: NULL argument", what);
+  UDS_REQUIRE(y && ey && b_norm && runoff && h0, "%s: NULL y/ey/b_norm/runoff/h0", what);
+  UDS_REQUIRE(B >= 0 && T >= 1 && p->N >= 1 && p->E >= 1 && p->ce >= 2 && p->ce <= 8 && p->n_act >= 0 && p->b_channels >= 1,
+              "%s: bad sizes B=%lld T=%lld N=%d E=%d ce=%d n_act=%d b_channels=%d (needs T >= 1, 2 <= ce <= 8)", what, (long long)B, (long long)T,
+              p->N, p->E, p->ce, p->n_act, p->b_channels);
+  const int want = (p->edge_fusion ? 1 : 3) + (p->if_flood ? 1 : 0);
+  UDS_REQUIRE(p->cy == want, "%s: cy=%d does not go with edge_fusion=%d if_flood=%d (needs %d)", what, p->cy, p->edge_fusion, p->if_flood, want);
+  UDS_REQUIRE(!p->act || (a && p->n_act >= 1), "%s: act needs the settings a and n_act >= 1", what);
+  bool aligned = aligned16(y) && aligned16(ey) && aligned16(a) && aligned16(b_norm) && aligned16(runoff) && aligned16(h0);
+  for (const void *q : more) aligned = aligned && aligned16(q);
+  UDS_REQUIRE(aligned, "%s: tensors must be 16-byte aligned", what);
+  UDS_REQUIRE(p->is_outfall && p->hmin && p->hmax && p->area_eps && p->ps && p->pump_in && p->pump_out && p->ny_in && p->ny_out && p->scale_in &&
+                  p->scale_out && p->span_y && p->mini_y && p->offset && p->pump && p->pump_mask && p->pump_den && p->ehmax && p->from_ok &&
+                  p->span_e && p->mini_e && p->from_node && p->link_node && p->link_sign,
+              "%s: NULL table in uds_tail_t", what);
+  UDS_REQUIRE(!p->act || (p->act_link && p->act_in && p->act_out && p->al_ptr && p->al_idx && p->ai_ptr && p->ai_idx && p->ao_ptr && p->ao_idx),
+              "%s: act needs the action tables of uds_tail_t", what);
+  UDS_REQUIRE(B * T * (int64_t)std::max(p->N, p->E) < INT32_MAX, "%s: batch x steps x rows exceeds the int32 index", what);
+  UDS_REQUIRE(inc_n->n_rows == p->N && inc_n->n_cols == p->E, "%s: incidence pattern is %lld x %lld, uds_tail_t says N=%d E=%d", what,
+              (long long)inc_n->n_rows, (long long)inc_n->n_cols, p->N, p->E);
+  return UDS_OK;
+}
+
+int uds_predict_tail(const uds_csr_t *inc_n, const float *sign, const uds_tail_t *p, const float *y, const float *ey, const float *a,
+                     const float *b_norm, const float *runoff, const float *h0, int64_t B, int64_t T, float *out_y, float *out_ey,
+                     uds_stream_t stream) {
+  const char *what = "uds_predict_tail";
+  UDS_REQUIRE(out_y && out_ey, "%s: NULL output", what);
+  if (int rc = tail_check(what, inc_n, sign, p, y, ey, a, b_norm, runoff, h0, B, T, {out_y, out_ey})) return rc;
+  if (B == 0) return UDS_OK;
+  uds::TailArgs t{};
+  t.p = *p;
+  t.rowptr = inc_n->d_rowptr; t.col = inc_n->d_col; t.sign = sign;
+  t.y = y; t.ey = ey; t.a = a; t.b_norm = b_norm; t.runoff = runoff; t.h0 = h0;
+  t.out_y = out_y; t.out_ey = out_ey;
+  t.B = (int)B; t.T = (int)T; t.C = 3 + (p->if_flood ? 1 : 0);
+  return launched(what, uds::launch_tail_forward(t, static_cast<hipStream_t>(stream)));
+}
+
+int64_t uds_predict_tail_workspace_floats(int64_t N, int64_t E, int64_t B, int64_t T) {
+  if (N < 0 || E < 0 || B < 0 || T < 0) return 0;
+  return 3 * align4(B * T * N) + align4(B * T * E);
+}
+
+int uds_predict_tail_backward(const uds_csr_t *inc_n, const float *sign, const uds_tail_t *p, const float *y, const float *ey, const float *a,
+                              const float *b_norm, const float *runoff, const float *h0, int64_t B, int64_t T, const float *g_out_y,
+                              const float *g_out_ey, float *dy, float *dey, float *da, float *dh0, float *workspace, uds_stream_t stream) {
+  const char *what = "uds_predict_tail_backward";
+  UDS_REQUIRE(g_out_y && g_out_ey && dy && dey && dh0 && workspace, "%s: NULL gradient / workspace", what);
+  UDS_REQUIRE(!(p && p->act) || da, "%s: act needs da", what);
+  if (int rc = tail_check(what, inc_n, sign, p, y, ey, a, b_norm, runoff, h0, B, T, {g_out_y, g_out_ey, dy, dey, da, dh0, workspace})) return rc;
+  if (B == 0) return UDS_OK;
+  uds::TailArgs t{};
+  t.p = *p;
+  t.rowptr = inc_n->d_rowptr; t.col = inc_n->d_col; t.sign = sign;
+  t.y = y; t.ey = ey; t.a = a; t.b_norm = b_norm; t.runoff = runoff; t.h0 = h0;
+  t.g_out_y = g_out_y; t.g_out_ey = g_out_ey; t.dy = dy; t.dey = dey; t.da = da; t.dh0 = dh0;
+  const int64_t bn = align4(B * T * p->N);
+  t.ws_qi = workspace; t.ws_qo = workspace + bn; t.ws_prev = workspace + 2 * bn; t.ws_set = workspace + 3 * bn;
+  t.B = (int)B; t.T = (int)T; t.C = 3 + (p->if_flood ? 1 : 0);
+  return launched(what, uds::launch_tail_backward(t, static_cast<hipStream_t>(stream)));
 }
 
 int uds_csr_spmm(const uds_csr_t *csr, const float *val, const float *x, int64_t S, int64_t F, const float *bias,

@@ -886,6 +886,10 @@ class Emulator(nn.Module):
         adj = self.get_adj_action(a, not np_form) if self.act and self.use_adj else None
         nb_ = self.normalize(b, 'b')
         y, ey = self.forward(self.normalize(x, 'x'), nb_, self.normalize(ex, 'e'), ae, adj)
+        fused = self._predict_tail_hip(y, ey, a, b, nb_, x, np_form)
+        if fused is not None:
+            return fused
+        self.last_tail_path = 'torch'
         y, ey = self._post_proc((y, ey), a, nb_, np_form)
         ey = self.normalize(ey, 'e', True)
         ey = torch.cat([torch.minimum(ey[..., 0].clamp(min=0), self.ehmax).unsqueeze(-1), ey[..., 1:]], dim=-1)
@@ -901,6 +905,106 @@ class Emulator(nn.Module):
             y = torch.cat([(h * (1 - ps) + torch.stack(de, dim=1) * ps).unsqueeze(-1), y[..., 1:]], dim=-1)
         q_w, y = self.constrain_tf(y, b[..., :1], x[:, -1:, :, 0])
         return torch.cat([y, q_w.unsqueeze(-1)], dim=-1), ey
+
+    # ------------------------------------------------------------------ the predict tail as one HIP operator
+    fused_tail = True          # False: `_predict` keeps its tensor code for everything after the forward
+    last_tail_path = None      # 'hip', 'hip-train' (through autograd.PredictTailFn) or 'torch' after a predict_tf / predict call
+
+    def _tail_spec(self, device, n_act, b_channels, ce):
+        """The `_lib.TailSpec` of this model on `device`: the constants the tensor code of `_post_proc` / `_predict` precomputes,
+        computed the same way, plus the index tables; built once and rebuilt when `set_norm` replaces a norm tensor."""
+        ny, ne = self._norm('y', device), self._norm('e', device)
+        key = ('tail', str(device))
+        hit = self._norm_derived.get(key)
+        if hit is not None and hit[0] is ny and hit[1] is ne and hit[2] == (n_act, b_channels, ce):
+            return hit[3]
+        N, E = self.n_node, self.n_edge
+        f32 = lambda t: t.detach().to(device=device, dtype=torch.float32).contiguous()
+        i32 = lambda arr: torch.as_tensor(np.concatenate([np.asarray(arr, dtype=np.int64).reshape(-1), [0]]), dtype=torch.int32, device=device)
+        C = 3 + int(bool(self.if_flood))
+        span_y, mini_y = self._norm_parts('y', C, device)
+        span_e, mini_e = self._norm_parts('e', ce, device)
+        idx, ok = self._from_node_index(device)
+        area, pump = f32(self.area), f32(self.pump)
+        ne2 = ne[0, :, 2] if ne.shape[-1] > 2 else torch.ones(E, device=device)
+        tab = dict(is_outfall=f32(self.is_outfall), hmin=f32(self.hmin), hmax=f32(self.hmax), area_eps=area + 1e-6,
+                   ps=((area * torch.zeros_like(area).index_add_(0, idx, pump * ok)) > 0).float(),
+                   pump_in=f32(self.pump_in), pump_out=f32(self.pump_out), ny_in=f32(ny[0, :, 1]), ny_out=f32(ny[0, :, 2]),
+                   scale_in=f32((ny[0, :, 1] > 1e-3).float() / ny[0, :, 1]), scale_out=f32((ny[0, :, 2] > 1e-3).float() / ny[0, :, 2]),
+                   span_y=f32(span_y), mini_y=f32(mini_y), offset=f32(self.offset), pump=pump, pump_mask=f32((ne2 > 1e-3).float()),
+                   pump_den=f32(ne2), ehmax=f32(self.ehmax), from_ok=f32(ok), span_e=f32(span_e), mini_e=f32(mini_e))
+        # the (up to) two incidence entries of every link, for the backward gather
+        inc = self.graph.inc_n
+        rows, cols, vals = inc.rows(), np.asarray(inc.col, dtype=np.int64), np.asarray(inc.val, dtype=np.float64)
+        link_node, link_sign = np.full((E, 2), -1, dtype=np.int64), np.zeros((E, 2), dtype=np.float32)
+        count = np.bincount(cols, minlength=E)
+        if len(cols) and count.max() > 2:
+            return None                          # a link with more than two incidence entries: not a drainage link
+        order = np.argsort(cols, kind='stable')
+        slot = np.arange(len(cols)) - (np.cumsum(count) - count)[cols[order]]
+        link_node[cols[order], slot], link_sign[cols[order], slot] = rows[order], vals[order]
+        tab['link_sign'] = torch.as_tensor(np.concatenate([link_sign.reshape(-1), [0.0]]), dtype=torch.float32, device=device)
+        act_link, act_in, act_out = np.zeros(E, dtype=np.int64), np.zeros(N, dtype=np.int64), np.zeros(N, dtype=np.int64)
+        if self.act:
+            act_link[self._act_edge_index()] = np.arange(1, n_act + 1)
+            if not self.edge_fusion:
+                act_out[self.act_edges[:, 0]] = np.arange(1, n_act + 1)
+                act_in[self.act_edges[:, 1]] = np.arange(1, n_act + 1)
+
+        def lists(table):
+            members = [np.nonzero(table == k + 1)[0] for k in range(n_act)]
+            return np.concatenate([[0], np.cumsum([len(m) for m in members])]), np.concatenate(members + [np.zeros(0, dtype=np.int64)])
+        ints = dict(from_node=i32(idx.cpu().numpy()), act_link=i32(act_link), act_in=i32(act_in), act_out=i32(act_out), link_node=i32(link_node))
+        for name, table in (('al', act_link), ('ai', act_in), ('ao', act_out)):
+            ptr, members = lists(table)
+            ints[name + '_ptr'], ints[name + '_idx'] = i32(ptr), i32(members)
+        tab.update(ints)
+        spec = _lib.TailSpec(tab, N=N, E=E, cy=C - 2 if self.edge_fusion else C, ce=ce, n_act=n_act, b_channels=b_channels,
+                             edge_fusion=self.edge_fusion, tide=self.tide, has_offset=self._has_offset, act=self.act, pump_override=0,
+                             any_pump=self._has_any_pump, if_flood=bool(self.if_flood), epsilon=self.epsilon)
+        self._norm_derived[key] = (ny, ne, (n_act, b_channels, ce), spec)
+        return spec
+
+    def _predict_tail_hip(self, y, ey, a, b, nb_, x, np_form):
+        """Everything of `_predict` after the forward as `uds_predict_tail` (bit-identical to the tensor code below it), or None
+        where the tensor route stays: `fused_tail` off, a local model of `shard_emulator` (its flows cross the cut between the
+        link gates and the balance), shapes the kernels do not take (conv='False' models with other channel counts), NumPy mode
+        under autograd, and `b` or a norm that needs a gradient."""
+        if not self.fused_tail or not y.is_cuda or hasattr(self, '_flow_exchange'):
+            return None
+        B, T, C = y.shape[0], self.seq_out, 3 + int(bool(self.if_flood))
+        ce, bc = ey.shape[-1], b.shape[-1]
+        cy = C - 2 if self.edge_fusion else C
+        n_act = a.shape[-1] if self.act else 0
+        ny, ne = self._norm('y', y.device), self._norm('e', y.device)
+        if (tuple(y.shape) != (B, T, self.n_node, cy) or tuple(ey.shape) != (B, T, self.n_edge, ce) or not 2 <= ce <= 8 or
+                tuple(b.shape) != (B, T, self.n_node, bc) or x.shape[-1] < 1 or tuple(ny.shape[1:]) != (self.n_node, ny.shape[-1]) or
+                ny.shape[-1] < C or tuple(ne.shape[1:]) != (self.n_edge, ne.shape[-1]) or ne.shape[-1] < max(ce, 3 if self.act else 0) or
+                any(t.dtype != torch.float32 for t in (y, ey, b, x))):
+            return None
+        if self.act and (a is None or tuple(a.shape) != (B, T, n_act) or a.dtype != torch.float32 or not a.is_cuda or
+                         len(self._act_edge_index()) != n_act or (not self.edge_fusion and len(self.act_edges) != n_act)):
+            return None
+        if _ag.grad_on(b, nb_, *self._norms.values()):
+            return None
+        train = _ag.grad_on(y, ey, a if self.act else None, x)
+        if train and np_form:
+            return None
+        spec = self._tail_spec(y.device, n_act, bc, ce)
+        if spec is None:
+            return None
+        if self._inc_handle is None:
+            self._inc_handle = _lib.CsrHandle(self.graph.inc_n)
+        pump_override = self.act and (self._has_link_pump if np_form else self._has_pump)
+        depth_gate = 0.01 if np_form else 0.0
+        c = lambda t: t.detach().contiguous()
+        h0, runoff, a_ = x[:, -1, :, 0], c(b[..., 0]), a if self.act else None
+        if train:
+            self.last_tail_path = 'hip-train'
+            return _ag.PredictTailFn.apply(y, ey, a_, h0, c(nb_), runoff, self._inc_handle, self._inc_sign, spec, depth_gate, pump_override)
+        self.last_tail_path = 'hip'
+        return _lib.predict_tail(self._inc_handle, self._inc_sign, spec, c(y), c(ey), None if a_ is None else c(a_), c(nb_), runoff, c(h0),
+                                 depth_gate, pump_override)
 
     def _model(self, x, a, b, ex, ae=None, adj=None, fit=False):
         """emulator.py:400-438 on normalised tensors; `roll` > 0 = autoregressive chunks of seq_out steps."""

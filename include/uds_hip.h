@@ -374,6 +374,58 @@ int uds_roll_update(const uds_csr_t *inc_n, const float *sign, const float *span
                     int64_t ce, const float *b, int64_t B, int64_t so, int64_t T, int flood, float *x, float *ex,
                     float *preds, uds_stream_t stream);
 
+/* Constants of the predict tail (uds_predict_tail): everything Emulator._predict does after the network forward.  All
+ * pointers are device memory, fp32 / int32, built once per model (gnn_uds_amd/emulator.py: Emulator._tail_params); a table
+ * whose switch is off is not read but must still be given.  C = 3 + (if_flood != 0) is the channel count of the
+ * de-normalised node row [h, q_in, q_out, (flood)]; cy, the channel count of the network output, is C - 2 with edge_fusion
+ * (q_in / q_out come from the link flows) and C without. */
+typedef struct uds_tail {
+  /* sizes */
+  int32_t N, E, cy, ce, n_act, b_channels;
+  /* switches (0 / 1) */
+  int32_t edge_fusion, tide, has_offset, act, pump_override, any_pump, if_flood;
+  /* scalars: depth_gate = the depth above which a node pump runs (0 in predict_tf, 0.01 in predict); epsilon as the model's */
+  float depth_gate, epsilon;
+  /* per node (N): area_eps = area + 1e-6, ps = the pumped-storage mask, ny_in / ny_out = norm_y[0, :, 1 / 2],
+   * scale_in / scale_out = (ny > 1e-3) / ny; span_y / mini_y (N, C) = max - min / min of norm_y */
+  const float *is_outfall, *hmin, *hmax, *area_eps, *ps, *pump_in, *pump_out, *ny_in, *ny_out, *scale_in, *scale_out;
+  const float *span_y, *mini_y;
+  /* per link (E): pump_den = norm_e[0, :, 2], pump_mask = pump_den > 1e-3; from_node / from_ok = the link's from-node and
+   * whether it has one (a link from a node to itself has none); span_e / mini_e (E, ce) */
+  const float *offset, *pump, *pump_mask, *pump_den, *ehmax, *from_ok;
+  const float *span_e, *mini_e;
+  const int32_t *from_node;
+  /* settings: act_link (E) / act_in / act_out (N) = 1 + the action that sets the link / gates the node's inflow / outflow,
+   * 0 = none */
+  const int32_t *act_link, *act_in, *act_out;
+  /* backward only: the (up to) two incidence entries of every link, link_node (E, 2) (-1 = none) and link_sign (E, 2); and per
+   * action the links / inflow nodes / outflow nodes it drives as CSR lists (ptr: n_act + 1) */
+  const int32_t *link_node;
+  const float *link_sign;
+  const int32_t *al_ptr, *al_idx, *ai_ptr, *ai_idx, *ao_ptr, *ao_idx;
+} uds_tail_t;
+
+/* The tail of Emulator.predict_tf / predict (emulator.py:811-903) in two launches: tide, offset gate, rated-pump override,
+ * edge and node action gates, link -> node flow balance (as uds_flow_balance), de-normalisation, ehmax clamp, pumped-storage
+ * depth scan over T and constrain_tf.  y (B,T,N,cy) and ey (B,T,E,ce) are the network outputs, a (B,T,n_act) the settings
+ * (NULL without act), b_norm (B,T,N,b_channels) the normalised boundary (its last channel is the tide), runoff (B,T,N) the raw
+ * runoff, h0 (B,N) the last known depth.  out_y (B,T,N,C+1) = [h, q_in, q_out, (flood), q_w], out_ey (B,T,E,ce).  2 <= ce <= 8.
+ * Same operations in the same order as the tensor code, no fused multiply-add: bit-identical to it. */
+int uds_predict_tail(const uds_csr_t *inc_n, const float *sign, const uds_tail_t *p, const float *y, const float *ey,
+                     const float *a, const float *b_norm, const float *runoff, const float *h0, int64_t B, int64_t T,
+                     float *out_y, float *out_ey, uds_stream_t stream);
+
+/* Floats of workspace uds_predict_tail_backward needs. */
+int64_t uds_predict_tail_workspace_floats(int64_t N, int64_t E, int64_t B, int64_t T);
+
+/* Reverse mode of uds_predict_tail for the upstream gradients g_out_y / g_out_ey: dy, dey, da (NULL without act), dh0 in the
+ * shapes of y, ey, a, h0.  Two launches plus one per-action reduction, no atomics: deterministic.  Comparisons carry no
+ * gradient; max / min split evenly at a tie; clamp(min = 0) passes at 0; the flow balance passes nothing at a flow of 0. */
+int uds_predict_tail_backward(const uds_csr_t *inc_n, const float *sign, const uds_tail_t *p, const float *y,
+                              const float *ey, const float *a, const float *b_norm, const float *runoff,
+                              const float *h0, int64_t B, int64_t T, const float *g_out_y, const float *g_out_ey,
+                              float *dy, float *dey, float *da, float *dh0, float *workspace, uds_stream_t stream);
+
 /* Floats of workspace uds_gat_forward needs: S * n * (d + 2). */
 int64_t uds_gat_workspace_floats(int64_t n, int64_t S, int64_t d);
 
