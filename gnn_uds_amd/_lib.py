@@ -87,6 +87,8 @@ SYMBOLS = {
     'uds_rowgemm_forward_cat': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int,
                                          _c_ptr, _c_i64, _c_i64, _c_ptr]),
     'uds_dense_cumsum': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr]),
+    'uds_conv_stack_plan': (_c_int, [_c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_conv_stack_forward': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr]),
     'uds_cumsum_act': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
     'uds_flow_balance': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     'uds_gat_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64]),
@@ -949,6 +951,39 @@ def dense_cumsum_heads(x, packed, bias, res, act, head_a, hidden=(), head_f=None
     if out.numel():
         _check(lib.uds_dense_cumsum_heads(_dev(x, 'x'), B, T, R, packed.data_ptr(), _dev(bias, 'bias', True), _dev(res, 'res', True), ACT[act],
                                           ctypes.byref(hd), _dev(out, 'out'), _stream()), 'uds_dense_cumsum_heads')
+    return out
+
+
+class _ConvStack(ctypes.Structure):
+    """uds_conv_stack_t"""
+    _fields_ = [('packed', ctypes.c_void_p * 3), ('bias', ctypes.c_void_p * 3), ('n_layers', ctypes.c_int32), ('act', ctypes.c_int32)]
+
+
+def conv_stack_plan(B, T, R, L):
+    """(n_seg, seg_len, halo): the time segmentation conv_stack_forward uses for n_seg = 0 (uds_conv_stack_plan, host only)."""
+    n_seg, seg_len, halo = _c_i64(), _c_i64(), _c_i64()
+    _check(load().uds_conv_stack_plan(B, T, R, L, ctypes.byref(n_seg), ctypes.byref(seg_len), ctypes.byref(halo)), 'uds_conv_stack_plan')
+    return n_seg.value, seg_len.value, halo.value
+
+
+def conv_stack_forward(x, layers, act='linear', n_seg=0, out=None):
+    """A stack of len(layers) (2 or 3) causal Conv1D(64 -> 64, kernel 3) layers with dilations 1, 2[, 4] and one activation in ONE
+    launch (uds_conv_stack_forward): x (B,T,R,64), layers = [(packed, bias), ...] with packed = rowgemm_pack of the layer's
+    (192, 64) kernel and bias (64,) or None.  Bit-identical to the layers run one by one on the streaming-Conv1D route.  n_seg = 0:
+    the planner's time segmentation, else that many segments.  out: the result's tensor, allocated when None."""
+    lib = load()
+    if x.dim() != 4 or x.shape[-1] != 64:
+        raise UdsError('conv_stack_forward: needs x (B,T,R,64), got %r' % (tuple(x.shape),))
+    B, T, R = x.shape[:3]
+    st = _ConvStack()
+    st.n_layers, st.act = len(layers), ACT[act]
+    for i, (pk, bs) in enumerate(layers[:3]):
+        st.packed[i], st.bias[i] = pk.data_ptr(), _dev(bs, 'bias', True)
+    out = _out(out, (B, T, R, 64), x, 'out')
+    if out.numel() == 0:
+        return _nothing_to_launch(x, 'x', out)
+    _check(lib.uds_conv_stack_forward(_dev(x, 'x'), B, T, R, ctypes.byref(st), int(n_seg), _dev(out, 'out'), _stream()),
+           'uds_conv_stack_forward')
     return out
 
 

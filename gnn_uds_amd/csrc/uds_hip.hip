@@ -25,6 +25,7 @@
 #include "kernels_rowgemm.hpp"
 #include "kernels_wgrad.hpp"
 #include "kernels_conv_stream.hpp"
+#include "kernels_conv_stack.hpp"
 #include "kernels_fused128.hpp"
 #include "kernels_gemm.hpp"
 #include "kernels_recurrent.hpp"
@@ -697,6 +698,49 @@ int uds_dense_cumsum(const float *x, int64_t B, int64_t T, int64_t R, const void
 int uds_dense_cumsum_heads(const float *x, int64_t B, int64_t T, int64_t R, const void *packed, const float *bias, const float *res, int act,
                            const uds_heads_t *heads, float *out, uds_stream_t stream) {
   return dense_cumsum("uds_dense_cumsum_heads", true, x, B, T, R, packed, bias, res, act, heads, out, stream);
+}
+
+int uds_conv_stack_plan(int64_t B, int64_t T, int64_t R, int n_layers, int64_t *n_seg, int64_t *seg_len, int64_t *halo) {
+  UDS_REQUIRE(n_seg && seg_len && halo, "uds_conv_stack_plan: NULL n_seg/seg_len/halo");
+  UDS_REQUIRE(n_layers == 2 || n_layers == 3, "uds_conv_stack_plan: stacks of 2 or 3 layers (got %d)", n_layers);
+  UDS_REQUIRE(B >= 0 && T > 0 && R > 0, "uds_conv_stack_plan: bad sizes B=%lld T=%lld R=%lld", (long long)B, (long long)T, (long long)R);
+  uds::conv_stack_plan(B, T, R, n_layers, *n_seg, *seg_len);
+  *halo = uds::conv_stack_halo(n_layers);
+  return UDS_OK;
+}
+
+int uds_conv_stack_forward(const float *x, int64_t B, int64_t T, int64_t R, const uds_conv_stack_t *layers, int64_t n_seg, float *out,
+                           uds_stream_t stream) {
+  UDS_REQUIRE(x && out && layers, "uds_conv_stack_forward: NULL x/out/layers");
+  const int L = layers->n_layers;
+  UDS_REQUIRE(L == 2 || L == 3, "uds_conv_stack_forward: stacks of 2 or 3 layers (got %d)", L);
+  for (int i = 0; i < L; ++i) UDS_REQUIRE(layers->packed[i], "uds_conv_stack_forward: layer %d has no weights", i);
+  UDS_REQUIRE(B >= 0 && T > 0 && R > 0, "uds_conv_stack_forward: bad sizes B=%lld T=%lld R=%lld", (long long)B, (long long)T, (long long)R);
+  UDS_REQUIRE(layers->act >= UDS_ACT_LINEAR && layers->act <= UDS_ACT_HARD_SIGMOID, "uds_conv_stack_forward: unknown activation %d",
+              (int)layers->act);
+  for (int i = 0; i < L; ++i)
+    UDS_REQUIRE(aligned16(layers->packed[i]) && aligned16(layers->bias[i]), "uds_conv_stack_forward: pointers must be 16-byte aligned");
+  UDS_REQUIRE(aligned16(x) && aligned16(out), "uds_conv_stack_forward: pointers must be 16-byte aligned");
+  UDS_REQUIRE(n_seg >= 0 && n_seg <= T, "uds_conv_stack_forward: n_seg %lld outside [0, T = %lld]", (long long)n_seg, (long long)T);
+  UDS_REQUIRE(B * T * R < INT32_MAX, "uds_conv_stack_forward: %lld rows exceed the int32 row index", (long long)(B * T * R));
+  {      // segments re-read halo steps of x that another segment's wave may already have overwritten
+    const uintptr_t xb = reinterpret_cast<uintptr_t>(x), ob = reinterpret_cast<uintptr_t>(out), bytes = (uintptr_t)(B * T * R) * 64 * 4;
+    UDS_REQUIRE(xb + bytes <= ob || ob + bytes <= xb, "uds_conv_stack_forward: out overlaps x");
+  }
+  if (B == 0) return UDS_OK;
+  uds::ConvStackArgs a{};
+  a.x = x, a.out = out;
+  for (int i = 0; i < L; ++i) a.packed[i] = reinterpret_cast<const uint4 *>(layers->packed[i]), a.bias[i] = layers->bias[i];
+  a.B = (int)B, a.T = (int)T, a.R = (int)R, a.act = layers->act, a.n_blocks = (int)((R + 15) / 16);
+  int64_t ns = n_seg, sl = 0;
+  if (ns == 0) {
+    uds::conv_stack_plan(B, T, R, L, ns, sl);
+  } else {
+    sl = (T + ns - 1) / ns;
+    ns = (T + sl - 1) / sl;
+  }
+  a.n_seg = (int)ns, a.seg_len = (int)sl;
+  return launched("uds_conv_stack_forward", uds::launch_conv_stack(a, L, static_cast<hipStream_t>(stream)));
 }
 
 int uds_cumsum_act(const float *x, const float *res, int64_t B, int64_t T, int64_t R, int64_t F, int act, float *out,

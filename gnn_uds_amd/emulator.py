@@ -550,6 +550,7 @@ class Emulator(nn.Module):
         dr = (lambda t: self._drop(t, True)) if drop else None
         nb = X.shape[0]
         c = lambda t: t.contiguous()
+        self.last_temporal_path = 'layers'
         adj_mask = None
         if ADJ is not None:
             if not (self.act and self.use_adj):
@@ -589,8 +590,33 @@ class Emulator(nn.Module):
                 sink['block1' if block is self.block1 else 'block2'] = [bt(a) if isinstance(a, torch.Tensor) else (bt(a[0]), bt(a[1])) for a in got]
             return xs.reshape(nb, T, self.n_node, -1), es.reshape(nb, T, self.n_edge, -1)
 
+        def stack(mods, t):
+            """One side's temporal stack as ONE launch (uds_conv_stack_forward: the layers in between never reach memory), or None
+            when it is not the shape that kernel takes: two or three Conv1D(64 -> 64, kernel 3) layers with dilations 1, 2[, 4],
+            one activation, the matrix-core precision, no gradient, and enough 16-row streams to fill the device."""
+            mods = list(mods)
+            if not (self.fused_temporal and len(mods) in (2, 3) and t.shape[-1] == 64 and all(isinstance(m, Conv1D) for m in mods)):
+                return None
+            if not all(tuple(m.kernel.shape) == (3, 64, 64) and m.dilation_rate == 2 ** i and m.activation == mods[0].activation
+                       and m.precision == 'bf16x3' for i, m in enumerate(mods)):
+                return None
+            if t.shape[0] * ((t.shape[2] + 15) // 16) < self.STACK_MIN_STREAMS or _ag.grad_on(t, *[p for m in mods for p in (m.kernel, m.bias)]):
+                return None
+            return _lib.conv_stack_forward(c(t), [(_packed_kernel(m, m.kernel.reshape(192, 64)), m.bias) for m in mods], mods[0].activation)
+
         def temporal(mods_x, mods_e, x, e):
-            """The two temporal stacks (:244-257): layer by layer; a pair of small Conv1D layers of one shape goes out as ONE launch."""
+            """The two temporal stacks (:244-257): layer by layer; a pair of small Conv1D layers of one shape goes out as ONE launch.
+            With `fused_temporal`, a side's whole stack is one launch where `stack` takes it (same bits as its layers)."""
+            sx, se = stack(mods_x, x), stack(mods_e, e)
+            if sx is not None or se is not None:
+                self.last_temporal_path = 'stack'
+                if sx is None:
+                    for ly in mods_x:
+                        x = ly(x)
+                if se is None:
+                    for ly in mods_e:
+                        e = ly(e)
+                return (x if sx is None else sx), (e if se is None else se)
             if len(mods_x) != len(mods_e):
                 for ly in mods_x:
                     x = ly(x)
@@ -906,8 +932,13 @@ class Emulator(nn.Module):
         q_w, y = self.constrain_tf(y, b[..., :1], x[:, -1:, :, 0])
         return torch.cat([y, q_w.unsqueeze(-1)], dim=-1), ey
 
+    # ------------------------------------------------------------------ a temporal stack as one launch
+    fused_temporal = False     # True: a side's Conv1D stack goes out as ONE uds_conv_stack_forward launch where `forward` finds its shape
+    STACK_MIN_STREAMS = 256    # (batch element, 16-row block) streams below which the layers stay (they leave k_conv3_stream there too)
+    last_temporal_path = None  # 'stack' (a side took the one-launch kernel) or 'layers' after a forward
+
     # ------------------------------------------------------------------ the predict tail as one HIP operator
-    fused_tail = True          # False: `_predict` keeps its tensor code for everything after the forward
+    fused_tail = True         # False: `_predict` keeps its tensor code for everything after the forward
     last_tail_path = None      # 'hip', 'hip-train' (through autograd.PredictTailFn) or 'torch' after a predict_tf / predict call
 
     def _tail_spec(self, device, n_act, b_channels, ce):

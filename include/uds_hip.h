@@ -318,6 +318,23 @@ typedef struct {
 int uds_dense_cumsum_heads(const float *x, int64_t B, int64_t T, int64_t R, const void *packed, const float *bias,
                            const float *res, int act, const uds_heads_t *heads, float *out, uds_stream_t stream);
 
+/* A whole temporal stack in one launch: n_layers (2 or 3) causal Conv1D(64 -> 64, kernel 3, dilation 2^i) layers with one
+ * activation applied back to back to x (B,T,R,64) -> out (B,T,R,64); the layers in between never reach memory (`tem1_x`,
+ * `tem1_e`, `tem2_x`, `tem2_e`).  packed[i] = uds_rowgemm_pack of layer i's (3*64, 64) kernel, bias[i] 64 floats or NULL.
+ * Bit-identical to n_layers uds_rowgemm_forward calls (taps 3, dil 2^i) on the streaming-Conv1D route.  Time is cut into n_seg
+ * segments, each of which re-computes a halo of sum_i 2 * 2^i steps (6 / 14): n_seg = 0 takes uds_conv_stack_plan's, else
+ * 1 <= n_seg <= T is used as given (the result does not depend on it).  `out` must not overlap `x`.  Any number of rows: whether
+ * the launch pays is the caller's call.  uds_conv_stack_plan is host only (no device).
+ *                                                                            emulator.py:154-157,244-257,299-310 */
+typedef struct {
+  const void *packed[3];
+  const float *bias[3];
+  int32_t n_layers, act;
+} uds_conv_stack_t;
+int uds_conv_stack_plan(int64_t B, int64_t T, int64_t R, int n_layers, int64_t *n_seg, int64_t *seg_len, int64_t *halo);
+int uds_conv_stack_forward(const float *x, int64_t B, int64_t T, int64_t R, const uds_conv_stack_t *layers, int64_t n_seg,
+                           float *out, uds_stream_t stream);
+
 /* out[b,t,r,:] = act(cumsum_t(x)[b,t,r,:] + res[b,0,r,:]); x, out (B,T,R,F), res (B,1,R,F) or NULL; F % 4 == 0.
  * The resnet head of the emulator.                                          emulator.py:313-320 */
 int uds_cumsum_act(const float *x, const float *res, int64_t B, int64_t T, int64_t R, int64_t F, int act,
