@@ -122,6 +122,9 @@ SYMBOLS = {
     'uds_predict_tail': (_c_int, [_c_ptr] * 9 + [_c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr]),
     'uds_predict_tail_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
     'uds_predict_tail_backward': (_c_int, [_c_ptr] * 9 + [_c_i64, _c_i64] + [_c_ptr] * 8),
+    'uds_fit_tail': (_c_int, [_c_ptr] * 15 + [_c_i64, _c_i64, _c_i64, _c_int] + [_c_ptr] * 5),
+    'uds_fit_tail_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    'uds_fit_tail_backward': (_c_int, [_c_ptr] * 15 + [_c_i64, _c_i64, _c_i64, _c_int] + [_c_ptr] * 7),
     'uds_spatial_workspace_floats': (_c_i64, [_c_ptr, _c_i64, _c_i64, _c_i64]),
     'uds_spatial_packed_bytes': (_c_i64, []),
     'uds_spatial_pack_weights': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr]),
@@ -1125,6 +1128,78 @@ def predict_tail_backward(handle, sign, spec, y, ey, a, b_norm, runoff, h0, g_ou
                                          _dev(g_out_ey, 'g_out_ey'), _dev(dy, 'dy'), _dev(dey, 'dey'), _dev(da, 'da', not s['act']), _dev(dh0, 'dh0'),
                                          _dev(ws, 'workspace'), _stream()), 'uds_predict_tail_backward')
     return dy, dey, da, dh0
+
+
+def _fit_tail_operands(what, handle, spec, y, ey, a, b_norm, y_true, ey_true, lw):
+    """The checks uds_fit_tail and uds_fit_tail_backward share -> (B, T, cyt, balance, the ABI's leading arguments).  lw: the loss
+    operands, nwei (N, 3 + balance) / poswei (N) / ewei (E) and, with balance, qw_den / span_b / mini_b (N)."""
+    s = spec.scalars
+    if y is None or y.dim() != 4:
+        raise UdsError('%s: y must be (B, T, N, cy)' % what)
+    B, T = y.shape[:2]
+    N, E = s['N'], s['E']
+    balance = int(bool(lw.get('balance')))
+    cyt = int(y_true.shape[-1]) if isinstance(y_true, torch.Tensor) and y_true.dim() == 4 else 0
+    want = dict(y=(B, T, N, s['cy']), ey=(B, T, E, s['ce']), b_norm=(B, T, N, s['b_channels']), y_true=(B, T, N, cyt), ey_true=(B, T, E, s['ce']),
+                nwei=(N, 3 + balance), poswei=(N,), ewei=(E,))
+    if s['act']:
+        want['a'] = (B, T, s['n_act'])
+    if balance:
+        want.update(qw_den=(N,), span_b=(N,), mini_b=(N,))
+    got = dict(y=y, ey=ey, a=a, b_norm=b_norm, y_true=y_true, ey_true=ey_true, **{k: lw.get(k) for k in ('nwei', 'poswei', 'ewei', 'qw_den', 'span_b', 'mini_b')})
+    for name, shape in want.items():
+        if not isinstance(got[name], torch.Tensor) or tuple(got[name].shape) != shape:
+            raise UdsError('%s: %s must be %r, got %r' % (what, name, shape, tuple(got[name].shape) if isinstance(got[name], torch.Tensor) else got[name]))
+        if got[name].dtype != torch.float32:
+            raise UdsError('%s: %s must be float32, got %s' % (what, name, got[name].dtype))
+    if cyt < 3:
+        raise UdsError('%s: y_true needs at least 3 channels, got %d' % (what, cyt))
+    if handle.n_rows != N or handle.n_cols != E:
+        raise UdsError('%s: the incidence pattern is %d x %d, the model has %d nodes and %d links' % (what, handle.n_rows, handle.n_cols, N, E))
+    opt = lambda k: _dev(lw[k], k) if balance else None
+    return B, T, cyt, balance, lambda p: (
+        handle.ptr, _dev(lw['sign'], 'sign'), ctypes.addressof(p), _dev(y, 'y'), _dev(ey, 'ey'), _dev(a, 'a') if s['act'] else None,
+        _dev(b_norm, 'b_norm'), _dev(y_true, 'y_true'), _dev(ey_true, 'ey_true'), _dev(lw['nwei'], 'nwei'), _dev(lw['poswei'], 'poswei'),
+        _dev(lw['ewei'], 'ewei'), opt('qw_den'), opt('span_b'), opt('mini_b'), B, T, cyt, balance)
+
+
+def fit_tail(handle, spec, y, ey, a, b_norm, y_true, ey_true, lw, pump_override=False, out_y=None, out_ey=None):
+    """Everything after the network forward of Emulator.fit_eval (include/uds_hip.h: uds_fit_tail): returns out_y (B,T,N,3 or 4) and
+    out_ey (B,T,E,ce), what post_proc_tf returns, and loss_sums (3,) = the node / flood / edge loss sums before the division by the
+    sample count.  spec: a TailSpec; lw: the loss operands plus 'sign', the incidence values (see _fit_tail_operands)."""
+    lib = load()
+    B, T, cyt, balance, lead = _fit_tail_operands('fit_tail', handle, spec, y, ey, a, b_norm, y_true, ey_true, lw)
+    s = spec.scalars
+    out_y = _out(out_y, (B, T, s['N'], 3 + int(bool(s['if_flood']))), y, 'out_y')
+    out_ey = _out(out_ey, (B, T, s['E'], s['ce']), y, 'out_ey')
+    if out_y.numel() == 0:
+        return out_y, out_ey, torch.zeros(3, device=y.device, dtype=torch.float32)
+    sums = torch.empty(3, device=y.device, dtype=torch.float32)
+    ws = torch.empty(int(lib.uds_fit_tail_workspace_floats(s['N'], s['E'], B, T)), device=y.device, dtype=torch.float32)
+    p = spec.struct(0.0, pump_override)
+    _check(lib.uds_fit_tail(*lead(p), _dev(out_y, 'out_y'), _dev(out_ey, 'out_ey'), _dev(sums, 'loss_sums'), _dev(ws, 'workspace'), _stream()),
+           'uds_fit_tail')
+    return out_y, out_ey, sums
+
+
+def fit_tail_backward(handle, spec, y, ey, a, b_norm, y_true, ey_true, lw, g_loss, g_out_y=None, g_out_ey=None, pump_override=False):
+    """Reverse mode of fit_tail: (dy, dey) for g_loss (3,) on the device and the optional gradients arriving at out_y / out_ey."""
+    lib = load()
+    B, T, cyt, balance, lead = _fit_tail_operands('fit_tail_backward', handle, spec, y, ey, a, b_norm, y_true, ey_true, lw)
+    s = spec.scalars
+    if not isinstance(g_loss, torch.Tensor) or tuple(g_loss.shape) != (3,):
+        raise UdsError('fit_tail_backward: g_loss must be (3,), got %r' % (tuple(g_loss.shape) if isinstance(g_loss, torch.Tensor) else g_loss,))
+    if ((g_out_y is not None and tuple(g_out_y.shape) != (B, T, s['N'], 3 + int(bool(s['if_flood'])))) or
+            (g_out_ey is not None and tuple(g_out_ey.shape) != tuple(ey.shape))):
+        raise UdsError('fit_tail_backward: the gradients of out_y / out_ey do not have the shapes of the outputs')
+    dy, dey = torch.empty_like(y), torch.empty_like(ey)
+    if dy.numel() == 0:
+        return dy, dey
+    ws = torch.empty(int(lib.uds_fit_tail_workspace_floats(s['N'], s['E'], B, T)), device=y.device, dtype=torch.float32)
+    p = spec.struct(0.0, pump_override)
+    _check(lib.uds_fit_tail_backward(*lead(p), _dev(g_loss, 'g_loss'), _dev(g_out_y, 'g_out_y', True), _dev(g_out_ey, 'g_out_ey', True),
+                                     _dev(dy, 'dy'), _dev(dey, 'dey'), _dev(ws, 'workspace'), _stream()), 'uds_fit_tail_backward')
+    return dy, dey
 
 
 def csr_spmm(handle, val, x, bias=None, act='linear', out=None):

@@ -545,6 +545,32 @@ class PredictTailFn(torch.autograd.Function):
         return dy, dey, da, dh0, None, None, None, None, None, None, None
 
 
+class FitTailFn(torch.autograd.Function):
+    """The tail of a training step (`Emulator.fit_eval` / `fit_grad_norm` after the network forward) as one HIP forward and one HIP
+    backward (include/uds_hip.h: uds_fit_tail / uds_fit_tail_backward): (out_y, out_ey, loss_sums).  Differentiable in y and ey
+    only; the settings, the boundary, the targets and the weights are constants here (the emulator keeps the tensor route when one
+    of them needs a gradient).  The backward keeps nothing of its own between calls: it may run more than once on one forward
+    (`fit_grad_norm` takes two gradients with retain_graph)."""
+
+    @staticmethod
+    def forward(ctx, y, ey, a, b_norm, y_true, ey_true, handle, spec, lw, pump_override):
+        y, ey = y.contiguous(), ey.contiguous()
+        ctx.save_for_backward(y, ey, b_norm, y_true, ey_true, *([] if a is None else [a]))
+        ctx.tail = (handle, spec, lw, pump_override)
+        ctx.set_materialize_grads(False)          # an output nothing reads hands None to the backward: no zero tensor, a NULL pointer
+        out_y, out_ey, sums = _lib.fit_tail(handle, spec, y, ey, a, b_norm, y_true, ey_true, lw, pump_override)
+        return out_y, out_ey, sums
+
+    @staticmethod
+    def backward(ctx, g_y, g_ey, g_sums):
+        y, ey, b_norm, y_true, ey_true, *rest = ctx.saved_tensors
+        handle, spec, lw, pump_override = ctx.tail
+        g_sums = torch.zeros(3, device=y.device, dtype=torch.float32) if g_sums is None else g_sums.contiguous()
+        dy, dey = _lib.fit_tail_backward(handle, spec, y, ey, rest[0] if rest else None, b_norm, y_true, ey_true, lw, g_sums,
+                                         None if g_y is None else g_y.contiguous(), None if g_ey is None else g_ey.contiguous(), pump_override)
+        return dy, dey, None, None, None, None, None, None, None, None
+
+
 def grad_on(*tensors):
     """True when autograd is recording and one of the tensors needs a gradient: the modules then take the Function path."""
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)

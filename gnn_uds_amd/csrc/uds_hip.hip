@@ -31,6 +31,7 @@
 #include "kernels_recurrent.hpp"
 #include "kernels_recurrent_bwd.hpp"
 #include "kernels_tail.hpp"
+#include "kernels_fit_tail.hpp"
 #include "tile_plan.hpp"
 
 namespace {
@@ -1076,6 +1077,67 @@ int uds_predict_tail_backward(const uds_csr_t *inc_n, const float *sign, const u
   t.ws_qi = workspace; t.ws_qo = workspace + bn; t.ws_prev = workspace + 2 * bn; t.ws_set = workspace + 3 * bn;
   t.B = (int)B; t.T = (int)T; t.C = 3 + (p->if_flood ? 1 : 0);
   return launched(what, uds::launch_tail_backward(t, static_cast<hipStream_t>(stream)));
+}
+
+// ---- fit tail.  uds_fit_tail and uds_fit_tail_backward share fit_tail_check: tail_check (the fit tail has no runoff / previous
+// depth operand: b_norm stands in for both) and the checks of the loss operands; it fills everything the two entries have in common.
+int64_t uds_fit_tail_workspace_floats(int64_t N, int64_t E, int64_t B, int64_t T) {
+  if (N < 0 || E < 0 || B < 0 || T < 0) return 0;
+  return std::max<int64_t>(3 * uds::FIT_MAX_BLOCKS, 2 * align4(B * T * N));
+}
+
+static int fit_tail_check(const char *what, const uds_csr_t *inc_n, const float *sign, const uds_tail_t *p, const float *y, const float *ey,
+                          const float *a, const float *b_norm, const float *y_true, const float *ey_true, const float *nwei, const float *poswei,
+                          const float *ewei, const float *qw_den, const float *span_b, const float *mini_b, int64_t B, int64_t T, int64_t cyt,
+                          int balance, const float *workspace, std::initializer_list<const void *> more, uds::FitTailArgs &f) {
+  UDS_REQUIRE(y_true && ey_true && nwei && poswei && ewei && workspace, "%s: NULL y_true/ey_true/nwei/poswei/ewei/workspace", what);
+  UDS_REQUIRE(balance == 0 || balance == 1, "%s: balance=%d (0 or 1)", what, balance);
+  UDS_REQUIRE(!balance || (qw_den && span_b && mini_b), "%s: balance needs qw_den, span_b and mini_b", what);
+  UDS_REQUIRE(cyt >= 3 && cyt <= 16, "%s: cyt=%lld (3 <= cyt <= 16)", what, (long long)cyt);
+  UDS_REQUIRE(aligned16(y_true) && aligned16(ey_true) && aligned16(workspace), "%s: tensors must be 16-byte aligned", what);
+  if (int rc = tail_check(what, inc_n, sign, p, y, ey, a, b_norm, b_norm, b_norm, B, T, more)) return rc;
+  f.t.p = *p;
+  f.t.rowptr = inc_n->d_rowptr; f.t.col = inc_n->d_col; f.t.sign = sign;
+  f.t.y = y; f.t.ey = ey; f.t.a = a; f.t.b_norm = b_norm;
+  f.t.B = (int)B; f.t.T = (int)T; f.t.C = 3 + (p->if_flood ? 1 : 0);
+  f.y_true = y_true; f.ey_true = ey_true; f.nwei = nwei; f.poswei = poswei; f.ewei = ewei;
+  f.qw_den = qw_den; f.span_b = span_b; f.mini_b = mini_b;
+  f.cyt = (int)cyt; f.balance = balance;
+  f.node_blocks = (int)uds::fit_blocks(B * T * p->N); f.link_blocks = (int)uds::fit_blocks(B * T * p->E);
+  return UDS_OK;
+}
+
+int uds_fit_tail(const uds_csr_t *inc_n, const float *sign, const uds_tail_t *p, const float *y, const float *ey, const float *a,
+                 const float *b_norm, const float *y_true, const float *ey_true, const float *nwei, const float *poswei, const float *ewei,
+                 const float *qw_den, const float *span_b, const float *mini_b, int64_t B, int64_t T, int64_t cyt, int balance, float *out_y,
+                 float *out_ey, float *loss_sums, float *workspace, uds_stream_t stream) {
+  const char *what = "uds_fit_tail";
+  UDS_REQUIRE(out_y && out_ey && loss_sums, "%s: NULL output", what);
+  uds::FitTailArgs f{};
+  if (int rc = fit_tail_check(what, inc_n, sign, p, y, ey, a, b_norm, y_true, ey_true, nwei, poswei, ewei, qw_den, span_b, mini_b, B, T, cyt,
+                              balance, workspace, {out_y, out_ey}, f))
+    return rc;
+  if (B == 0) return UDS_OK;
+  f.t.out_y = out_y; f.t.out_ey = out_ey; f.loss_sums = loss_sums;
+  f.part_node = workspace; f.part_flood = workspace + uds::FIT_MAX_BLOCKS; f.part_edge = workspace + 2 * uds::FIT_MAX_BLOCKS;
+  return launched(what, uds::launch_fit_tail_forward(f, static_cast<hipStream_t>(stream)));
+}
+
+int uds_fit_tail_backward(const uds_csr_t *inc_n, const float *sign, const uds_tail_t *p, const float *y, const float *ey, const float *a,
+                          const float *b_norm, const float *y_true, const float *ey_true, const float *nwei, const float *poswei,
+                          const float *ewei, const float *qw_den, const float *span_b, const float *mini_b, int64_t B, int64_t T, int64_t cyt,
+                          int balance, const float *g_loss, const float *g_out_y, const float *g_out_ey, float *dy, float *dey,
+                          float *workspace, uds_stream_t stream) {
+  const char *what = "uds_fit_tail_backward";
+  UDS_REQUIRE(g_loss && dy && dey, "%s: NULL g_loss / gradient output", what);
+  uds::FitTailArgs f{};
+  if (int rc = fit_tail_check(what, inc_n, sign, p, y, ey, a, b_norm, y_true, ey_true, nwei, poswei, ewei, qw_den, span_b, mini_b, B, T, cyt,
+                              balance, workspace, {g_out_y, g_out_ey, dy, dey}, f))
+    return rc;
+  if (B == 0) return UDS_OK;
+  f.g_loss = g_loss; f.t.g_out_y = g_out_y; f.t.g_out_ey = g_out_ey; f.t.dy = dy; f.t.dey = dey;
+  f.t.ws_qi = workspace; f.t.ws_qo = workspace + align4(B * T * p->N);
+  return launched(what, uds::launch_fit_tail_backward(f, static_cast<hipStream_t>(stream)));
 }
 
 int uds_csr_spmm(const uds_csr_t *csr, const float *val, const float *x, int64_t S, int64_t F, const float *bias,

@@ -1203,6 +1203,100 @@ class Emulator(nn.Module):
         weight = lw['poswei'] * y[..., -2] + lw['nwei'][:, -1] * (1 - y[..., -2])
         return self._bce(y[..., -2:-1], preds[..., -1:], weight)
 
+    # ------------------------------------------------------------------ the training tail as one HIP operator
+    fused_fit_tail = True      # False: `fit_eval` / `fit_grad_norm` keep their tensor code for everything after the forward
+    last_fit_tail_path = None  # 'hip' (through autograd.FitTailFn) or 'torch' after a fit_eval / fit_grad_norm call
+
+    def _fit_tail_spec(self, x, a, b, y, ey):
+        """(`_lib.TailSpec`, loss operands) when the tail of this step runs as `uds_fit_tail`, or None where the tensor route stays:
+        `fused_fit_tail` off, a local model of `shard_emulator` (its flows cross the cut between the link gates and the balance),
+        channel counts the kernels do not take (conv='False' models with a wider state; the rule of `_predict_tail_hip`), and a
+        setting, boundary, target or norm that needs a gradient (the operator is differentiable in the network outputs only)."""
+        if not self.fused_fit_tail or not x.is_cuda or hasattr(self, '_flow_exchange'):
+            return None
+        if 'y' not in self._norms or 'e' not in self._norms or (self.balance and 'b' not in self._norms):
+            return None                          # the kernels read the norms a plain model's tensor code never asks for
+        dev, N, E = x.device, self.n_node, self.n_edge
+        B, T = x.shape[0], self.seq_out * max(self.roll, 1)
+        ce, C = self.e_out, 3 + int(bool(self.if_flood))
+        n_act = a.shape[-1] if self.act and a is not None else 0
+        ny, ne, nb = self._norm('y', dev), self._norm('e', dev), self._norm('b', dev) if self.balance else None
+        if (self.n_out != (1 if self.edge_fusion else 3) or not 2 <= ce <= 8 or b.dim() != 4 or tuple(b.shape[:3]) != (B, T, N) or
+                y.dim() != 4 or tuple(y.shape[:3]) != (B, T, N) or y.shape[-1] < 3 or tuple(ey.shape) != (B, T, E, ce) or
+                tuple(ny.shape[1:]) != (N, ny.shape[-1]) or ny.shape[-1] < C or tuple(ne.shape[1:]) != (E, ne.shape[-1]) or
+                ne.shape[-1] < max(ce, 3 if self.act else 0) or (nb is not None and tuple(nb.shape[1:]) != (N, nb.shape[-1])) or
+                any(t.dtype != torch.float32 or not t.is_cuda for t in (x, b, y, ey))):
+            return None
+        if self.act and (a is None or tuple(a.shape) != (B, T, n_act) or a.dtype != torch.float32 or not a.is_cuda):
+            return None
+        if self.act:            # every setting drives its links (and, without edge fusion, its two nodes): a fact of the model, looked up once
+            ok = self._idx_cache.get(('fit_tail_act', n_act))       # (`_act_edge_index` walks the link list: 5 ms on 250 000 links)
+            if ok is None:
+                ok = self._idx_cache[('fit_tail_act', n_act)] = (len(self._act_edge_index()) == n_act and
+                                                                 (self.edge_fusion or len(self.act_edges) == n_act))
+            if not ok:
+                return None
+        if _ag.grad_on(a if self.act else None, b, y, ey, *self._norms.values()):
+            return None
+        spec = self._tail_spec(dev, n_act, b.shape[-1], ce)
+        if spec is None:
+            return None
+        lw = self._loss_setup(dev)
+        hit = self._norm_derived.get(('fit_tail', str(dev)))
+        if hit is None or hit[0] is not ny or hit[1] is not nb or hit[2] is not lw:
+            ops = dict(nwei=lw['nwei'].contiguous(), poswei=lw['poswei'].contiguous(), ewei=lw['ewei'].contiguous(), balance=self.balance)
+            if self.balance:
+                ops.update(qw_den=ny[0, :, -1].contiguous(), span_b=(nb[0, :, 0] - nb[1, :, 0]).contiguous(), mini_b=nb[1, :, 0].contiguous())
+            hit = self._norm_derived[('fit_tail', str(dev))] = (ny, nb, lw, ops)
+        if self._inc_handle is None:
+            self._inc_handle = _lib.CsrHandle(self.graph.inc_n)
+        return spec, dict(hit[3], sign=self._inc_sign)
+
+    def _fit_losses(self, x, a, b, y, ex, ey, ae, fit, flood=False):
+        """(node_loss, flood_loss or None, edge_loss) of one step on NORMALISED tensors, for `fit_eval` and `fit_grad_norm`: the
+        network forward, then everything after it either as ONE HIP operator per chunk (`autograd.FitTailFn`: `post_proc_tf`,
+        clamp, the three losses and their reverse mode) or as the tensor code (`_model`, `get_node_loss`, `get_flood_loss`, `_mse`).
+        With `roll` the operator's unclamped `out_y` / `out_ey` feed the next window, the loss sums add up over the chunks and
+        the division by the sample count follows.  flood=True (`fit_grad_norm`) asks for the flood loss whatever `balance` says; with
+        `balance` the operator does not compute it and the tensor route stays."""
+        fused = None if flood and self.balance else self._fit_tail_spec(x, a, b, y, ey)
+        if fused is None:
+            self.last_fit_tail_path = 'torch'
+            preds, edge_preds = self._model(x, a, b, ex, ae, None, fit)
+            lw = self._loss_setup(preds.device)
+            node_loss = self.get_node_loss(y, b, preds)
+            fl_loss = self.get_flood_loss(y, preds) if flood or (self.if_flood and not self.balance) else None
+            return node_loss, fl_loss, self._mse(ey, edge_preds, lw['ewei'])
+        self.last_fit_tail_path = 'hip'
+        spec, ops = fused
+        c = lambda t: None if t is None else t.detach().contiguous()
+        so, keep = self.seq_out, self.seq_in - self.seq_out
+        tail = lambda ny_, ney_, sl: _ag.FitTailFn.apply(ny_, ney_, c(a[:, sl]) if self.act else None, c(b[:, sl]), c(y[:, sl]), c(ey[:, sl]),
+                                                         self._inc_handle, spec, ops, self.act and self._has_pump)
+        if not self.roll:
+            adj = self.get_adj_action(a, True) if self.act and self.use_adj else None
+            _, _, sums = tail(*self.forward(x, b, ex, ae, adj, training=fit), slice(None))
+        else:
+            sums = None
+            for i in range(self.roll):                     # `_model` with roll > 0, `_roll_step` with the tail fused
+                sl = slice(i * so, (i + 1) * so)
+                a_i, b_i = (a[:, sl] if a is not None else None), b[:, sl]
+                ae_i = self.get_edge_action(a_i, True) if self.act else None
+                adj_i = self.get_adj_action(a_i, True) if self.act and self.use_adj else None
+                out_y, out_ey, s = tail(*self.forward(x[:, -self.seq_in:], b_i, ex[:, -self.seq_in:], ae_i, adj_i, training=fit), sl)
+                sums = s if sums is None else sums + s
+                if self.if_flood:
+                    x_new = torch.cat([out_y[..., :-1], (out_y[..., -1:] > 0.5).float(), b_i], dim=-1)
+                else:
+                    x_new = torch.cat([out_y, b_i], dim=-1)
+                x = torch.cat([x[:, -keep:], x_new], dim=1) if keep > 0 else x_new
+                ex_new = torch.cat([out_ey, ae_i if self.act else torch.ones(out_ey.shape[:-1] + (1,), device=out_ey.device)], dim=-1)
+                ex = torch.cat([ex[:, -keep:], ex_new], dim=1) if keep > 0 else ex_new
+        rows = float(y.shape[0] * y.shape[1])
+        node_loss, edge_loss = sums[0] / (rows * self.n_node), sums[2] / (rows * self.n_edge)
+        fl_loss = sums[1] / (rows * self.n_node) if self.if_flood and not self.balance else None
+        return node_loss, fl_loss, edge_loss
+
     def fit_eval(self, x, a, b, y, ex, ey, fit=True):
         """One training (fit=True) or evaluation step on NORMALISED tensors (emulator.py:457-484): forward through
         `_model`, node MSE (+ weighted flood BCE) + link MSE, reverse mode through the HIP operators (autograd.py), Adam with
@@ -1213,15 +1307,11 @@ class Emulator(nn.Module):
                 p.requires_grad_(True)
         with torch.set_grad_enabled(bool(fit)):
             ae = self.get_edge_action(a, True) if self.act else None
-            preds, edge_preds = self._model(x, a, b, ex, ae, None, fit)
-            lw = self._loss_setup(preds.device)
-            node_loss = self.get_node_loss(y, b, preds)
-            fl_loss = self.get_flood_loss(y, preds) if self.if_flood and not self.balance else None
-            edge_loss = self._mse(ey, edge_preds, lw['ewei'])
+            node_loss, fl_loss, edge_loss = self._fit_losses(x, a, b, y, ex, ey, ae, fit)
             if fit:
                 loss = node_loss + edge_loss
                 if self.gradnorm:                    # GradNorm task weights (emulator.py:470-473): constants for this step
-                    alpha = self._alphas(preds.device)
+                    alpha = self._alphas(node_loss.device)
                     loss = alpha[0].detach() * loss
                 if self.if_flood:
                     if fl_loss is None:
@@ -1264,13 +1354,11 @@ class Emulator(nn.Module):
         try:
             with torch.enable_grad():
                 ae = self.get_edge_action(a, True) if self.act else None
-                preds, edge_preds = self._model(x, a, b, ex, ae, None)
-                lw = self._loss_setup(preds.device)
-                reg_loss = self.get_node_loss(y, b, preds) + self._mse(ey, edge_preds, lw['ewei'])
-                fl_loss = self.get_flood_loss(y, preds)
+                node_loss, fl_loss, edge_loss = self._fit_losses(x, a, b, y, ex, ey, ae, False, flood=True)
+                reg_loss = node_loss + edge_loss
                 g_reg, = torch.autograd.grad(reg_loss, W, retain_graph=True)
                 g_cls, = torch.autograd.grad(fl_loss, W)
-                alpha = self._alphas(preds.device)
+                alpha = self._alphas(reg_loss.device)
                 norms = torch.stack([(alpha[0] * g_reg.detach()).norm(), (alpha[1] * g_cls.detach()).norm()])
                 ini = [float(v) for v in ini_loss]
                 r = torch.stack([reg_loss.detach() / (ini[0] + ini[-1]), fl_loss.detach() / ini[1]])

@@ -443,6 +443,40 @@ int uds_predict_tail_backward(const uds_csr_t *inc_n, const float *sign, const u
                               const float *h0, int64_t B, int64_t T, const float *g_out_y, const float *g_out_ey,
                               float *dy, float *dey, float *da, float *dh0, float *workspace, uds_stream_t stream);
 
+/* The tail of a training step: everything Emulator.fit_eval / fit_grad_norm do after the network forward (emulator.py:400-484)
+ * -- post_proc_tf (tide, offset gate, rated-pump override, link and node action gates, link -> node flow balance), clamp(0, 1),
+ * get_node_loss (balance != 0: through constrain_tf, emulator.py:441-447), the weighted flood BCE (if_flood without balance) and
+ * the link MSE -- in three launches.  p as for uds_predict_tail, with depth_gate = 0 and pump_override = "every link is a pump";
+ * area_eps, ps, ehmax and the per-action lists are not read.  y, ey, a: as there; b_norm (B,T,N,b_channels) the normalised
+ * boundary (channel 0 the runoff, the last one the tide); y_true (B,T,N,cyt) = [h, q_in, q_out, .., (flood at cyt - 2), q_w at
+ * cyt - 1], cyt >= 3; ey_true (B,T,E,ce); nwei (N, 3 + balance), poswei (N), ewei (E) the loss weights; qw_den (N) =
+ * norm_y[0, :, -1], span_b / mini_b (N) = max - min / min of the runoff norm (read with balance only).
+ * out_y (B,T,N,C) and out_ey (B,T,E,ce) are what post_proc_tf returns (normalised, NOT clamped: the rollout feeds them back),
+ * bit-identical to the tensor code.  loss_sums[3] = [node, flood, edge]: the sums of the per-sample terms of the three losses on
+ * clamp(out_y, 0, 1) before the division by the sample count (flood: 0 unless if_flood without balance).  Probabilities are clipped
+ * to [1e-7, 1 - 1e-7].  Per-workgroup partials in `workspace`, then a fixed-order second stage: no atomics, the same bits every
+ * run. */
+int uds_fit_tail(const uds_csr_t *inc_n, const float *sign, const uds_tail_t *p, const float *y, const float *ey,
+                 const float *a, const float *b_norm, const float *y_true, const float *ey_true, const float *nwei,
+                 const float *poswei, const float *ewei, const float *qw_den, const float *span_b, const float *mini_b,
+                 int64_t B, int64_t T, int64_t cyt, int balance, float *out_y, float *out_ey, float *loss_sums,
+                 float *workspace, uds_stream_t stream);
+
+/* Floats of workspace uds_fit_tail and uds_fit_tail_backward need (one size serves both). */
+int64_t uds_fit_tail_workspace_floats(int64_t N, int64_t E, int64_t B, int64_t T);
+
+/* Reverse mode of uds_fit_tail (emulator.py:400-484 under the tape): dy and dey in the shapes of y and ey for g_loss[3], the
+ * gradients of the three loss sums (device memory: no host round trip), plus g_out_y / g_out_ey, the gradients arriving at the two
+ * outputs through the rollout's feedback (either may be NULL: none).  The gates are recomputed from y and ey.  clamp(0, 1) and the
+ * probability clip pass on their closed intervals, comparisons carry nothing, max / min split evenly at a tie, the flow balance
+ * passes nothing at a flow of 0.  Not differentiable in a, b_norm or the targets.  Two launches, no atomics. */
+int uds_fit_tail_backward(const uds_csr_t *inc_n, const float *sign, const uds_tail_t *p, const float *y, const float *ey,
+                          const float *a, const float *b_norm, const float *y_true, const float *ey_true,
+                          const float *nwei, const float *poswei, const float *ewei, const float *qw_den,
+                          const float *span_b, const float *mini_b, int64_t B, int64_t T, int64_t cyt, int balance,
+                          const float *g_loss, const float *g_out_y, const float *g_out_ey, float *dy, float *dey,
+                          float *workspace, uds_stream_t stream);
+
 /* Floats of workspace uds_gat_forward needs: S * n * (d + 2). */
 int64_t uds_gat_workspace_floats(int64_t n, int64_t S, int64_t d);
 
