@@ -31,13 +31,7 @@ struct ConvStreamArgs {
   int n_seg, seg_len;         // the T steps are cut into n_seg segments of seg_len steps (each re-reads a 2D-step halo)
 };
 
-#ifndef UDS_CS_WAVES
-#define UDS_CS_WAVES 8
-#endif
-#ifndef UDS_CS_PREF
-#define UDS_CS_PREF 2
-#endif
-constexpr int CS_WAVES = UDS_CS_WAVES, CS_PREF = UDS_CS_PREF, CS_RING = CS_PREF + 1;      // one workgroup per CU (two waves per SIMD): 48 KB weights + waves x ring
+constexpr int CS_WAVES = 8, CS_PREF = 2, CS_RING = CS_PREF + 1;      // one workgroup per CU (two waves per SIMD): 48 KB weights + waves x ring
 
 template <int D, int ACT>
 __global__ __launch_bounds__(CS_WAVES * 64, 2) void k_conv3_stream(ConvStreamArgs a) {

@@ -230,16 +230,7 @@ __device__ __forceinline__ void static_for(F &&f) {
   }
 }
 
-#ifdef UDS_SMALL_IN_LDS
-constexpr bool SMALL_IN_LDS = true;     // the fusion-MLP weights (32 VGPRs) live in LDS, read per 16-row block
-#else
-constexpr bool SMALL_IN_LDS = false;
-#endif
-
-#ifndef UDS_P3_SLOTS
-#define UDS_P3_SLOTS 2
-#endif
-constexpr int P3_SLOTS = UDS_P3_SLOTS;      // neighbour slots per P3 step (reads in flight per row group)
+constexpr int P3_SLOTS = 2;      // neighbour slots per P3 step (reads in flight per row group)
 
 // value of lane K of this lane's 16-lane row (v_mov_b32_dpp row_newbcast:K), K compile-time
 template <int K>
@@ -370,9 +361,6 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_tile(FusedArgs a)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, qd = lane >> 4;
   const int c16 = r16, rs = qd;                  // P3 mapping: 16 lanes x float4 per output row, 4 rows per group
-#ifdef UDS_PRIO_YOUNG
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);  // experiment: static priority for the second-dispatched half (MI355X_MICROARCH.md item 4)
-#endif
 
   // XCD-aware bijective remap: workgroups b, b+8, b+16.. share an XCD (round-robin dispatch), give each XCD
   // a contiguous range of work items so neighbouring tiles of one snapshot chunk meet in one L2.
@@ -390,8 +378,8 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_tile(FusedArgs a)
   const int sd = __builtin_amdgcn_readfirstlane(a.hdr[tile * TILE_HDR_INTS + 6]);
   if (!((a.side_mask >> sd) & 1)) return;
   const FusedSide &S_ = a.side[sd];
-  constexpr bool COLD_X = FP > 64, COLD_S = FS > 64 || SMALL_IN_LDS;
-  constexpr int T_COLD_X = KT_X - 1, T_COLD_S = SMALL_IN_LDS ? 0 : KT_S - 1;     // first k-step that lives in LDS
+  constexpr bool COLD_X = FP > 64, COLD_S = FS > 64;
+  constexpr int T_COLD_X = KT_X - 1, T_COLD_S = KT_S - 1;    // first k-step that lives in LDS
   constexpr int N_COLD_S = (KT_S - T_COLD_S) * MB_S * 2 * 64;
   float *s_self = reinterpret_cast<float *>(smem + a.meta_cap);
   float *s_nbr = s_self + a.p_cap;
@@ -652,7 +640,6 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_tile(FusedArgs a)
         fma_row(wa, a0, a1);
         fma_row(wb, b0, b1);
       };
-#ifndef UDS_ABL_NO_AGG
       add2(locs & 0xffu, vals[0], (locs >> 8) & 0xffu, vals[1]);
       if (inc_width > 2) add2((locs >> 16) & 0xffu, vals[2], locs >> 24, vals[3]);
       if (flags & ELL_FLAG_INC_OVF)      // rows with more than four incident rows (a junction of five or more conduits)
@@ -660,7 +647,6 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_tile(FusedArgs a)
           const float *ra = sec + ovf_loc[p] * SEC_STRIDE + 4 * qd;
           fma_row(ovf_val[p], *reinterpret_cast<const float4 *>(ra), *reinterpret_cast<const float4 *>(ra + 16));
         }
-#endif
       split8(g0, g1, dh[KT_X], dl[KT_X]);
       UDS_STAMP(10);   // P2c: aggregation
 #pragma unroll
@@ -704,7 +690,6 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_tile(FusedArgs a)
   // max / sum are DPP all-reduces inside the 16-lane group; weights and neighbour indices are then broadcast
   // lane by lane while every lane accumulates its own float4 feature chunk.
   auto phase3 = [&](int s) {
-#ifndef UDS_ABL_NO_P3
     int n_st = 0;      // output-store instructions of this phase
     // rows are degree-sorted inside the tile; 4-row groups are dealt round-robin to the waves (group g -> wave g % NW),
     // so every wave gets the same mix of degrees and its groups come in descending degree
@@ -746,7 +731,6 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_tile(FusedArgs a)
           joff[u] = jn[u] * (FUSED_D * 4) + ((jn[u] & 7) << 4);
         }
         row16_sum4(wgt, den);
-#ifndef UDS_ABL_NO_P3_STEPS
         // Lane c of a 16-lane row group holds (weight, offset) of neighbour c.  Neighbour K reaches the row's other
         // lanes by a DPP row broadcast (v_mov_b32_dpp row_newbcast:K): no LDS round trip for the pairs.  The XOR with
         // the lane's own chunk offset (c16 << 4) applies the hx swizzle: bits 4-6 key ^ chunk, bits >= 8 the row.
@@ -793,10 +777,6 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_tile(FusedArgs a)
             more = e0 > K + P3_SLOTS;
           }
         });
-#else
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc[u] = f32x4{wgt[u], __int_as_float(joff[u]), wgt[u], wgt[u]};
-#endif
       } else {   // some row has more than 16 neighbours: every lane walks its row's whole list (tiles with ELL_FLAG_LONG_ROWS)
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -824,27 +804,16 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_tile(FusedArgs a)
           f32x4 o;
 #pragma unroll
           for (int q = 0; q < 4; ++q) o[q] = fused_act<ACT>(fmaf(acc[u][q], inv, bo[q]), a.act);
-#ifndef UDS_ABL_NO_STORE
           *reinterpret_cast<f32x4 *>(S_.out + ((int64_t)s * S_.n_prim_glob * FUSED_D + orow[u])) = o;
-#else
-          asm volatile("" ::"v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "v"(orow[u]));
-#endif
         }
       }
     }
-#ifndef UDS_ABL_NO_STORE
     vm_since_sec += n_st;
     vm_since_prim += n_st;
-#endif
-#endif
     UDS_STAMP(6);
   };
 
-#ifdef UDS_ABL_NO_BAR
-#define UDS_BAR() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#else
 #define UDS_BAR() lds_barrier()
-#endif
   if (s_begin < s_end) phase1(s_begin);
   for (int s = s_begin; s < s_end; ++s) {
     // index lists do not depend on the data: fetch the aggregation operands of this wave's first P2 block now, so the

@@ -249,14 +249,10 @@ __global__ __launch_bounds__(NW * 64) void k_fused_cs(FusedArgs a) {
         st[(2 * t + 1) * 64] = __builtin_bit_cast(float4, lo);
       }
     };
-#ifndef UDS_F128_NOP0
     for (int blk = 0; blk < nb_sec; ++blk)
       if (sec_owner(blk) == wave) split_block(std::integral_constant<int, KT_S>{}, stage_s, blk);
     for (int blk = 0; blk < nb_prim; ++blk)
       if (prim_owner(blk) == wave) split_block(std::integral_constant<int, KT_X>{}, stage_p, blk);
-#else
-    (void)split_block;
-#endif
     UDS_STAMP128(2);
     lds_barrier();
     UDS_STAMP128(3);
@@ -266,13 +262,7 @@ __global__ __launch_bounds__(NW * 64) void k_fused_cs(FusedArgs a) {
       f32x4 acc = *reinterpret_cast<const f32x4 *>(attn + 2 * D + 16 * cs_s + 4 * qd);
 #pragma unroll
       for (int t = 0; t < KT_S; ++t) {
-#ifndef UDS_F128_NOP0
         acc = mfma3(wsh[t], wsl[t], __builtin_bit_cast(bf16x8, st[(2 * t) * 64]), __builtin_bit_cast(bf16x8, st[(2 * t + 1) * 64]), acc);
-#else
-        bf16x8 dh, dl;
-        split8(st[(2 * t) * 64], st[(2 * t + 1) * 64], dh, dl);
-        acc = mfma3(wsh[t], wsl[t], dh, dl, acc);
-#endif
       }
       const int lrow = blk * 16 + r16;
       if (lrow < n_sec) {
@@ -343,12 +333,7 @@ __global__ __launch_bounds__(NW * 64) void k_fused_cs(FusedArgs a) {
         for (int m = 0; m < MPW; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < KT_X; ++t) {
-#ifndef UDS_F128_NOP0
           const bf16x8 dh = __builtin_bit_cast(bf16x8, st[(2 * t) * 64]), dl = __builtin_bit_cast(bf16x8, st[(2 * t + 1) * 64]);
-#else
-          bf16x8 dh, dl;
-          split8(st[(2 * t) * 64], st[(2 * t + 1) * 64], dh, dl);
-#endif
 #pragma unroll
           for (int m = 0; m < MPW; ++m) acc[m] = mfma3(wbh[t][m], wbl[t][m], dh, dl, acc[m]);
         }

@@ -28,28 +28,11 @@
 
 namespace uds {
 
-#ifndef UDS_WS_NY
-#define UDS_WS_NY 4
-#endif
-#ifndef UDS_WS_SLOTS
-#define UDS_WS_SLOTS 4      // measured: 4 slots 257 us, 2 slots 265 us per launch at the headline size (X has the registers: no weights)
-#endif
-constexpr int WS_NY = UDS_WS_NY, WS_NX = FUSED_WAVES - WS_NY;      // team sizes
-#ifdef UDS_WS_YG
-constexpr int WS_YG = UDS_WS_NY;        // experiment: one P3 row group (the NY highest-degree ones) per Y wave, in the time Y waits at the barrier
-#else                                   // (measured: 263 us against 259 us without -- the Y waves' P3 costs the X partner what it saves it)
-constexpr int WS_YG = 0;
-#endif
-constexpr int WS_SLOTS = UDS_WS_SLOTS;                              // neighbour slots per P3 step (reads in flight per row group)
-#ifndef UDS_WS_PRE
-#define UDS_WS_PRE 0
-#endif
-constexpr int WS_PRE = UDS_WS_PRE;      // P3: neighbour slots whose hx rows are fetched BEFORE the softmax chain (their addresses are static)
-static_assert(WS_PRE % WS_SLOTS == 0, "WS_PRE must be a multiple of WS_SLOTS");
-#ifndef UDS_WS_XPRIO
-#define UDS_WS_XPRIO 1      // s_setprio of the X team's waves (the Y team stays at 0)
-#endif
-static_assert(WS_NY >= 2 && WS_NY <= 4, "2 .. 4 waves multiply the primary rows");
+// Tuning values: to sweep one, edit its line.
+constexpr int WS_NY = 4, WS_NX = FUSED_WAVES - WS_NY;      // team sizes (the 32-row P2 needs four Y waves: see the static_assert there)
+constexpr int WS_XPRIO = 1;       // s_setprio of the X team's waves (the Y team stays at 0)
+constexpr int WS_OCT_WD = 4;      // neighbour slots per step of the octet P3 (each step: WS_OCT_WD x 2 x octets ds_read_b128 in flight)
+constexpr int WS_OCT_GRP = 1;     // octets per batch of reads in a P3 step (registers: 8 x WS_OCT_GRP x WS_OCT_WD for the pieces)
 
 // LDS bytes: tile block + 2 x (s_self, s_nbr) + attention vectors / bias + 2 x sec rows + 2 x hx rows
 inline int64_t fused_ws_lds_bytes(int p_cap, int q_cap, int meta_cap) {
@@ -109,26 +92,13 @@ template <int ACT>
 __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
   constexpr int NT = FUSED_WAVES * 64, NY = WS_NY, NX = WS_NX;
   constexpr int FP = 64, FS = 64;
-  constexpr int KT_S = FS / 32, MB_S = FUSED_H / 16;                    // small GEMM: 64 -> 32
-  constexpr int KT_X = FP / 32, KT_B = KT_X + 1, MB_B = FUSED_D / 16;   // big GEMM: 64 + 32 -> 64
   constexpr int U = FUSED_U;
-  constexpr int PJ = (8 + NY - 1) / NY;        // primary 16-row blocks per Y wave (p_cap <= 128)
-  constexpr int SJ = (16 + NX - 1) / NX;       // secondary 16-row blocks per X wave (q_cap <= 256)
   extern __shared__ __attribute__((aligned(16))) int32_t smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef UDS_WS_PAIR_SAME
-  // waves w and w + 4 share a SIMD: put each team on SIMDs of its own (NY = 4: Y on the SIMDs of waves 0/4 and 1/5, X on 2/6 and 3/7)
-  static_assert(NY == 4, "UDS_WS_PAIR_SAME assumes 4 + 4");
-  const bool team_y = (wave & 3) < 2;
-  const int yw = (wave & 1) + 2 * (wave >> 2), xw = ((wave & 3) - 2) + 2 * (wave >> 2);
-#else
   const bool team_y = wave < NY;                 // wave-uniform role
   const int yw = wave, xw = wave - NY;           // index inside the team
-#endif
-  const int r16 = lane & 15, qd = lane >> 4;
-  const int c16 = r16, rs = qd;                  // P3 mapping: 16 lanes x float4 per output row, 4 rows per group
 
   // XCD-aware bijective remap (as k_fused_tile): workgroups b, b+8, .. share an XCD and get a contiguous range of items
   const int W = gridDim.x, b = blockIdx.x;
@@ -204,9 +174,8 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
   // The two teams run two separate loops (the same number of barriers in each): what a team keeps in registers across the
   // snapshots -- the big weights here, the small weights, rows in flight and P3 state there -- is live in its own loop only.
   if (team_y) {
-#ifndef UDS_WS_MFMA16
     // =========================== Y team: P2 on v_mfma_f32_32x32x16_bf16 ===========================
-    // One 32-row block per wave (rows 32 yw ..).  Same flops per cycle as the 16x16x32 form, but an MFMA holds its SIMD's
+    // One 32-row block per wave (rows 32 yw ..).  Same flops per cycle as 16x16x32 (k_fused_tile), but an MFMA holds its SIMD's
     // vector issue for 8 of its 32 cycles instead of 8 of 16 (MI355X_MICROARCH.md): the X wave on this SIMD -- the long
     // instruction stream of the kernel -- loses half as many issue slots to this wave's matrix work.  Lane l: n = l & 31 is
     // the row, hf = l >> 5 the k half: B fragment of k-step t = floats 16 t + 8 hf .. + 7 of the row; the accumulators hold
@@ -261,11 +230,7 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
       return acc;
     };
     for (int k = 0; k <= n_snap; ++k) {
-#ifdef UDS_WS_ABL_NO_P2
-      if (false) {
-#else
       if (k < n_snap && 32 * yw < n_prim) {
-#endif
         const bool more = k + 1 < n_snap;
         const float *next = S_.prim_in + (s_begin + k + 1) * prim_stride;
         const float *secr = sec + (k & 1) * sec_buf;
@@ -346,7 +311,7 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
 #pragma unroll
           for (int m = 0; m < MB32; ++m)
 #pragma unroll
-            for (int gq = 0; gq < 4; ++gq) {      // 16-byte chunk 8 m + 2 gq + hf of the row, XOR (row & 7): as the 16x16x32 form writes it
+            for (int gq = 0; gq < 4; ++gq) {      // 16-byte chunk 8 m + 2 gq + hf of the row, XOR (row & 7): the layout k_fused_tile's P2 writes
               const f32x4 o = {acc[m][4 * gq], acc[m][4 * gq + 1], acc[m][4 * gq + 2], acc[m][4 * gq + 3]};
               *reinterpret_cast<f32x4 *>(hxw + lrow * FUSED_D + (((8 * m + 2 * gq + hf) ^ (lrow & 7)) << 2)) = o;
             }
@@ -357,247 +322,9 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
       WS_STAMP(2);
     }
     WS_DUMP();
-#else
-    // =========================== Y team: P2 ===========================
-    bf16x8 wbh[KT_B][MB_B], wbl[KT_B][MB_B];      // 96 VGPRs, resident across the snapshot loop
-#pragma unroll
-    for (int t = 0; t < KT_B; ++t)
-#pragma unroll
-      for (int m = 0; m < MB_B; ++m) {
-        wbh[t][m] = __builtin_bit_cast(bf16x8, S_.w_big[((t * MB_B + m) * 2 + 0) * 64 + lane]);
-        wbl[t][m] = __builtin_bit_cast(bf16x8, S_.w_big[((t * MB_B + m) * 2 + 1) * 64 + lane]);
-      }
-    // element offsets of the rows of this wave's primary blocks (blk = yw + NY j); a lane's piece c of a row = floats 16 c + 4 qd
-    unsigned prow[PJ];
-#pragma unroll
-    for (int j = 0; j < PJ; ++j) prow[j] = (unsigned)prim_ids[min((yw + NY * j) * 16 + r16, n_prim - 1)] * FP + 4u * qd;
-    f32x4 pp[PJ][2 * KT_X];       // the primary rows of the snapshot P2 multiplies next (compile-time indices only: registers)
-    // aggregation operands of the primary blocks (static per tile)
-    unsigned ag_locs[PJ];
-    f32x4 ag_vals[PJ];
-#pragma unroll
-    for (int j = 0; j < PJ; ++j) {
-      const int lr = min((yw + NY * j) * 16 + r16, n_prim - 1);
-      ag_locs[j] = inc_loc[lr];
-      ag_vals[j] = inc_val4[lr];
-    }
-    // P3 of ONE 4-row group per Y wave (group yw: the highest degrees of the tile), static per tile
-    const int yg_i = 4 * yw + rs, yg_ic = min(yg_i, n_own - 1);
-    const bool yg_ok = WS_YG > 0 && yg_i < n_own;
-    const unsigned yg_jb = adj_b[yg_ic * ELL_ADJ + c16];
-    const bool yg_has = yg_ok && yg_jb != 0xFFu;
-    const int yg_jn = yg_has ? (int)yg_jb : 0;
-    const int yg_joff = yg_jn * (FUSED_D * 4) + ((yg_jn & 7) << 4);
-    const int yg_orow = prim_ids[yg_ic] * FUSED_D + 4 * c16;
-    int yg_dmax;
-    {
-      int dmx;
-      if (flags & ELL_FLAG_LONG_ROWS) {
-        dmx = yg_i < n_own ? adj_ptr[yg_ic + 1] - adj_ptr[yg_ic] : 0;
-      } else {
-        const unsigned long long m = __ballot(yg_i < n_own && adj_b[yg_ic * ELL_ADJ + c16] != 0xFF);
-        dmx = __builtin_popcountll((m >> (16 * rs)) & 0xffffull);
-      }
-      dmx = max(dmx, __shfl_xor(dmx, 16));
-      dmx = max(dmx, __shfl_xor(dmx, 32));
-      yg_dmax = WS_YG > 0 ? __builtin_amdgcn_readfirstlane(dmx) : 0;
-    }
-    f32x4 bo = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (S_.b_out) bo = *reinterpret_cast<const f32x4 *>(S_.b_out + 4 * c16);
-    auto phase3_y = [&](int s, int buf) __attribute__((always_inline)) {
-      if (yg_dmax == 0) return;
-      const float *hxr = hx + buf * hx_buf;
-      const float *ssr = s_self + buf * a.p_cap, *snr = s_nbr + buf * a.p_cap;
-      const float ss = ssr[yg_ic];
-      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-      float den;
-      if (yg_dmax <= 16) {
-        const float sv = ss + snr[yg_jn];
-        const float lg = yg_has ? fmaxf(sv, 0.2f * sv) : -INFINITY;
-        const float mx = row16_max(lg);
-        const float ex = __builtin_amdgcn_exp2f(lg - mx);
-        const float wgt = yg_has ? ex : 0.f;
-        den = row16_sum(wgt);
-        const char *hxb = reinterpret_cast<const char *>(hxr);
-        const int cx = c16 << 4;
-        int dmx = yg_dmax;
-        asm volatile("" : "+s"(dmx));
-        static_for<16 / WS_SLOTS>([&](auto t_) {
-          constexpr int K = decltype(t_)::value * WS_SLOTS;
-          if (K < dmx) {
-            f32x4 hh[WS_SLOTS];
-            static_for<WS_SLOTS>([&](auto i_) {
-              constexpr int i = decltype(i_)::value;
-              hh[i] = *reinterpret_cast<const f32x4 *>(hxb + (row16_bcast<K + i>(yg_joff) ^ cx));
-            });
-            static_for<WS_SLOTS>([&](auto i_) {
-              constexpr int i = decltype(i_)::value;
-              const float wv = __int_as_float(row16_bcast<K + i>(__float_as_int(wgt)));
-#pragma unroll
-              for (int q = 0; q < 4; ++q) acc[q] = fmaf(wv, hh[i][q], acc[q]);
-            });
-          }
-        });
-      } else {      // a row with more than 16 neighbours: walk the whole list
-        const int b0 = yg_ok ? adj_ptr[yg_i] : 0;
-        const int dg = yg_ok ? adj_ptr[yg_i + 1] - b0 : 0;
-        float mx = -INFINITY;
-        for (int p = b0; p < b0 + dg; ++p) mx = fmaxf(mx, leaky02(ss + snr[adj_loc[p]]));
-        den = 0.f;
-        for (int p = b0; p < b0 + dg; ++p) {
-          const int jj = adj_loc[p];
-          const float wv = __builtin_amdgcn_exp2f(leaky02(ss + snr[jj]) - mx);
-          const f32x4 hv = *reinterpret_cast<const f32x4 *>(hxr + jj * FUSED_D + ((c16 ^ (jj & 7)) << 2));
-          den += wv;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) acc[q] = fmaf(wv, hv[q], acc[q]);
-        }
-      }
-      if (yg_ok) {
-        const float inv = __builtin_amdgcn_rcpf(den);
-        f32x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = fused_act<ACT>(fmaf(acc[q], inv, bo[q]), a.act);
-        *reinterpret_cast<f32x4 *>(S_.out + ((int64_t)s * S_.n_prim_glob * FUSED_D + yg_orow)) = o;
-      }
-    };
-    // Drain the set-up loads HERE, on every path, with a wait the compiler's counter bookkeeping sees: a value loaded before
-    // the loop and first used inside it otherwise gets a conservative `s_waitcnt vmcnt(0)` at that use in EVERY iteration
-    // (the pending state survives the merge at the loop header), which would drain the row prefetch each time.
-    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0)
-    if (n_snap > 0) {
-      const float *base = S_.prim_in + s_begin * prim_stride;
-      static_for<PJ>([&](auto j_) {
-        constexpr int j = decltype(j_)::value;
-        static_for<2 * KT_X>([&](auto c_) {
-          constexpr int c = decltype(c_)::value;
-          pp[j][c] = *reinterpret_cast<const f32x4 *>(base + prow[j] + 16 * c);
-        });
-      });
-    }
-    WS_STAMP(0);
-    lds_barrier();      // the X team has computed the secondary MLP of the first snapshot
-
-    for (int k = 0; k <= n_snap; ++k) {
-#ifdef UDS_WS_ABL_NO_P2
-      if (false) {
-#else
-      if (k < n_snap) {
-#endif
-        // ---------------- P2: [prim | agg] @ Wbig -> hx, attention scalars ----------------
-        const bool more = k + 1 < n_snap;
-        const float *next = S_.prim_in + (s_begin + k + 1) * prim_stride;
-        const float *secr = sec + (k & 1) * sec_buf;
-        float *hxw = hx + (k & 1) * hx_buf;
-        float *ssw = s_self + (k & 1) * a.p_cap, *snw = s_nbr + (k & 1) * a.p_cap;
-        static_for<PJ>([&](auto j_) {
-          constexpr int j = decltype(j_)::value;
-          const int blk = yw + NY * j;
-#ifndef UDS_WS_P2_BRANCH
-          {     // every block unconditionally (rows clamped, stores predicated): one basic block, the scheduler interleaves the blocks (-2 %)
-#else
-          if (blk * 16 < n_prim) {
-#endif
-            bf16x8 dh[KT_B], dl[KT_B];
-            static_for<KT_X>([&](auto t_) {
-              constexpr int t = decltype(t_)::value;
-              const f32x4 u0 = pp[j][2 * t], u1 = pp[j][2 * t + 1];
-              split8(make_float4(u0[0], u0[1], u0[2], u0[3]), make_float4(u1[0], u1[1], u1[2], u1[3]), dh[t], dl[t]);
-            });
-            if (more)      // the registers are free (their values went through the split): the next snapshot's rows, a whole interval ahead
-              static_for<2 * KT_X>([&](auto c_) {
-                constexpr int c = decltype(c_)::value;
-                pp[j][c] = *reinterpret_cast<const f32x4 *>(next + prow[j] + 16 * c);
-              });
-            const int lrow = blk * 16 + r16;
-            const bool valid = lrow < n_prim;
-            const int lr = min(lrow, n_prim - 1);
-            f32x4 acc[MB_B];
-#pragma unroll
-            for (int m = 0; m < MB_B; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifndef UDS_WS_ABL_Y_NO_MFMA
-#pragma unroll
-            for (int t = 0; t < KT_X; ++t)
-#pragma unroll
-              for (int m = 0; m < MB_B; ++m) acc[m] = mfma3(wbh[t][m], wbl[t][m], dh[t], dl[t], acc[m]);
-#else
-#pragma unroll
-            for (int m = 0; m < MB_B; ++m) acc[m] = f32x4{__builtin_bit_cast(float, (unsigned)dh[0][0] << 16), (float)m, __builtin_bit_cast(float, (unsigned)dl[1][0] << 16), 0.f};
-#endif
-            const unsigned locs = ag_locs[j];
-            const f32x4 vals = ag_vals[j];
-            float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0;   // this lane's 8 aggregate features (fragment shape)
-            auto fma_row = [&](float wv, const float4 &u0, const float4 &u1) {
-              g0.x = fmaf(wv, u0.x, g0.x); g0.y = fmaf(wv, u0.y, g0.y); g0.z = fmaf(wv, u0.z, g0.z); g0.w = fmaf(wv, u0.w, g0.w);
-              g1.x = fmaf(wv, u1.x, g1.x); g1.y = fmaf(wv, u1.y, g1.y); g1.z = fmaf(wv, u1.z, g1.z); g1.w = fmaf(wv, u1.w, g1.w);
-            };
-            auto add2 = [&](unsigned la, float wa, unsigned lb, float wb) {      // two rows: four reads in flight, then the FMAs
-              const float *ra = secr + la * SEC_STRIDE + 4 * qd, *rb = secr + lb * SEC_STRIDE + 4 * qd;
-              const float4 a0 = *reinterpret_cast<const float4 *>(ra), a1 = *reinterpret_cast<const float4 *>(ra + 16);
-              const float4 b0 = *reinterpret_cast<const float4 *>(rb), b1 = *reinterpret_cast<const float4 *>(rb + 16);
-              fma_row(wa, a0, a1);
-              fma_row(wb, b0, b1);
-            };
-#ifndef UDS_WS_ABL_Y_NO_AGG
-            add2(locs & 0xffu, vals[0], (locs >> 8) & 0xffu, vals[1]);
-            if (inc_width > 2) add2((locs >> 16) & 0xffu, vals[2], locs >> 24, vals[3]);
-#else
-            g0.x = vals[0]; g1.y = vals[1]; g0.z = __uint_as_float(locs);
-#endif
-            if (flags & ELL_FLAG_INC_OVF)      // rows with more than four incident rows (a junction of five or more conduits)
-              for (int p = ovf_ptr[lr]; p < ovf_ptr[lr + 1]; ++p) {
-                const float *ra = secr + ovf_loc[p] * SEC_STRIDE + 4 * qd;
-                fma_row(ovf_val[p], *reinterpret_cast<const float4 *>(ra), *reinterpret_cast<const float4 *>(ra + 16));
-              }
-            split8(g0, g1, dh[KT_X], dl[KT_X]);
-#ifndef UDS_WS_ABL_Y_NO_MFMA
-#pragma unroll
-            for (int m = 0; m < MB_B; ++m) acc[m] = mfma3(wbh[KT_X][m], wbl[KT_X][m], dh[KT_X], dl[KT_X], acc[m]);
-#else
-            acc[0][3] += __builtin_bit_cast(float, (unsigned)dh[KT_X][0] << 16) + __builtin_bit_cast(float, (unsigned)dl[KT_X][0] << 16);
-#endif
-            typedef float f32x2 __attribute__((ext_vector_type(2)));
-            f32x2 ps2 = {0.f, 0.f}, pn2 = {0.f, 0.f};
-#pragma unroll
-            for (int m = 0; m < MB_B; ++m) {
-              const f32x4 as4 = *reinterpret_cast<const f32x4 *>(attn + 16 * m + 4 * qd);
-              const f32x4 an4 = *reinterpret_cast<const f32x4 *>(attn + FUSED_D + 16 * m + 4 * qd);
-              ps2 = __builtin_elementwise_fma(acc[m].xy, as4.xy, ps2);
-              pn2 = __builtin_elementwise_fma(acc[m].xy, an4.xy, pn2);
-              ps2 = __builtin_elementwise_fma(acc[m].zw, as4.zw, ps2);
-              pn2 = __builtin_elementwise_fma(acc[m].zw, an4.zw, pn2);
-            }
-            const float ps = quarters_sum(ps2.x + ps2.y);
-            const float pn = quarters_sum(pn2.x + pn2.y);
-#ifdef UDS_WS_ABL_Y_NO_HXW
-            if (valid && ps == 12345.f) {
-#else
-            if (valid) {
-#endif
-              if (qd == 0) {
-                ssw[lrow] = ps;
-                snw[lrow] = pn;
-              }
-#pragma unroll
-              for (int m = 0; m < MB_B; ++m)   // chunk index XOR (row & 7): the 8 lanes of a write group hit 8 different slots
-                *reinterpret_cast<f32x4 *>(hxw + lrow * FUSED_D + (((4 * m + qd) ^ (lrow & 7)) << 2)) = acc[m];
-            }
-          }
-        });
-      }
-      if (WS_YG > 0 && k >= 1) phase3_y(s_begin + k - 1, (k - 1) & 1);      // this wave's share of P3(s - 1), in the time it would wait at the barrier
-      WS_STAMP(1);
-      lds_barrier();      // hx / scores of snapshot k are in LDS (and the X team's sec rows of snapshot k + 1)
-      WS_STAMP(2);
-    }
-    WS_DUMP();
-#endif
   } else {
     // =========================== X team: P1 and P3 ===========================
-#ifndef UDS_WS_NO_PRIO
-    __builtin_amdgcn_s_setprio(UDS_WS_XPRIO);      // the longer instruction stream of the two, and the younger half of the workgroup (-2 %)
-#endif
-#ifndef UDS_WS_MFMA16
+    __builtin_amdgcn_s_setprio(WS_XPRIO);      // the longer instruction stream of the two, and the younger half of the workgroup (-2 %)
     // P1 on v_mfma_f32_32x32x16_bf16 too: half as many matrix instructions in this team's (issue-bound) stream.  32-row blocks
     // blk = xw + NX j; lane l: n = l & 31 the row, hf = l >> 5: piece i of the row = floats 16 (i >> 1) + 8 hf + 4 (i & 1).
     typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -627,42 +354,9 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
       });
     };
     auto load_sec = [&](int s) __attribute__((always_inline)) { load_sec_at(S_.sec_in + s * sec_stride); };
-#define UDS_WS_RUNNING_PTRS 1
-#else
-    bf16x8 wsh[KT_S][MB_S], wsl[KT_S][MB_S];      // 32 VGPRs
-#pragma unroll
-    for (int t = 0; t < KT_S; ++t)
-#pragma unroll
-      for (int m = 0; m < MB_S; ++m) {
-        wsh[t][m] = __builtin_bit_cast(bf16x8, S_.w_small[((t * MB_S + m) * 2 + 0) * 64 + lane]);
-        wsl[t][m] = __builtin_bit_cast(bf16x8, S_.w_small[((t * MB_S + m) * 2 + 1) * 64 + lane]);
-      }
-    // BYTE offsets of the rows of the secondary blocks this wave multiplies (blk = xw + NX j); piece c = bytes 64 c + 16 qd
-    unsigned srow[SJ];
-#pragma unroll
-    for (int j = 0; j < SJ; ++j) srow[j] = ((unsigned)sec_ids[min((xw + NX * j) * 16 + r16, n_sec - 1)] * FS + 4u * qd) * 4u;
-    f32x4 sp[SJ][2 * KT_S];       // the secondary rows of the snapshot P1 multiplies next (asm loads: see the header)
-    auto load_sec = [&](int s) __attribute__((always_inline)) {      // unconditional (rows are clamped): a fixed number of loads
-      const float *base = S_.sec_in + s * sec_stride;
-      static_for<SJ>([&](auto j_) {
-        constexpr int j = decltype(j_)::value;
-        ws_gld16<0>(sp[j][0], base, srow[j]);
-        ws_gld16<64>(sp[j][1], base, srow[j]);
-        ws_gld16<128>(sp[j][2], base, srow[j]);
-        ws_gld16<192>(sp[j][3], base, srow[j]);
-      });
-    };
-#endif
-#ifndef UDS_WS_OCT_WD
-#define UDS_WS_OCT_WD 4       // neighbour slots per step of the octet P3 (each step: UDS_WS_OCT_WD x 2 x octets ds_read_b128 in flight)
-#endif
-#ifndef UDS_WS_OCT_GRP
-#define UDS_WS_OCT_GRP 1
-#endif
-#ifndef UDS_WS_P3_GROUPS
     // P3 in the OCTET layout: 8 lanes x 2 float4 per output row, 8 rows per wave-instruction (ro = lane >> 3, c8 = lane & 7 owns
     // features 4 c8 .. + 3 and 32 + 4 c8 .. + 3: the two 16-byte pieces sit 128 B apart in a swizzled hx row, ONE address).
-    // Against 16 lanes x float4 (k_fused_tile, and this kernel under -DUDS_WS_P3_GROUPS) every instruction of the softmax
+    // Against 16 lanes x float4 (k_fused_tile, and the form this kernel started with) every instruction of the softmax
     // prologue and of the output epilogue covers twice the rows, and a neighbour slot costs 7 vector + 2 LDS instructions per
     // 8 rows instead of 10 + 2.  Lane c8 of a row scores neighbour slots c8 and (rows with more than eight neighbours: 7 %
     // of the line graph at the headline, none of the shipped networks) c8 + 8.  The LDS byte offsets of slots 0..7 are
@@ -705,46 +399,7 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
     }
     const float *bias_l = attn + 2 * FUSED_D + FUSED_H + 4 * c8;      // + 32 hf8 / + 32 - 32 hf8 for the lane's first / second piece      // the output bias, read back per snapshot (registers are short)
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): drain the set-up loads on every path (see the Y team's note)
-#else
-    // P3 rows: degree-sorted inside the tile and dealt in 4-row groups: trip t (0, 1), unit u (0..3) -> group NX (2 u + t) + xw,
-    // so both trips and all waves get the same mix of degrees, in descending order.  Static per tile: the (wave-uniform)
-    // largest degree of every group in SGPRs, this lane's neighbour byte of every group in VGPRs.
-    int p3_dmax[2][U];
-    unsigned p3_jb[2][U];
-    int p3_joff[2][U], p3_orow[2][U], p3_ic[2][U];      // static per tile: neighbour's hx offset (swizzled), output row offset, own row
-    int n_st = 0;                 // output-store instructions this wave issues per snapshot (one per group that has a row)
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int i = 4 * (WS_YG + NX * (2 * u + t) + xw) + rs;
-        const int ic = min(i, n_own - 1);
-        int dmx;
-        if (flags & ELL_FLAG_LONG_ROWS) {
-          dmx = i < n_own ? adj_ptr[ic + 1] - adj_ptr[ic] : 0;
-        } else {
-          const unsigned long long m = __ballot(i < n_own && adj_b[ic * ELL_ADJ + c16] != 0xFF);
-          dmx = __builtin_popcountll((m >> (16 * rs)) & 0xffffull);
-        }
-        dmx = max(dmx, __shfl_xor(dmx, 16));
-        dmx = max(dmx, __shfl_xor(dmx, 32));
-        p3_dmax[t][u] = __builtin_amdgcn_readfirstlane(dmx);
-        p3_jb[t][u] = adj_b[ic * ELL_ADJ + c16];
-        {
-          const bool has_ = i < n_own && p3_jb[t][u] != 0xFFu;
-          const int jn_ = has_ ? (int)p3_jb[t][u] : 0;
-          p3_joff[t][u] = jn_ * (FUSED_D * 4) + ((jn_ & 7) << 4);
-          p3_orow[t][u] = prim_ids[ic] * FUSED_D + 4 * c16;
-          p3_ic[t][u] = ic;
-        }
-        if (4 * (WS_YG + NX * (2 * u + t) + xw) < n_own) ++n_st;
-      }
-    f32x4 bo = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (S_.b_out) bo = *reinterpret_cast<const f32x4 *>(S_.b_out + 4 * c16);
-    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): drain the set-up loads on every path (see the Y team's note)
-#endif
 
-#ifndef UDS_WS_MFMA16
     // ---------------- P1: secondary MLP, registers -> MFMA (32x32x16) -> sec ----------------
     auto phase1 = [&](int buf) __attribute__((always_inline)) {
       float *secw = sec + buf * sec_buf;
@@ -788,49 +443,6 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
         ws_pin4(sp[j][4], sp[j][5], sp[j][6], sp[j][7]);
       });
     };
-#else
-    // ---------------- P1: secondary MLP, registers -> MFMA -> sec ----------------
-    auto phase1 = [&](int buf) __attribute__((always_inline)) {
-      float *secw = sec + buf * sec_buf;
-      static_for<SJ>([&](auto j_) {
-        constexpr int j = decltype(j_)::value;
-        const int blk = xw + NX * j;
-        if (blk * 16 < n_sec) {
-          bf16x8 dh[KT_S], dl[KT_S];
-          static_for<KT_S>([&](auto t_) {
-            constexpr int t = decltype(t_)::value;
-            const f32x4 u0 = sp[j][2 * t], u1 = sp[j][2 * t + 1];
-            split8(make_float4(u0[0], u0[1], u0[2], u0[3]), make_float4(u1[0], u1[1], u1[2], u1[3]), dh[t], dl[t]);
-          });
-          const int lrow = blk * 16 + r16;
-          f32x4 acc[MB_S];
-#pragma unroll
-          for (int m = 0; m < MB_S; ++m) acc[m] = *reinterpret_cast<const f32x4 *>(attn + 2 * FUSED_D + 16 * m + 4 * qd);
-#pragma unroll
-          for (int t = 0; t < KT_S; ++t)
-#pragma unroll
-            for (int m = 0; m < MB_S; ++m) acc[m] = mfma3(wsh[t][m], wsl[t][m], dh[t], dl[t], acc[m]);
-          if (lrow < n_sec) {
-#pragma unroll
-            for (int m = 0; m < MB_S; ++m) {
-              f32x4 o;
-#pragma unroll
-              for (int q = 0; q < 4; ++q) o[q] = fused_act<ACT>(acc[m][q], a.act);
-              *reinterpret_cast<f32x4 *>(secw + lrow * SEC_STRIDE + 16 * m + 4 * qd) = o;
-            }
-          }
-        }
-      });
-    };
-    // tie the row registers to a point of the program: nothing that reads them is scheduled above, nothing that writes them below
-    auto pin_rows = [&]() __attribute__((always_inline)) {
-      static_for<SJ>([&](auto j_) {
-        constexpr int j = decltype(j_)::value;
-        ws_pin4(sp[j][0], sp[j][1], sp[j][2], sp[j][3]);
-      });
-    };
-
-#endif
 
     // first snapshot: rows -> registers -> P1 -> sec[0]; the second snapshot's rows into the registers
     if (n_snap > 0) {
@@ -843,7 +455,6 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
     WS_STAMP(0);
     lds_barrier();
 
-#ifndef UDS_WS_P3_GROUPS
     // ---------------- P3 (octets): segmented softmax + neighbour sum -> HBM, the wave's four octets in one pass ----------------
     auto phase3o = [&](float *out_snap, int buf) __attribute__((always_inline)) {      // out_snap: the snapshot's (n_prim_glob, 64) output
       const float *hxr = hx + buf * hx_buf;
@@ -927,8 +538,8 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
         // slots K .. K + Wd - 1 (0 <= K < 8) of slot set SET for the first A octets of the wave
         auto step = [&](auto SET_, auto K_, auto A_) __attribute__((always_inline)) {
           constexpr int SET = decltype(SET_)::value, K = decltype(K_)::value, A = decltype(A_)::value,
-                        Wd = (8 - K < UDS_WS_OCT_WD ? 8 - K : UDS_WS_OCT_WD);
-          constexpr int G = UDS_WS_OCT_GRP;            // octets per batch of reads (registers: 8 x G x Wd for the pieces)
+                        Wd = (8 - K < WS_OCT_WD ? 8 - K : WS_OCT_WD);
+          constexpr int G = WS_OCT_GRP;           // octets per batch of reads (registers: 8 x G x Wd for the pieces)
           static_for<(A + G - 1) / G>([&](auto g_) {
             constexpr int u0 = decltype(g_)::value * G, GA = (A - u0 < G ? A - u0 : G);
             f32x4 h0[GA][Wd], h1[GA][Wd];
@@ -971,8 +582,8 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
             });
           });
         };
-        static_for<(8 + UDS_WS_OCT_WD - 1) / UDS_WS_OCT_WD>([&](auto t_) {                  // slot set 0: slots 0..7, UDS_WS_OCT_WD per step
-          constexpr int K = decltype(t_)::value * UDS_WS_OCT_WD;
+        static_for<(8 + WS_OCT_WD - 1) / WS_OCT_WD>([&](auto t_) {                  // slot set 0: slots 0..7, WS_OCT_WD per step
+          constexpr int K = decltype(t_)::value * WS_OCT_WD;
           using IK = std::integral_constant<int, K>;
           using S0 = std::integral_constant<int, 0>;
           if (K < e3) step(S0{}, IK{}, I4{});
@@ -981,8 +592,8 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
           else if (K < e0) step(S0{}, IK{}, I1{});
         });
         if (ext)
-          static_for<(8 + UDS_WS_OCT_WD - 1) / UDS_WS_OCT_WD>([&](auto t_) {                // slot set 1: slots 8..15
-            constexpr int K = decltype(t_)::value * UDS_WS_OCT_WD;
+          static_for<(8 + WS_OCT_WD - 1) / WS_OCT_WD>([&](auto t_) {                // slot set 1: slots 8..15
+            constexpr int K = decltype(t_)::value * WS_OCT_WD;
             using IK = std::integral_constant<int, K>;
             using S1 = std::integral_constant<int, 1>;
             if (K + 8 < e3) step(S1{}, IK{}, I4{});
@@ -1040,167 +651,12 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
         }
       }
     };
-#else
-    // ---------------- P3: segmented softmax + neighbour sum -> HBM, one trip = 4 row groups of this wave ----------------
-    auto phase3 = [&](int TR, int s, int buf) __attribute__((always_inline)) {      // TR: trip 0 / 1 (a constant after inlining, or the
-                                                                                        // counter of a real loop under UDS_WS_P3_LOOP: half the code)
-#define P3S(arr, u) (TR ? arr[1][u] : arr[0][u])
-      const float *hxr = hx + buf * hx_buf;
-      const float *ssr = s_self + buf * a.p_cap, *snr = s_nbr + buf * a.p_cap;
-      int jn[U], dmax[U], orow[U];
-      float ss[U], lg[U], wgt[U], den[U];
-      bool ok[U], has[U];
-      int dm = 0;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {   // unconditional loads on clamped indices: the four groups' reads overlap
-        const int i = 4 * (WS_YG + NX * (2 * u + TR) + xw) + rs;
-        const int ic = min(i, n_own - 1);
-        ok[u] = i < n_own;
-        has[u] = ok[u] && P3S(p3_jb, u) != 0xFFu;      // neighbour slot c16 of this row exists (slots fill from 0)
-        jn[u] = has[u] ? (int)P3S(p3_jb, u) : 0;
-        dmax[u] = P3S(p3_dmax, u);
-        ss[u] = ssr[P3S(p3_ic, u)];
-        orow[u] = P3S(p3_orow, u);
-        dm = max(dm, dmax[u]);
-      }
-      if (dm == 0) return;            // no row of this trip exists
-      f32x4 acc[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (dm <= 16) {
-        int d0 = dmax[0], d1 = dmax[1], d2 = dmax[2], d3 = dmax[3];
-        asm volatile("" : "+s"(d0), "+s"(d1), "+s"(d2), "+s"(d3));      // keep the slot tests on the scalar unit (see k_fused_tile)
-        const int e3 = d3, e2 = max(e3, d2), e1 = max(e2, d1), e0 = max(e1, d0);
-        const char *hxb = reinterpret_cast<const char *>(hxr);
-        const int cx = c16 << 4;
-        int joff[U];      // byte offset of the neighbour's hx row with its swizzle key in bits 4-6: j*256 + (j&7)*16
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          joff[u] = P3S(p3_joff, u);
-          const float sv = ss[u] + snr[jn[u]];
-          const float sc = fmaxf(sv, 0.2f * sv);      // leaky_relu(0.2)
-          lg[u] = has[u] ? sc : -INFINITY;
-        }
-        using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
-        using I3 = std::integral_constant<int, 3>; using I4 = std::integral_constant<int, 4>;
-        constexpr int R = WS_PRE > 0 ? WS_PRE : 1;
-        f32x4 hh0[U][R];
-        auto pre_read = [&](auto K_, auto A_) __attribute__((always_inline)) {      // slot K of the A groups that still have one
-          constexpr int K = decltype(K_)::value, A = decltype(A_)::value;
-          static_for<A>([&](auto u_) {
-            constexpr int u = decltype(u_)::value;
-            hh0[u][K] = *reinterpret_cast<const f32x4 *>(hxb + (row16_bcast<K>(joff[u]) ^ cx));
-          });
-        };
-        if constexpr (WS_PRE > 0)
-          static_for<WS_PRE>([&](auto K_) {
-            constexpr int K = decltype(K_)::value;
-            if (K < e3) pre_read(K_, I4{});
-            else if (K < e2) pre_read(K_, I3{});
-            else if (K < e1) pre_read(K_, I2{});
-            else if (K < e0) pre_read(K_, I1{});
-          });
-        static_assert(U == 4, "the four-at-once reductions below");
-        float mx[U];
-        row16_max4(lg, mx);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const float ex = __builtin_amdgcn_exp2f(lg[u] - mx[u]);
-          wgt[u] = has[u] ? ex : 0.f;
-        }
-        row16_sum4(wgt, den);
-        auto pre_fma = [&](auto K_, auto A_) __attribute__((always_inline)) {
-          constexpr int K = decltype(K_)::value, A = decltype(A_)::value;
-          static_for<A>([&](auto u_) {
-            constexpr int u = decltype(u_)::value;
-            const float wv = __int_as_float(row16_bcast<K>(__float_as_int(wgt[u])));
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[u][q] = fmaf(wv, hh0[u][K][q], acc[u][q]);
-          });
-        };
-        if constexpr (WS_PRE > 0)
-          static_for<WS_PRE>([&](auto K_) {
-            constexpr int K = decltype(K_)::value;
-            if (K < e3) pre_fma(K_, I4{});
-            else if (K < e2) pre_fma(K_, I3{});
-            else if (K < e1) pre_fma(K_, I2{});
-            else if (K < e0) pre_fma(K_, I1{});
-          });
-        auto step = [&](auto K_, auto A_) __attribute__((always_inline)) {
-          constexpr int K = decltype(K_)::value, A = decltype(A_)::value, Wd = WS_SLOTS;
-          f32x4 hh[A][Wd];
-#pragma unroll
-          for (int u = 0; u < A; ++u)
-            static_for<Wd>([&](auto i_) {
-              constexpr int i = decltype(i_)::value;
-              hh[u][i] = *reinterpret_cast<const f32x4 *>(hxb + (row16_bcast<K + i>(joff[u]) ^ cx));
-            });
-#pragma unroll
-          for (int u = 0; u < A; ++u)
-            static_for<Wd>([&](auto i_) {
-              constexpr int i = decltype(i_)::value;
-              const float wv = __int_as_float(row16_bcast<K + i>(__float_as_int(wgt[u])));
-#pragma unroll
-              for (int q = 0; q < 4; ++q) acc[u][q] = fmaf(wv, hh[u][i][q], acc[u][q]);
-            });
-        };
-        bool more = e0 > WS_PRE;
-        static_for<(16 - WS_PRE) / WS_SLOTS>([&](auto t_) {
-          constexpr int K = WS_PRE + decltype(t_)::value * WS_SLOTS;
-          if (more) {
-            using IK = std::integral_constant<int, K>;
-#ifdef UDS_WS_P3_FLAT
-            step(IK{}, I4{});      // experiment: all four groups at every step (exhausted groups read row 0 with weight 0): no if-chain, a quarter of the code
-#else
-            if (K < e3) step(IK{}, I4{});
-            else if (K < e2) step(IK{}, I3{});
-            else if (K < e1) step(IK{}, I2{});
-            else step(IK{}, I1{});
-#endif
-            more = e0 > K + WS_SLOTS;
-          }
-        });
-      } else {   // some row has more than 16 neighbours: every lane walks its row's whole list (tiles with ELL_FLAG_LONG_ROWS)
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const int i = 4 * (WS_YG + NX * (2 * u + TR) + xw) + rs;
-          const int b0 = i < n_own ? adj_ptr[i] : 0;
-          const int dg = i < n_own ? adj_ptr[i + 1] - b0 : 0;
-          float mx = -INFINITY;
-          for (int p = b0; p < b0 + dg; ++p) mx = fmaxf(mx, leaky02(ss[u] + snr[adj_loc[p]]));
-          den[u] = 0.f;
-          for (int p = b0; p < b0 + dg; ++p) {
-            const int jj = adj_loc[p];
-            const float wv = __builtin_amdgcn_exp2f(leaky02(ss[u] + snr[jj]) - mx);
-            const f32x4 hv = *reinterpret_cast<const f32x4 *>(hxr + jj * FUSED_D + ((c16 ^ (jj & 7)) << 2));
-            den[u] += wv;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[u][q] = fmaf(wv, hv[q], acc[u][q]);
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        if (ok[u]) {
-          const float inv = __builtin_amdgcn_rcpf(den[u]);
-          f32x4 o;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) o[q] = fused_act<ACT>(fmaf(acc[u][q], inv, bo[q]), a.act);
-          *reinterpret_cast<f32x4 *>(S_.out + ((int64_t)s * S_.n_prim_glob * FUSED_D + orow[u])) = o;
-        }
-      }
-    };
-
-#endif
-#ifdef UDS_WS_RUNNING_PTRS
     // the base of the rows requested next and of the snapshot P3 writes next, as running pointers: formed from the kernel arguments
     // inside the loop, each costs a scalar load + s_waitcnt lgkmcnt(0) per interval -- a wait that also drains the wave's LDS queue
     const float *sec_next = S_.sec_in + (int64_t)(s_begin + 2) * sec_stride;
     float *out_next = S_.out + (int64_t)s_begin * S_.n_prim_glob * FUSED_D;
     const int64_t out_stride = (int64_t)S_.n_prim_glob * FUSED_D;
-#endif
     for (int k = 0; k <= n_snap; ++k) {
-      const int s = s_begin + k;
       if (k + 1 < n_snap) {
         // the rows of snapshot k + 1 were requested in interval k - 1, right after its P1; the only younger vector-memory
         // operations of this wave are the output stores of THAT interval's P3 -- which exists from interval 1 on.  (k >= 1
@@ -1208,40 +664,16 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
         // let n_st of the sixteen row loads themselves stay in flight.)
         ws_vmcnt(k >= 2 ? n_st : 0);
         pin_rows();
-#ifndef UDS_WS_ABL_NO_P1
         phase1((k + 1) & 1);
-#endif
-#ifdef UDS_WS_RUNNING_PTRS
         if (k + 2 < n_snap) load_sec_at(sec_next);
         sec_next += sec_stride;
-#else
-        if (k + 2 < n_snap) load_sec(s + 2);
-#endif
       }
       WS_STAMP(3);
-#ifndef UDS_WS_ABL_NO_P3
       if (k >= 1) {
-#ifndef UDS_WS_P3_GROUPS
-#ifdef UDS_WS_RUNNING_PTRS
         phase3o(out_next, (k - 1) & 1);
         out_next += out_stride;
-#else
-        phase3o(S_.out + (int64_t)(s - 1) * S_.n_prim_glob * FUSED_D, (k - 1) & 1);
-#endif
         WS_STAMP(4);
-#elif defined(UDS_WS_P3_LOOP)
-#pragma nounroll
-        for (int tr = 0; tr < 2; ++tr) phase3(tr, s - 1, (k - 1) & 1);
-#else
-        phase3(0, s - 1, (k - 1) & 1);
-        WS_STAMP(4);
-#ifndef UDS_WS_ABL_HALF_P3
-        phase3(1, s - 1, (k - 1) & 1);
-#endif
-        WS_STAMP(5);
-#endif
       }
-#endif
       WS_STAMP(1);
       lds_barrier();
       WS_STAMP(2);

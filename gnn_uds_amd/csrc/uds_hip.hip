@@ -200,6 +200,23 @@ hipError_t launch_fused(const uds::FusedArgs &a, int grid, int64_t lds, hipStrea
   return launch_fused_act<FP, FS, -1>(a, grid, lds, st);
 }
 
+// Snapshots of a fused spatial launch are cut into chunks; one workgroup = (tile, chunk).  All working workgroups take about
+// the same time (setup ~1.5 snapshots' worth + its snapshots), one per CU at a time, so a launch lasts ~ceil(working / 256)
+// rounds: the chunk length that minimises rounds * (setup + chunk), in half snapshots, ties to the shorter chunk.  (Metadata,
+// weights and the DMA pipeline are set up once per workgroup, so long chunks are cheap.)
+int64_t pick_chunk(int64_t S, int64_t working_tiles) {
+  int64_t chunk = S, best = INT64_MAX;
+  for (int64_t c = 1; c <= S; ++c) {
+    const int64_t rounds = (((S + c - 1) / c) * working_tiles + 255) / 256;
+    const int64_t cost = rounds * (3 + 2 * c);
+    if (cost < best || (cost == best && c < chunk)) {
+      best = cost;
+      chunk = c;
+    }
+  }
+  return chunk;
+}
+
 hipError_t pack_weights(const float *W, int K, int F_out, uint4 *out, hipStream_t st) {
   const int total = (K / 32) * (F_out / 16) * 64;
   hipLaunchKernelGGL(uds::k_pack_weight_frags, dim3((total + 255) / 256), dim3(256), 0, st, W, K, F_out, out);
@@ -474,9 +491,6 @@ struct RemainderPlan {
 RemainderPlan remainder_plan(int64_t R, int64_t Nc, int64_t Kp) {
   RemainderPlan q{false, 0, 0, 0, 1};
   q.v2 = Nc * Kp * 2 < ((int64_t)1 << 32) && R * Kp * 2 < ((int64_t)1 << 32) && Nc >= 256 && R >= 128;
-#ifdef UDS_GEMM_V1
-  q.v2 = false;
-#endif
   if (!q.v2) return q;
   q.n_ctile = (Nc + 255) / 256;
   const int64_t tiles = q.n_ctile * ((R + 255) / 256);
@@ -522,20 +536,15 @@ int remainder_gemm_from_planes(const void *packed, int64_t R, int64_t Kp, int64_
   const RemainderPlan plan = remainder_plan(R, Nc, Kp);
   if (plan.v2) {
     using C = uds::Gemm2Cfg<2>;
-#ifdef UDS_GEMM_M32
-    constexpr bool M32 = true;       // the 32 x 32 x 16 form: measured 3 % slower than 16 x 16 x 32 here (profiles/r03_gemm2.md)
-#else
-    constexpr bool M32 = false;
-#endif
     static unsigned long long done = 0;
-    if ((e = uds::set_max_lds_once(reinterpret_cast<const void *>(&uds::k_remainder_gemm2<2, M32>), C::LDS_BYTES, done)) != hipSuccess)
+    if ((e = uds::set_max_lds_once(reinterpret_cast<const void *>(&uds::k_remainder_gemm2<2>), C::LDS_BYTES, done)) != hipSuccess)
       return fail(UDS_EHIP, "uds_remainder_forward: LDS attribute -> %s", hipGetErrorString(e));
     const int64_t n_ctile = plan.n_ctile, t_main = plan.t_main, t_rest = plan.t_rest, ks = plan.ks;
     float *partial = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + 2 * Nc * Kp * 2);
-    hipLaunchKernelGGL((uds::k_remainder_gemm2<2, M32>), dim3((unsigned)(t_main + t_rest * ks)), dim3(512), C::LDS_BYTES, st, xh, xl, wh, wl, Nc, R, Kp, (int)h,
+    hipLaunchKernelGGL((uds::k_remainder_gemm2<2>), dim3((unsigned)(t_main + t_rest * ks)), dim3(512), C::LDS_BYTES, st, xh, xl, wh, wl, Nc, R, Kp, (int)h,
                        (int)n_ctile, out, (int)t_main, (int)ks, partial);
     if (t_rest)
-      hipLaunchKernelGGL((uds::k_remainder_gemm2_reduce<2, M32>), dim3((unsigned)t_rest), dim3(512), 0, st, partial, (int)ks, (int)t_main, Nc, R, (int)h,
+      hipLaunchKernelGGL((uds::k_remainder_gemm2_reduce<2>), dim3((unsigned)t_rest), dim3(512), 0, st, partial, (int)ks, (int)t_main, Nc, R, (int)h,
                          (int)n_ctile, out);
     return launched("uds_remainder_forward", hipGetLastError());
   }
@@ -614,8 +623,11 @@ int uds_rowgemm_forward_cat(const float *x, int64_t F1, const float *x2, int64_t
   UDS_REQUIRE(B * T * R < INT32_MAX, "uds_rowgemm_forward: %lld rows exceed the int32 row index", (long long)(B * T * R));
   if (B == 0) return UDS_OK;
   const int64_t n_blocks = (R + 15) / 16;
-  if (uds::conv_stream_supported((int)taps, (int)F, (int)f_out, (int)dil) && B * n_blocks >= 256 && ldo == f_out &&
-      !std::getenv("UDS_NO_CONV_STREAM")) {
+  bool stream_conv = uds::conv_stream_supported((int)taps, (int)F, (int)f_out, (int)dil) && B * n_blocks >= 256 && ldo == f_out;
+#ifdef UDS_KNOBS
+  if (std::getenv("UDS_NO_CONV_STREAM")) stream_conv = false;      // experiment builds only: the row GEMM in place of the streaming conv
+#endif
+  if (stream_conv) {
     // enough (batch element, 16-row block) streams to fill the CUs: read every row once instead of once per tap
     uds::ConvStreamArgs ca{x, bias, reinterpret_cast<const uint4 *>(packed), out, (int)B, (int)T, (int)R, act, dil > 0 ? 1 : -1, (int)n_blocks, 1, (int)T};
     hipError_t ec = uds::launch_conv_stream(ca, (int)dil, static_cast<hipStream_t>(stream));
@@ -1668,15 +1680,7 @@ static int spatial_forward_impl(const uds_network_t *net, const uds_spatial_para
       a.meta_cap = u.plan.meta_cap;
       a.side_mask = side < 0 ? 3 : (1 << side);
       if ((rem_x || rem_e) && a.p_cap > 64) return hipErrorInvalidValue;      // one P1.5 unit per wave (kernels_fused128.hpp)
-      int64_t chunk = S, best = INT64_MAX;
-      for (int64_t c = 1; c <= S; ++c) {
-        const int64_t rounds = (((S + c - 1) / c) * a.n_tiles + 255) / 256;
-        const int64_t cost = rounds * (3 + 2 * c);
-        if (cost < best || (cost == best && c < chunk)) {
-          best = cost;
-          chunk = c;
-        }
-      }
+      const int64_t chunk = pick_chunk(S, a.n_tiles);
       a.chunk = (int)chunk;
       const int grid = (int)(((S + chunk - 1) / chunk) * a.n_tiles);
       return launch_fused128<decltype(FP_)::value, decltype(FS_)::value>(a, grid, u.lds_bytes, st);
@@ -1743,21 +1747,8 @@ static int spatial_forward_impl(const uds_network_t *net, const uds_spatial_para
 #ifdef UDS_PHASE_TIMING
     a.dbg = reinterpret_cast<unsigned long long *>(ws + PACKED_WEIGHT_FLOATS);   // diagnostic build: stamps go to the (otherwise unused) workspace
 #endif
-    // Snapshots are cut into chunks; one workgroup = (tile, chunk).  All working workgroups take about the same time
-    // (setup ~1.5 snapshots' worth + its snapshots), one per CU at a time, so a launch lasts ~ceil(working / 256) rounds:
-    // pick the chunk length that minimises rounds * (setup + chunk).  (Metadata, weights and the DMA pipeline are set
-    // up once per workgroup, so long chunks are cheap; a launch for one side only skips the other side's tiles at once.)
-    auto set_chunk = [&](int64_t working_tiles) {
-      int64_t chunk = S, best = INT64_MAX;
-      for (int64_t c = 1; c <= S; ++c) {
-        const int64_t n_c = (S + c - 1) / c;
-        const int64_t rounds = (n_c * working_tiles + 255) / 256;
-        const int64_t cost = rounds * (3 + 2 * c);          // in half snapshots
-        if (cost < best || (cost == best && c < chunk)) {
-          best = cost;
-          chunk = c;
-        }
-      }
+    auto set_chunk = [&](int64_t working_tiles) {     // (a launch for one side only skips the other side's tiles at once)
+      int64_t chunk = pick_chunk(S, working_tiles);
 #ifdef UDS_KNOBS
       if (const char *ov = std::getenv("UDS_CHUNK")) chunk = std::max<int64_t>(1, std::min<int64_t>(S, std::atoll(ov)));   // experiment builds only (UDS_DEFINES=-DUDS_KNOBS)
 #endif
@@ -1769,8 +1760,8 @@ static int spatial_forward_impl(const uds_network_t *net, const uds_spatial_para
       const int grid = set_chunk(a.n_tiles);
       const int64_t ws_lds = uds::fused_ws_lds_bytes(a.p_cap, a.q_cap, a.meta_cap);
       bool ws = fx == 64 && !xb && !eb && ws_lds <= FUSED_LDS_BUDGET && a.p_cap <= 128 && a.q_cap <= 256;
-#ifdef UDS_NO_WS
-      ws = false;
+#ifdef UDS_KNOBS
+      if (std::getenv("UDS_NO_WS")) ws = false;      // experiment builds only: k_fused_tile<64, 64> in place of k_fused_ws
 #endif
       UDS_REQUIRE(ws || (!rem_x && !rem_e), "uds_spatial_layer_forward_rem: the wave-specialised d = 64 kernel cannot take this network's plan (p_cap %d, q_cap %d, %lld B of LDS)",
                   a.p_cap, a.q_cap, (long long)ws_lds);

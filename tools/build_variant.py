@@ -1,5 +1,5 @@
-"""Cross-compile a copy of the library with extra defines into build_variants/NAME.so (git-ignored, travels with gpurun):
-    UDS_DEFINES='-DUDS_X=1' python tools/build_variant.py NAME"""
+"""Cross-compile a copy of the library with extra defines into build_variants/NAME.so (git-ignored):
+    UDS_DEFINES=-DUDS_KNOBS python tools/build_variant.py NAME        (the switches: -DUDS_PHASE_TIMING, -DUDS_KNOBS)"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,3 +1,7 @@
+"""Time the 3-tap Conv1D row GEMM at dilation 1 / 2 / 4: python tools/conv_bench.py
+
+UDS_NO_CONV_STREAM=1 routes the calls to the row GEMM in place of the streaming conv kernel; the library reads it only
+in a knob build (UDS_DEFINES=-DUDS_KNOBS python tools/build_variant.py knobs), the product build ignores it."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,4 +1,4 @@
-"""Time uds_remainder_forward at the headline shapes: python tools/gemm_time.py [h ...] (UDS_GEMM_FORM = 0 / 2 / 4 in -DUDS_KNOBS builds)."""
+"""Time uds_remainder_forward at the headline shapes: python tools/gemm_time.py [h ...] (UDS_GEMM_KS = pieces per cut tile in -DUDS_KNOBS builds)."""
 import sys, time, json, os
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,4 +20,4 @@ for h in [int(a) for a in sys.argv[1:]] or [32, 64]:
         ts.append(time.perf_counter() - t0)
     ms = sorted(ts)[len(ts) // 2] * 1e3
     fl = 2.0 * R * M * S * h
-    print(json.dumps({'h': h, 'form': os.environ.get('UDS_GEMM_FORM'), 'ms': ms, 'tflops_fp32_eq': fl / ms / 1e9, 'frac_bf16_peak': 3 * fl / ms / 1e9 / 2500}), flush=True)
+    print(json.dumps({'h': h, 'ks': os.environ.get('UDS_GEMM_KS'), 'ms': ms, 'tflops_fp32_eq': fl / ms / 1e9, 'frac_bf16_peak': 3 * fl / ms / 1e9 / 2500}), flush=True)
