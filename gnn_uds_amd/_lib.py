@@ -109,6 +109,8 @@ SYMBOLS = {
     'uds_csr_sddmm': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr]),
     'uds_wgrad_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_int]),
     'uds_wgrad': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_wgrad_wide_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_int]),
+    'uds_wgrad_wide': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     'uds_network_create': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, ctypes.POINTER(_c_ptr)]),
     'uds_network_destroy': (_c_int, [_c_ptr]),
     'uds_network_prepare': (_c_int, [_c_ptr, _c_i64, _c_i64]),
@@ -1421,6 +1423,29 @@ def wgrad(a, g, shift=0, with_bias=True):
     ws = torch.empty(n_ws, device=a.device, dtype=torch.float32)
     _check(lib.uds_wgrad(_dev(a, 'a'), _dev(g, 'g'), B, T, R, F, H, shift, int(with_bias), _dev(ws, 'workspace'), _dev(dk, 'd_kernel'),
                          _dev(db, 'd_bias', True), _stream()), 'uds_wgrad')
+    return dk, db
+
+
+def wgrad_wide_supported(F, H, with_bias=True):
+    return load().uds_wgrad_wide_workspace_floats(128, F, H, int(with_bias)) > 0
+
+
+def wgrad_wide(a, g, shift=0, with_bias=True):
+    """wgrad for outputs up to 256 (+ the bias row) x 256 (uds_wgrad_wide): the output cut into blocks, one per wave of a
+    workgroup, a and g read from memory once.  Same arithmetic, deterministic."""
+    lib = load()
+    B, T, R, F = a.shape
+    H = g.shape[-1]
+    if tuple(g.shape[:-1]) != (B, T, R):
+        raise UdsError('wgrad_wide: a %r and g %r disagree' % (tuple(a.shape), tuple(g.shape)))
+    n_ws = lib.uds_wgrad_wide_workspace_floats(max(B * T * R, 1), F, H, int(with_bias))
+    if n_ws <= 0:
+        raise UdsError('wgrad_wide: F=%d / H=%d not supported' % (F, H))
+    dk = torch.empty((F, H), device=a.device, dtype=torch.float32)
+    db = torch.empty(H, device=a.device, dtype=torch.float32) if with_bias else None
+    ws = torch.empty(n_ws, device=a.device, dtype=torch.float32)
+    _check(lib.uds_wgrad_wide(_dev(a, 'a'), _dev(g, 'g'), B, T, R, F, H, shift, int(with_bias), _dev(ws, 'workspace'), _dev(dk, 'd_kernel'),
+                              _dev(db, 'd_bias', True), _stream()), 'uds_wgrad_wide')
     return dk, db
 
 

@@ -18,9 +18,10 @@ operator of the forward carries its own backward, so `loss.backward()` on an `Em
     RecurrentFn    GRU / LSTM time recurrence     back-propagation through time in one launch (uds_recurrent_backward)
     RemainderFn    dense off-support NodeEdge bias  forward and d x on the split-bf16 MFMA GEMM (uds_remainder_forward)
 
-Weight gradients are GEMMs with a huge reduction dimension (rows) and tiny outputs: the split-K MFMA kernel uds_wgrad
-(`weight_grad`; shapes it does not take fall back to a library GEMM through `torch.mm`).  Activations are differentiated
-from their outputs.
+Weight gradients are GEMMs with a huge reduction dimension (rows) and tiny outputs: the split-K MFMA kernels uds_wgrad (up to
+128 input rows with the bias row, 64 columns) and uds_wgrad_wide (up to 256 + the bias row, 256 columns), chosen by
+`weight_grad_route`; exact-fp32 layers and anything wider take a library GEMM through `torch.mm`.  Activations are
+differentiated from their outputs.
 """
 import torch
 
@@ -79,13 +80,34 @@ def rows_matmul(x, w, precision='bf16x3'):
     return _lib.dense_act(x3, w.contiguous(), None, 'linear').reshape(lead + (M,))
 
 
+# Shapes uds_wgrad refuses (more than 128 input rows with the bias row, more than 64 columns) go to uds_wgrad_wide (up to
+# 256 + the bias row x 256) when True; False: to the library GEMM, as before the wide entry existed.
+WIDE_WGRAD = True
+# calls of weight_grad per route since the dict was last reset by hand (tests, tools/wgrad_wide_time.py)
+ROUTE_COUNTS = {'wgrad': 0, 'wgrad_wide': 0, 'library': 0}
+
+
+def weight_grad_route(F, H, want_bias, precision):
+    """'wgrad' (uds_wgrad), 'wgrad_wide' (uds_wgrad_wide) or 'library' (torch.mm) for the (F [+ bias row], H) weight gradient of
+    a layer of this precision.  What uds_wgrad takes stays on it; 'fp32' models and anything wider than 256 stay on the library."""
+    if precision != 'bf16x3':
+        return 'library'
+    if _lib.wgrad_supported(F, H, want_bias):
+        return 'wgrad'
+    if WIDE_WGRAD and _lib.wgrad_wide_supported(F, H, want_bias):
+        return 'wgrad_wide'
+    return 'library'
+
+
 def weight_grad(x, gz, precision, want_bias, shift=0):
-    """(dW, db) of y = x @ W + b summed over all leading axes: the HIP split-K MFMA kernel ('bf16x3'), else rocBLAS."""
+    """(dW, db) of y = x @ W + b summed over all leading axes: the HIP split-K MFMA kernels ('bf16x3'), else rocBLAS."""
     F, H = x.shape[-1], gz.shape[-1]
-    if precision == 'bf16x3' and _lib.wgrad_supported(F, H, want_bias):
+    route = weight_grad_route(F, H, want_bias, precision)
+    ROUTE_COUNTS[route] += 1
+    if route != 'library':
         x4 = x.contiguous().reshape((1, 1, -1, F)) if shift == 0 else x.contiguous()
         g4 = gz.contiguous().reshape((1, 1, -1, H)) if shift == 0 else gz.contiguous()
-        return _lib.wgrad(x4, g4, shift, want_bias)
+        return (_lib.wgrad if route == 'wgrad' else _lib.wgrad_wide)(x4, g4, shift, want_bias)
     if shift:
         T = x.shape[1]
         dw = x[:, :T - shift].reshape(-1, F).t().mm(gz[:, shift:].reshape(-1, H)) if shift < T else torch.zeros(F, H, device=x.device)

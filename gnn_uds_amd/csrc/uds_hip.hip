@@ -1378,6 +1378,46 @@ int uds_wgrad(const float *a, const float *g, int64_t B, int64_t T, int64_t R, i
   return UDS_OK;
 }
 
+int64_t uds_wgrad_wide_workspace_floats(int64_t rows, int64_t F, int64_t H, int with_bias) {
+  (void)with_bias;                                             // the partial carries the bias row either way
+  const uds::WgradWidePlan p = uds::wgrad_wide_plan(F, H);
+  if (!p.ok || rows <= 0) return 0;
+  return (int64_t)uds::wgrad_wide_grid(p, rows) * (p.ld_f + 1) * p.ld_n;
+}
+
+int uds_wgrad_wide(const float *a, const float *g, int64_t B, int64_t T, int64_t R, int64_t F, int64_t H, int64_t shift, int with_bias,
+                   float *workspace, float *d_kernel, float *d_bias, uds_stream_t stream) {
+  UDS_REQUIRE(a && g && workspace && d_kernel, "uds_wgrad_wide: NULL argument");
+  UDS_REQUIRE(!with_bias || d_bias, "uds_wgrad_wide: with_bias needs d_bias");
+  UDS_REQUIRE(B >= 0 && T > 0 && R > 0 && F > 0 && H > 0 && shift >= 0, "uds_wgrad_wide: bad sizes");
+  const uds::WgradWidePlan p = uds::wgrad_wide_plan(F, H);
+  UDS_REQUIRE(p.ok, "uds_wgrad_wide: F=%lld or H=%lld not supported (1 to 256 each)", (long long)F, (long long)H);
+  UDS_REQUIRE(B * T * R < INT32_MAX, "uds_wgrad_wide: %lld rows exceed the int32 row index", (long long)(B * T * R));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t rows = B * T * R;
+  if (rows == 0) {
+    hipError_t e0 = hipMemsetAsync(d_kernel, 0, sizeof(float) * F * H, st);
+    if (e0 == hipSuccess && with_bias) e0 = hipMemsetAsync(d_bias, 0, sizeof(float) * H, st);
+    if (e0 != hipSuccess) return fail(UDS_EHIP, "uds_wgrad_wide: memset -> %s", hipGetErrorString(e0));
+    return UDS_OK;
+  }
+  const int grid = uds::wgrad_wide_grid(p, rows);
+  int64_t rpw = (rows + (int64_t)grid * p.ks - 1) / ((int64_t)grid * p.ks);
+  rpw = (rpw + 31) / 32 * 32;
+  // T and R fit an int (rows does); a shift past T drops every term, as a shift of T does: clamp it before it is narrowed
+  const int64_t sh = shift < T ? shift : T;
+  uds::WgradWideArgs wa{a, g, workspace, rows, (int)F, (int)H, (int)sh, (int)T, (int)R, (int)rpw, p.rb, p.cb, p.ks};
+  if (int rc = launched("uds_wgrad_wide", uds::launch_wgrad_wide(wa, p.mt, p.nt, grid, st))) return rc;
+  hipLaunchKernelGGL(uds::k_wgrad_reduce, dim3((unsigned)((F * H + 15) / 16)), dim3(256), 0, st, workspace, grid, p.ld_f + 1, p.ld_n,
+                     (int)F, (int)H, d_kernel);
+  if (with_bias)
+    hipLaunchKernelGGL(uds::k_wgrad_reduce, dim3((unsigned)((H + 15) / 16)), dim3(256), 0, st, workspace + (int64_t)p.ld_f * p.ld_n, grid,
+                       p.ld_f + 1, p.ld_n, 1, (int)H, d_bias);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(UDS_EHIP, "uds_wgrad_wide: reduce launch -> %s", hipGetErrorString(e));
+  return UDS_OK;
+}
+
 // Build (once) and upload the tile plan of kernel variant <fp, fs>.  A plan that does not fit the LDS leaves the slot
 // !ok (the layer then runs unfused); only an allocation / copy failure is an error.
 static int build_slot(uds_network *n, int fp, int fs) {

@@ -586,6 +586,21 @@ int64_t uds_wgrad_workspace_floats(int64_t rows, int64_t F, int64_t H, int with_
 int uds_wgrad(const float *a, const float *g, int64_t B, int64_t T, int64_t R, int64_t F, int64_t H, int64_t shift,
               int with_bias, float *workspace, float *d_kernel, float *d_bias, uds_stream_t stream);
 
+/* The same gradient for the wide layers of a default-size model (embed_size 128, GRU / LSTM projections of 192 / 256 columns):
+ * every 1 <= F <= 256 and 1 <= H <= 256, with or without the bias row, widths that are no multiple of 16 and the shapes
+ * uds_wgrad takes included.  Semantics, d_kernel's arithmetic (split-bf16, 3 products, fp32 accumulate) and refusals are
+ * uds_wgrad's: terms with t < shift dropped, d_bias the column sum of g over ALL rows whatever the shift, B * T * R == 0 gives
+ * zeros by memset, B * T * R < INT32_MAX, NULL arguments / with_bias without d_bias / non-positive sizes return -22; any other
+ * F or H returns -22 too (message "uds_wgrad_wide: ...") and uds_wgrad_wide_workspace_floats() is 0 for it.  d_bias is summed
+ * in plain fp32 from the g values the kernel holds anyway (no row of ones in a: at F = 128 and 256 it would open a tile row).
+ * The output is cut into at most 2 x 4 blocks of at most 128 x 64; the (up to 8) waves of one workgroup each own a block
+ * and walk the same rows together, so a and g are fetched from memory once per call.  One partial per workgroup in
+ * `workspace` (uds_wgrad_wide_workspace_floats() floats, all of them written), summed in index order by a second launch:
+ * no atomics, the same inputs give the same bits.  No allocation, no synchronisation. */
+int64_t uds_wgrad_wide_workspace_floats(int64_t rows, int64_t F, int64_t H, int with_bias);
+int uds_wgrad_wide(const float *a, const float *g, int64_t B, int64_t T, int64_t R, int64_t F, int64_t H, int64_t shift,
+                   int with_bias, float *workspace, float *d_kernel, float *d_bias, uds_stream_t stream);
+
 /* ---- one spatial layer (node side + link side) ---------------------------------------------- */
 typedef struct uds_network uds_network_t;
 
