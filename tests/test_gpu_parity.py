@@ -248,14 +248,18 @@ def test_spatial_layer_with_per_snapshot_adjacency(dev, networks, precision):
 
 
 @pytest.mark.parametrize('R,M,S,h', [(1, 1, 1, 4), (130, 77, 3, 32), (257, 300, 5, 32), (64, 1000, 2, 64), (300, 129, 7, 12),
-                                     # the LDS-DMA staged form (k_remainder_gemm2; S * h >= 256 and R >= 128): 256 x 128 tiles with ragged
-                                     # edges on both sides, two k-steps / one k-step / many, and a shape whose round count picks 256 x 256 tiles
+                                     # (the five above: k_remainder_gemm, 128 x 128 tiles).  The LDS-DMA staged form, k_remainder_gemm2<2>, runs when
+                                     # S * h >= 256 and R >= 128, with 256 x 256 tiles only.  remainder_plan computes these whole (ks = 1): 1, 4, 2 and
+                                     # 256 tiles with ragged edges on both sides, 2 / 14 / 2 / 10 k-steps of 32; it cuts K at (1000, 777, 9, 32): 8
+                                     # tiles in 3 pieces of 8, 9, 9 k-steps + the reduce launch
                                      (130, 64, 8, 32), (1000, 777, 9, 32), (443, 444, 5, 64), (129, 31, 37, 12), (8192, 300, 64, 32),
-                                     # 272 tiles: one whole round of 256 + 16 tiles cut along K into four pieces each, in one launch + the reduce
+                                     # 272 tiles: one whole round of 256 + 16 tiles cut along K into four pieces each, in one launch + the reduce.
+                                     # ks = 1, 3 and 4 are all these shapes reach: tests/test_gpu_remainder_routes.py runs every route (ks = 2 .. 8
+                                     # included) on signed inputs in guarded memory, and states which kernel each of its cases runs
                                      (8704, 1000, 64, 32)])
 def test_remainder_gemm_ragged_shapes(dev, R, M, S, h):
     """uds_remainder_forward (the dense off-support part of a trained NodeEdge, emulator.py:44) against the fp64 product:
-    shapes that are not multiples of the 128 x 128 (or 256 x 128 / 256 x 256) tile, of the k-step of 32, or of one snapshot per tile
+    shapes that are not multiples of the 128 x 128 (or 256 x 256) tile, of the k-step of 32, or of one snapshot per tile
     column block."""
     g = torch.Generator().manual_seed(R * 7 + M)
     rest, x = rnd(g, R, M), rnd(g, S, M, h)

@@ -1,5 +1,6 @@
 """GPU parity of the reverse-mode path (`fit_eval`, emulator.py:440-484) against torch autograd over the
-fp64 CPU oracle: every autograd Function of gnn_uds_amd/autograd.py on its own, the gradients of all Emulator
+fp64 CPU oracle: every autograd Function of gnn_uds_amd/autograd.py on its own (RemainderFn: tests/test_gpu_remainder_routes.py,
+beside the GEMM it runs forward and transposed), the gradients of all Emulator
 parameters, and the parameters after Adam steps.  The oracle is "parity unpinned" (oracle/__init__.py): the reference
 holds no gradients or trained weights to pin it.
 
