@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # UDS_LIB_PATH: a differently built copy of the same library (kernel experiments: tools/variant_bench.py)
 LIB_PATH = os.environ.get('UDS_LIB_PATH') or os.path.join(_HERE, 'libuds_hip.so')
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 FLAG_EXACT_FP32, FLAG_REQUIRE_FUSED = 1, 2
 PRECISION_FLAGS = {'bf16x3': 0, 'fp32': FLAG_EXACT_FP32}
 
@@ -316,6 +316,7 @@ class NetworkHandle:
                'uds_network_create')
         self._h = h
         self._prepared = {(64, 64)}
+        self._bits = None
 
     @property
     def ptr(self):
@@ -328,6 +329,15 @@ class NetworkHandle:
         if key not in self._prepared:
             _check(load().uds_network_prepare(self.ptr, key[0], key[1]), 'uds_network_prepare')
             self._prepared.add(key)
+            self._bits = None
+
+    def fused_bits(self, fx, fe):
+        """prepare(fx, fe), then plan_info()['fused'] (include/uds_hip.h: uds_network_plan_info): read again only after a
+        prepare that built a plan, so a layer's forward asks without a library call."""
+        self.prepare(fx, fe)
+        if self._bits is None:
+            self._bits = self.plan_info()['fused']
+        return self._bits
 
     def plan_info(self):
         """Tile plan of the fused kernel: dict(fused, node_tiles, link_tiles, p_cap, q_cap, meta_cap, lds_bytes, ...)."""

@@ -114,6 +114,11 @@ inline int slot_index(int fp, int fs) {
   return (fp > 64 ? 2 : 0) + (fs > 64 ? 1 : 0);
 }
 
+// the wave-specialised d = 64 kernel (k_fused_ws) can hold this plan's tiles; uds_network_plan_info reports it as bit 32
+inline bool ws_plan_ok(const uds_plan_slot &u) {
+  return uds::fused_ws_lds_bytes(u.plan.p_cap, u.plan.q_cap, u.blk_cap) <= FUSED_LDS_BUDGET && u.plan.p_cap <= 128 && u.plan.q_cap <= 256;
+}
+
 // Tile plan for the kernel variant <fp, fs> (primary / secondary input rows of fp / fs floats: they set the size of the
 // DMA stage) under the LDS budget: fix the footprint limits (primary / secondary rows staged per tile, multiples of 16)
 // first; the planner then fills them (tile_plan.hpp: merge_clusters).
@@ -1522,7 +1527,7 @@ int uds_network_plan_info(const uds_network_t *net, int32_t *info8) {
   UDS_REQUIRE(net && info8, "uds_network_plan_info: NULL argument");
   const uds_plan_slot &sl = net->slot[0];   // the plan for 64-float rows (d = 64 layers)
   info8[0] = (sl.ok ? 1 : 0) | ((net->slot[1].ok && net->slot[2].ok) ? 2 : 0) | (net->slot[3].ok ? 4 : 0) | (net->slot[4].ok ? 8 : 0) |
-             ((net->slot[5].ok && net->slot[6].ok) ? 16 : 0);
+             ((net->slot[5].ok && net->slot[6].ok) ? 16 : 0) | ((sl.ok && ws_plan_ok(sl)) ? 32 : 0);
   info8[1] = sl.plan.side[0].n_tiles;
   info8[2] = sl.plan.side[1].n_tiles;
   info8[3] = sl.plan.p_cap;
@@ -1799,7 +1804,7 @@ static int spatial_forward_impl(const uds_network_t *net, const uds_spatial_para
       a.side_mask = 3;
       const int grid = set_chunk(a.n_tiles);
       const int64_t ws_lds = uds::fused_ws_lds_bytes(a.p_cap, a.q_cap, a.meta_cap);
-      bool ws = fx == 64 && !xb && !eb && ws_lds <= FUSED_LDS_BUDGET && a.p_cap <= 128 && a.q_cap <= 256;
+      bool ws = fx == 64 && !xb && !eb && ws_plan_ok(sl);
 #ifdef UDS_KNOBS
       if (std::getenv("UDS_NO_WS")) ws = false;      // experiment builds only: k_fused_tile<64, 64> in place of k_fused_ws
 #endif

@@ -228,23 +228,16 @@ class GATConv(nn.Module):
         if attn_dropout is not None and self.dropout_rate:
             ones = torch.ones((xs.shape[0], h.nnz), device=xs.device, dtype=torch.float32)
             coef = _lib.dropout(ones, self.dropout_rate, attn_dropout.seed, attn_dropout.take(ones.numel()))
-        if edge_mask is not None:
-            mk = edge_mask.reshape(-1, edge_mask.shape[-1]).to(torch.float32).contiguous()
-            if coef is not None or _ag.grad_on(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias):
-                out = _ag.GatFn.apply(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias,
-                                      self.activation, h, self.precision, coef, mk)
-                return out.reshape(lead + out.shape[-2:])
-            fin = xs.shape[-1] + (0 if xbs is None else xbs.shape[-1])
+        mk = None if edge_mask is None else edge_mask.reshape(-1, edge_mask.shape[-1]).to(torch.float32).contiguous()
+        fin = xs.shape[-1] + (0 if xbs is None else xbs.shape[-1])
+        if coef is not None or _ag.grad_on(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias):
+            out = _ag.GatFn.apply(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias,
+                                  self.activation, h, self.precision, coef, mk)
+        elif mk is not None:
             hx, s_self, s_nbr = _lib.dense_act(xs, self.kernel.reshape(fin, self.channels), None, 'linear', xbs,
                                                attn=(self.attn_kernel_self.reshape(-1), self.attn_kernel_neighs.reshape(-1)))
             out = _lib.gat_aggregate(h, hx, s_self, s_nbr, self.bias, self.activation, edge_mask=mk)
-            return out.reshape(lead + out.shape[-2:])
-        if coef is not None or _ag.grad_on(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias):
-            out = _ag.GatFn.apply(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias,
-                                  self.activation, h, self.precision, coef)
-            return out.reshape(lead + out.shape[-2:])
-        fin = xs.shape[-1] + (0 if xbs is None else xbs.shape[-1])
-        if self.precision == 'bf16x3' and fin % 32 == 0 and self.channels % 16 == 0 and xs.shape[0] * xs.shape[1] >= 4096:
+        elif self.precision == 'bf16x3' and fin % 32 == 0 and self.channels % 16 == 0 and xs.shape[0] * xs.shape[1] >= 4096:
             # wide layers (d = 128, the reference's default): the linear part on the matrix cores (split-bf16 row GEMM, 64
             # columns per launch), the attention projections as two matrix-vector products, then the CSR aggregation kernel
             w2 = self.kernel.reshape(fin, self.channels)
@@ -264,9 +257,9 @@ class GATConv(nn.Module):
             s2 = _lib.rowgemm_cat(xs, xbs, wa_packed, None, 2, 'linear')
             s_self, s_nbr = s2[..., 0].contiguous(), s2[..., 1].contiguous()
             out = _lib.gat_aggregate(h, hx, s_self, s_nbr, self.bias, self.activation)
-            return out.reshape(lead + out.shape[-2:])
-        out = _lib.gat_forward(h, xs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias,
-                               self.activation, xbs)
+        else:
+            out = _lib.gat_forward(h, xs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias,
+                                   self.activation, xbs)
         return out.reshape(lead + out.shape[-2:])
 
 
@@ -617,6 +610,8 @@ class SpatialLayer(nn.Module):
         self._net = net
         self._packed = None       # (parameter versions, packed bf16 hi/lo fragments) of the four GEMM kernels
         self.last_path = None     # which kernels the last forward ran: 'fused', 'fused+remainder', 'unfused' (tests, bench)
+        self.last_route = None    # ... and the row of the route table (`route`) it took
+        self._ws_rem_ok = None    # override for tests: False sends a d = 64 remainder to 'rem-split96' whatever the plan says
 
     def _packed_weights(self, p, fx, fe, remainder=False):
         ks = (self.dense_xe.kernel, self.dense_ex.kernel, self.gat_x.kernel, self.gat_e.kernel)
@@ -635,14 +630,6 @@ class SpatialLayer(nn.Module):
                 aug = {}
             self._packed = (key, _lib.spatial_pack_weights(p, fx, fe, self.h, self.d), aug)
         return self._packed[1], self._packed[2]
-
-    def _d128_remainder_ok(self, xs, es, xbs, ebs):
-        if not (self.precision == 'bf16x3' and self.h == 64 and self.d == 128 and xs.shape[-1] == 128 and es.shape[-1] in (64, 128)
-                and xbs is None and ebs is None):
-            return False
-        net = self.network()
-        net.prepare(128, es.shape[-1])
-        return bool(net.plan_info()['fused'] & (8 if es.shape[-1] == 128 else 16))
 
     def network(self):
         if self._net is None:
@@ -685,172 +672,189 @@ class SpatialLayer(nn.Module):
                 p['ne_%s_w' % tag], p['ne_%s_b' % tag] = c(ne.weight), c(ne.bias)
         return p
 
-    def forward(self, x, e, xb=None, eb=None, adj_mask=None, attn_dropout=None, return_attn_coef=False):
-        """xb / eb: 32 extra columns appended to a 64-wide x / e (`concat([x, b])`, emulator.py:260-262) -- read in place
-        by the fused kernel; every other path concatenates.  adj_mask (..., nnz of the node adjacency): the per-snapshot
-        adjacency of `use_adj` (emulator.py:268-271,282) -- node side through the masked aggregation kernels (under autograd
-        or attention dropout: GatFn on uds_gat_aggregate_ex / uds_gat_backward_ex).
-        attn_dropout: a DropoutStream = Keras' training mode for the two GATConv layers (Spektral's attention dropout, rate 0.5).
-        A multi-head layer (attn_heads > 1) and return_attn_coef=True run the unfused chain: the fused kernels are single-head
-        and never hold the coefficients.  return_attn_coef: also return (alpha_x, alpha_e), (..., H, nnz) of the node and link
-        adjacency (GAT only)."""
-        if adj_mask is not None or self.attn_heads > 1 or return_attn_coef:
+    # route -> (last_path, the method that runs it)
+    ROUTES = {'chain': ('unfused', '_chain'), 'conv': ('unfused', '_conv'), 'entry': ('unfused', '_entry'),
+              'fused': ('fused', '_fused'), 'fused-tiled': ('fused', '_fused_tiled'),
+              'rem-ws': ('fused+remainder', '_fused_rem'), 'rem-d128': ('fused+remainder', '_fused_rem'),
+              'rem-split96': ('fused+remainder', '_rem_split96')}
+
+    def route(self, fx, fxb, fe, feb, S, plan_bits, adj_mask=False, attn_coef=False, attn_dropout=False, grad=False,
+              remainder=False):
+        """Which kernels a forward runs -> (route, split): a key of ROUTES, and whether xb / eb stay separate tensors (only
+        'fused' reads split rows; every other route concatenates).  Plain values in, no tensor, no launch, no side effect:
+        fx, fxb, fe, feb: widths of x, xb, e, eb (0 = absent); S: snapshots; plan_bits(fx, fe): info8[0] of
+        uds_network_plan_info once the plans for those widths are built; adj_mask / attn_coef / attn_dropout: asked for;
+        grad: autograd records for an operand or parameter; remainder: a NodeEdge bias is non-zero off the support.
+        First match wins (widths are the concatenated ones, bf16x3 unless said):
+
+          1   adj_mask, attn_heads > 1 or attn_coef (GAT only)                          chain
+          2   conv is GCN / Diffusion                                                   conv
+          3   attn_dropout or grad                                                      chain
+          4a  remainder, d = 64, 64 / 64, plan bit 32 and _ws_rem_ok is not False       rem-ws
+          4a' as 4a without the bit, or overridden                                      rem-split96
+          4b  remainder, d = 128, fx = 128, fe = 128 with bit 8 / fe = 64 with bit 16   rem-d128
+          4c  remainder, anything else                                                  chain
+          5a  d = 64, fx and fe in {64, 96}; split iff every given piece is 64 + 32     fused
+          5b  d = 128, fx = 128, fe = 128 with bit 8 / fe = 64 with bit 16              fused
+          5c  fx, fe multiples of 32, h, d multiples of 16, S * N >= 4096               chain
+          5d  everything left (fp32, d = 8, ...): the C entry without packed weights    entry
+
+        5a / 5b with pack_factor() = k > 1 and S >= 16 k: fused-tiled (k snapshots per tile; a handful of snapshots -- the
+        rollout's windows -- stay one launch).  4b: the launch refuses plans with p_cap > 64 with an error, not a fallback.
+        5a does not look at plan bits 1 / 2 / 4: on a network whose d = 64 plan does not fit the LDS the C entry composes the
+        layer unfused and last_path still says 'fused'."""
+        if adj_mask or self.attn_heads > 1 or attn_coef:
             if self.conv != 'GAT':
                 raise NotImplementedError('use_adj and return_attn_coef are built for conv=GAT (GCN / Diffusion would re-normalise '
                                           'the filter per snapshot and have no coefficients)')
-            if xb is not None:
-                x = torch.cat([x, xb], dim=-1)
-            if eb is not None:
-                e = torch.cat([e, eb], dim=-1)
-            xs, lead_x = _flatten_snapshots(x)
-            es, lead_e = _flatten_snapshots(e)
-            net = self.network()
-            x_e, e_x = self.dense_xe(es), self.dense_ex(xs)
-            # attention-dropout draws in the order of the unmasked training branch below: gat_x, then gat_e
-            ox = self.gat_x([xs, net.adj], xb=self.node_edge_n(x_e), edge_mask=adj_mask, attn_dropout=attn_dropout,
-                            return_attn_coef=return_attn_coef)
-            oe = self.gat_e([es, net.edge_adj], xb=self.node_edge_e(e_x), attn_dropout=attn_dropout, return_attn_coef=return_attn_coef)
-            self.last_path = 'unfused'
-            if return_attn_coef:
-                (ox, ax), (oe, ae) = ox, oe
-                return (ox.reshape(lead_x + ox.shape[-2:]), oe.reshape(lead_e + oe.shape[-2:]),
-                        (ax.reshape(lead_x + ax.shape[-2:]), ae.reshape(lead_e + ae.shape[-2:])))
-            return ox.reshape(lead_x + ox.shape[-2:]), oe.reshape(lead_e + oe.shape[-2:])
-        fused_split = (xb is not None or eb is not None) and self.conv == 'GAT' and self.precision == 'bf16x3' and \
-            self.h == 32 and self.d == 64 and x.shape[-1] + (0 if xb is None else xb.shape[-1]) in (64, 96) and \
-            e.shape[-1] + (0 if eb is None else eb.shape[-1]) in (64, 96) and (xb is None or (x.shape[-1], xb.shape[-1]) == (64, 32)) and \
-            (eb is None or (e.shape[-1], eb.shape[-1]) == (64, 32)) and not _ag.grad_on(x, e, xb, eb, *self.parameters()) and \
-            self.node_edge_n.support_values()[1] is None and self.node_edge_e.support_values()[1] is None
-        if not fused_split:
-            if xb is not None:
-                x = torch.cat([x, xb], dim=-1)
-            if eb is not None:
-                e = torch.cat([e, eb], dim=-1)
-            xb = eb = None
+            return 'chain', False
+        if self.conv != 'GAT':
+            return 'conv', False
+        if attn_dropout or grad:
+            return 'chain', False
+        d64 = self.precision == 'bf16x3' and (self.h, self.d) == (32, 64)
+        d128 = self.precision == 'bf16x3' and (self.h, self.d) == (64, 128)
+        pieces = ((fx, fxb), (fe, feb))
+        fx, fe = fx + fxb, fe + feb
+        if remainder:
+            if d64 and (fx, fe) == (64, 64):
+                return ('rem-ws' if self._ws_rem_ok is not False and plan_bits(64, 64) & 32 else 'rem-split96'), False
+            if d128 and fx == 128 and fe in (64, 128) and plan_bits(128, fe) & (8 if fe == 128 else 16):
+                return 'rem-d128', False
+            return 'chain', False
+        if (d64 and fx in (64, 96) and fe in (64, 96)) or \
+                (d128 and fx == 128 and fe in (64, 128) and plan_bits(128, fe) & (8 if fe == 128 else 16)):
+            k = self.pack_factor()
+            split = d64 and bool(fxb or feb) and all(b == 0 or (a, b) == (64, 32) for a, b in pieces)
+            return ('fused-tiled' if k > 1 and S >= 16 * k else 'fused'), split
+        if self.precision == 'bf16x3' and fx % 32 == 0 and fe % 32 == 0 and self.h % 16 == 0 and self.d % 16 == 0 \
+                and S * self.graph.n_node >= 4096:
+            return 'chain', False
+        return 'entry', False
+
+    def forward(self, x, e, xb=None, eb=None, adj_mask=None, attn_dropout=None, return_attn_coef=False):
+        """xb / eb: extra columns appended to x / e (`concat([x, b])`, emulator.py:260-262) -- 32 on a 64-wide x / e are
+        read in place by the fused kernel; every other route concatenates.  adj_mask (..., nnz of the node adjacency): the
+        per-snapshot adjacency of `use_adj` (emulator.py:268-271,282) -- node side through the masked aggregation kernels.
+        attn_dropout: a DropoutStream = Keras' training mode for the two GATConv layers (Spektral's attention dropout, rate 0.5).
+        return_attn_coef: also return (alpha_x, alpha_e), (..., H, nnz) of the node and link adjacency (GAT only).
+        `route` picks the kernels (its docstring is the table); last_route / last_path say what this call ran."""
         xs, lead_x = _flatten_snapshots(x)
         es, lead_e = _flatten_snapshots(e)
         xbs = None if xb is None else _flatten_snapshots(xb)[0]
         ebs = None if eb is None else _flatten_snapshots(eb)[0]
-        if self.conv != 'GAT':     # GCN a_hat @ ([x | agg] W) + b, or Diffusion: unfused composition of the Dense / NodeEdge / sparse kernels
-            x_e, e_x = self.dense_xe(es), self.dense_ex(xs)
-            ox = self.gcn_x([torch.cat([xs, self.node_edge_n(x_e)], dim=-1), self.filters[0]])
-            oe = self.gcn_e([torch.cat([es, self.node_edge_e(e_x)], dim=-1), self.filters[1]])
-            return ox.reshape(lead_x + ox.shape[-2:]), oe.reshape(lead_e + oe.shape[-2:])
-        if attn_dropout is not None or _ag.grad_on(xs, es, *self.parameters()):
-            # training: the unfused chain, every operator with its own HIP backward (autograd.py)
-            net = self.network()
-            x_e, e_x = self.dense_xe(es), self.dense_ex(xs)
-            ox = self.gat_x([xs, net.adj], xb=self.node_edge_n(x_e), attn_dropout=attn_dropout)
-            oe = self.gat_e([es, net.edge_adj], xb=self.node_edge_e(e_x), attn_dropout=attn_dropout)
-            return ox.reshape(lead_x + ox.shape[-2:]), oe.reshape(lead_e + oe.shape[-2:])
-        vn, rest_n = self.node_edge_n.support_values()
-        ve, rest_e = self.node_edge_e.support_values()
-        p = dict(xe_k=self.dense_xe.kernel, xe_b=self.dense_xe.bias, ex_k=self.dense_ex.kernel, ex_b=self.dense_ex.bias,
-                 ne_n_val=vn, ne_e_val=ve,
-                 gx_k=self.gat_x.kernel, gx_as=self.gat_x.attn_kernel_self, gx_an=self.gat_x.attn_kernel_neighs,
-                 gx_b=self.gat_x.bias,
-                 ge_k=self.gat_e.kernel, ge_as=self.gat_e.attn_kernel_self, ge_an=self.gat_e.attn_kernel_neighs,
-                 ge_b=self.gat_e.bias)
-        self.last_path = 'unfused'
-        if rest_n is not None or rest_e is not None:
-            # trained dense NodeEdge bias (every checkpoint the reference trains, emulator.py:36-45): secondary MLP on the
-            # row-GEMM kernel, the dense remainder on the MFMA GEMM, everything else in the fused kernel
-            net = self.network()
-
-            def remainders():
-                # rest_n @ Dense_xe(es) and rest_e @ Dense_ex(xs): the Dense outputs exist only for these products (the fused kernel has
-                # its own secondary MLP), so they go straight into the GEMM's operand planes (uds_remainder_forward_dense) when the
-                # shapes allow; else they are materialised first
-                S_, N_, E_ = xs.shape[0], xs.shape[1], es.shape[1]
-                if rest_n is None:
-                    rem_n = torch.zeros((S_, N_, self.h), device=xs.device, dtype=torch.float32)
-                else:
-                    rem_n = self.node_edge_n.remainder_of_dense(es, self.dense_xe) if not os.environ.get('UDS_REMAINDER_MATERIALISE') else None
-                    if rem_n is None:
-                        rem_n = self.node_edge_n.remainder(self.dense_xe(es))
-                if rest_e is None:
-                    rem_e = torch.zeros((S_, E_, self.h), device=xs.device, dtype=torch.float32)
-                else:
-                    rem_e = self.node_edge_e.remainder_of_dense(xs, self.dense_ex) if not os.environ.get('UDS_REMAINDER_MATERIALISE') else None
-                    if rem_e is None:
-                        rem_e = self.node_edge_e.remainder(self.dense_ex(xs))
-                return rem_n, rem_e
-
-            if self.precision == 'bf16x3' and self.h == 32 and self.d == 64 and xs.shape[-1] == 64 and es.shape[-1] == 64 \
-                    and xbs is None and ebs is None:
-                rem_n, rem_e = remainders()
-                ox = None
-                if getattr(self, '_ws_rem_ok', True):
-                    # the wave-specialised kernel adds the remainder to its NodeEdge aggregate (uds_spatial_layer_forward_rem); it
-                    # refuses plans whose tiles it cannot hold -- then the 96-wide split-input kernel below carries the remainder
-                    try:
-                        net.prepare(64, 64)
-                        ox, oe = _lib.spatial_layer_forward(net, dict(p, packed=self._packed_weights(p, 64, 64)[0]), xs, es, self.h, self.d,
-                                                            self.activation, _lib.PRECISION_FLAGS[self.precision], rem_x=rem_n, rem_e=rem_e)
-                    except _lib.UdsError:
-                        self._ws_rem_ok = False
-                if ox is None:
-                    packed, aug = self._packed_weights(p, 96, 96, remainder=True)
-                    net.prepare(96, 96)
-                    ox, oe = _lib.spatial_layer_forward(net, dict(p, packed=packed, **aug), xs, es, self.h, self.d, self.activation,
-                                                        _lib.PRECISION_FLAGS[self.precision], xb=rem_n, eb=rem_e)
-                self.last_path = 'fused+remainder'
-            elif self._d128_remainder_ok(xs, es, xbs, ebs):
-                # the reference's stock model after training (embed_size 128, dense bias): the remainder is added to the support
-                # aggregate inside the column-split kernel (uds_spatial_layer_forward_rem)
-                rem_n, rem_e = remainders()
-                packed = self._packed_weights(p, 128, es.shape[-1])[0]
-                ox, oe = _lib.spatial_layer_forward(net, dict(p, packed=packed), xs, es, self.h, self.d, self.activation,
-                                                    _lib.PRECISION_FLAGS[self.precision], rem_x=rem_n, rem_e=rem_e)
-                self.last_path = 'fused+remainder'
-            else:
-                x_e, e_x = self.dense_xe(es), self.dense_ex(xs)
-                ox = self.gat_x([xs, net.adj], xb=self.node_edge_n(x_e))
-                oe = self.gat_e([es, net.edge_adj], xb=self.node_edge_e(e_x))
+        grad = _ag.grad_on(x, e, xb, eb, *self.parameters())
+        # per side (support values, off-support remainder or None), read once per call; support_values caches what it derives,
+        # so it is not asked while autograd records
+        ne = None if grad else (self.node_edge_n.support_values(), self.node_edge_e.support_values())
+        remainder = ne is not None and (ne[0][1] is not None or ne[1][1] is not None)
+        route, split = self.route(xs.shape[-1], 0 if xbs is None else xbs.shape[-1], es.shape[-1], 0 if ebs is None else ebs.shape[-1],
+                                  xs.shape[0], lambda fx, fe: self.network().fused_bits(fx, fe), adj_mask is not None,
+                                  bool(return_attn_coef), attn_dropout is not None, grad, remainder)
+        if not split:
+            xs = xs if xbs is None else torch.cat([xs, xbs], dim=-1)
+            es = es if ebs is None else torch.cat([es, ebs], dim=-1)
+            xbs = ebs = None
+        self.last_route, (self.last_path, run) = route, self.ROUTES[route]
+        if route == 'chain':
+            ox, oe = self._chain(xs, es, adj_mask, attn_dropout, return_attn_coef)
         else:
-            fx = xs.shape[-1] + (0 if xbs is None else xbs.shape[-1])
-            fe = es.shape[-1] + (0 if ebs is None else ebs.shape[-1])
-            if self.precision == 'bf16x3' and self.h == 32 and self.d == 64 and fx in (64, 96) and fe in (64, 96):
-                p['packed'] = self._packed_weights(p, fx, fe)[0]    # split once per parameter update, not per call
-                self.network().prepare(fx, fe)                      # tile plans of the 96-wide variants are built on first use
-            elif self.precision == 'bf16x3' and self.h == 64 and self.d == 128 and fx == 128 and fe in (64, 128) and xbs is None and ebs is None:
-                self.network().prepare(128, fe)                     # d = 128 (the reference default): the column-split fused kernel
-                if self.network().plan_info()['fused'] & (8 if fe == 128 else 16):
-                    p['packed'] = self._packed_weights(p, fx, fe)[0]
-            if 'packed' not in p and self.precision == 'bf16x3' and fx % 32 == 0 and fe % 32 == 0 and self.h % 16 == 0 and self.d % 16 == 0 \
-                    and xs.shape[0] * xs.shape[1] >= 4096:
-                # no fused kernel for this shape (d = 128: the reference's default embed_size): unfused composition with
-                # the dense parts on the matrix cores instead of the exact-fp32 FMA kernels
-                net = self.network()
-                x_e, e_x = self.dense_xe(es), self.dense_ex(xs)
-                ox = self.gat_x([xs, net.adj], xb=self.node_edge_n(x_e))
-                oe = self.gat_e([es, net.edge_adj], xb=self.node_edge_e(e_x))
-                return ox.reshape(lead_x + ox.shape[-2:]), oe.reshape(lead_e + oe.shape[-2:])
-            k, S = self.pack_factor(), xs.shape[0]
-            if 'packed' in p and k > 1 and S >= 16 * k:      # (a handful of snapshots -- the rollout's windows -- stay one launch)
-                # small network: k snapshots per tile.  (S, N, F) -> (S / k, k N, F) is a view; the NodeEdge values repeat per copy.
-                N, E, Sm = self.graph.n_node, self.graph.n_edge, S // k * k
-                rep = self._replica(k)
-                if self.d == 64:
-                    rep.prepare(fx, fe)
-                else:
-                    rep.prepare(128, fe)
-                pk = dict(p, ne_n_val=vn.repeat(k), ne_e_val=ve.repeat(k))
-                v = lambda t, R: None if t is None else t[:Sm].reshape(Sm // k, k * R, t.shape[-1])
-                ox, oe = _lib.spatial_layer_forward(rep, pk, v(xs, N), v(es, E), self.h, self.d, self.activation,
-                                                    _lib.PRECISION_FLAGS[self.precision], xb=v(xbs, N), eb=v(ebs, E))
-                ox, oe = ox.reshape(Sm, N, self.d), oe.reshape(Sm, E, self.d)
-                if Sm < S:     # the last S mod k snapshots one per tile
-                    t = lambda a: None if a is None else a[Sm:].contiguous()
-                    rx, re = _lib.spatial_layer_forward(self.network(), p, t(xs), t(es), self.h, self.d, self.activation,
-                                                        _lib.PRECISION_FLAGS[self.precision], xb=t(xbs), eb=t(ebs))
-                    ox, oe = torch.cat([ox, rx]), torch.cat([oe, re])
-                self.last_path = 'fused'
+            ox, oe = getattr(self, run)(ne, xs, es, xbs, ebs)
+        back = lambda t, lead: t.reshape(lead + t.shape[-2:])
+        if return_attn_coef:
+            (ox, ax), (oe, ae) = ox, oe
+            return back(ox, lead_x), back(oe, lead_e), (back(ax, lead_x), back(ae, lead_e))
+        return back(ox, lead_x), back(oe, lead_e)
+
+    def _chain(self, xs, es, adj_mask=None, attn_dropout=None, return_attn_coef=False):
+        """The unfused composition Dense -> NodeEdge -> GAT: every operator its own launch, under autograd each with its own
+        HIP backward (autograd.py); wide layers run their dense parts on the matrix cores (GATConv.forward).
+        Attention-dropout draws: gat_x, then gat_e."""
+        net = self.network()
+        x_e, e_x = self.dense_xe(es), self.dense_ex(xs)
+        ox = self.gat_x([xs, net.adj], xb=self.node_edge_n(x_e), edge_mask=adj_mask, attn_dropout=attn_dropout,
+                        return_attn_coef=return_attn_coef)
+        oe = self.gat_e([es, net.edge_adj], xb=self.node_edge_e(e_x), attn_dropout=attn_dropout, return_attn_coef=return_attn_coef)
+        return ox, oe
+
+    def _conv(self, ne, xs, es, xbs=None, ebs=None):
+        """GCN a_hat @ ([x | agg] W) + b, or Diffusion: unfused composition of the Dense / NodeEdge / sparse kernels."""
+        x_e, e_x = self.dense_xe(es), self.dense_ex(xs)
+        ox = self.gcn_x([torch.cat([xs, self.node_edge_n(x_e)], dim=-1), self.filters[0]])
+        oe = self.gcn_e([torch.cat([es, self.node_edge_e(e_x)], dim=-1), self.filters[1]])
+        return ox, oe
+
+    def _params(self, ne, fx=None, fe=None):
+        """The tensors of uds_spatial_params_t; with widths, also the packed weights of the fused kernel for them (split once
+        per parameter update, not per call) and the network's tile plans (those of the 96-wide variants are built on first use)."""
+        xe, ex, gx, ge = self.dense_xe, self.dense_ex, self.gat_x, self.gat_e
+        p = dict(xe_k=xe.kernel, xe_b=xe.bias, ex_k=ex.kernel, ex_b=ex.bias, ne_n_val=ne[0][0], ne_e_val=ne[1][0],
+                 gx_k=gx.kernel, gx_as=gx.attn_kernel_self, gx_an=gx.attn_kernel_neighs, gx_b=gx.bias,
+                 ge_k=ge.kernel, ge_as=ge.attn_kernel_self, ge_an=ge.attn_kernel_neighs, ge_b=ge.bias)
+        if fx is not None:
+            p['packed'] = self._packed_weights(p, fx, fe)[0]
+            self.network().prepare(fx, fe)
+        return p
+
+    def _launch(self, net, p, xs, es, **pieces):
+        return _lib.spatial_layer_forward(net, p, xs, es, self.h, self.d, self.activation, _lib.PRECISION_FLAGS[self.precision], **pieces)
+
+    def _entry(self, ne, xs, es, xbs=None, ebs=None):
+        return self._launch(self.network(), self._params(ne), xs, es)
+
+    def _fused(self, ne, xs, es, xbs, ebs):
+        p = self._params(ne, xs.shape[-1] + (0 if xbs is None else 32), es.shape[-1] + (0 if ebs is None else 32))
+        return self._launch(self.network(), p, xs, es, xb=xbs, eb=ebs)
+
+    def _fused_tiled(self, ne, xs, es, xbs, ebs):
+        """Small network: k snapshots per tile.  (S, N, F) -> (S / k, k N, F) is a view; the NodeEdge values repeat per copy."""
+        fx, fe = xs.shape[-1] + (0 if xbs is None else 32), es.shape[-1] + (0 if ebs is None else 32)
+        p, k, S = self._params(ne, fx, fe), self.pack_factor(), xs.shape[0]
+        N, E, Sm = self.graph.n_node, self.graph.n_edge, S // k * k
+        rep = self._replica(k)
+        rep.prepare(fx, fe)
+        pk = dict(p, ne_n_val=p['ne_n_val'].repeat(k), ne_e_val=p['ne_e_val'].repeat(k))
+        v = lambda t, R: None if t is None else t[:Sm].reshape(Sm // k, k * R, t.shape[-1])
+        ox, oe = self._launch(rep, pk, v(xs, N), v(es, E), xb=v(xbs, N), eb=v(ebs, E))
+        ox, oe = ox.reshape(Sm, N, self.d), oe.reshape(Sm, E, self.d)
+        if Sm < S:     # the last S mod k snapshots one per tile
+            t = lambda a: None if a is None else a[Sm:].contiguous()
+            rx, re = self._launch(self.network(), p, t(xs), t(es), xb=t(xbs), eb=t(ebs))
+            ox, oe = torch.cat([ox, rx]), torch.cat([oe, re])
+        return ox, oe
+
+    def _remainders(self, ne, xs, es):
+        """rest_n @ Dense_xe(es), rest_e @ Dense_ex(xs) (zeros for a side without a remainder): the Dense outputs exist only
+        for these products (the fused kernel has its own secondary MLP), so they go straight into the GEMM's operand planes
+        (uds_remainder_forward_dense) when the shapes allow and UDS_REMAINDER_MATERIALISE is unset; else they are materialised first."""
+        direct = not os.environ.get('UDS_REMAINDER_MATERIALISE')
+        rems = []
+        for (_, rest), layer, dense, src, rows in ((ne[0], self.node_edge_n, self.dense_xe, es, xs.shape[1]),
+                                                   (ne[1], self.node_edge_e, self.dense_ex, xs, es.shape[1])):
+            if rest is None:
+                rem = torch.zeros((xs.shape[0], rows, self.h), device=xs.device, dtype=torch.float32)
             else:
-                ox, oe = _lib.spatial_layer_forward(self.network(), p, xs, es, self.h, self.d, self.activation,
-                                                    _lib.PRECISION_FLAGS[self.precision], xb=xbs, eb=ebs)
-                self.last_path = 'fused' if 'packed' in p else 'unfused'
-        return ox.reshape(lead_x + ox.shape[-2:]), oe.reshape(lead_e + oe.shape[-2:])
+                rem = layer.remainder_of_dense(src, dense) if direct else None
+                if rem is None:
+                    rem = layer.remainder(dense(src))
+            rems.append(rem)
+        return rems
+
+    def _fused_rem(self, ne, xs, es, xbs=None, ebs=None):
+        """A trained dense NodeEdge bias (every checkpoint the reference trains, emulator.py:36-45): the dense remainder on the
+        MFMA GEMM, added to the NodeEdge aggregate inside the fused kernel (uds_spatial_layer_forward_rem) -- the wave-specialised
+        one at d = 64, the column-split one at d = 128."""
+        rem_n, rem_e = self._remainders(ne, xs, es)
+        return self._launch(self.network(), self._params(ne, xs.shape[-1], es.shape[-1]), xs, es, rem_x=rem_n, rem_e=rem_e)
+
+    def _rem_split96(self, ne, xs, es, xbs=None, ebs=None):
+        """d = 64 on a tile plan the wave-specialised kernel cannot hold: the remainder rides into the 96-wide split-input
+        kernel as 32 extra input columns (_packed_weights)."""
+        p = self._params(ne)
+        rem_n, rem_e = self._remainders(ne, xs, es)
+        packed, aug = self._packed_weights(p, 96, 96, remainder=True)
+        self.network().prepare(96, 96)
+        return self._launch(self.network(), dict(p, packed=packed, **aug), xs, es, xb=rem_n, eb=rem_e)
 
 
 class GraphBaseBlock(nn.Module):

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define UDS_ABI_VERSION 22
+#define UDS_ABI_VERSION 23
 
 enum {
   UDS_OK = 0,
@@ -615,7 +615,10 @@ int uds_network_destroy(uds_network_t *net);
  * runs the unfused kernels.  fx / fe = input widths of the node / link side. */
 int uds_network_prepare(uds_network_t *net, int64_t fx, int64_t fe);
 /* info8 = {fused plan available, node tiles, link tiles, max primary rows per tile, max secondary rows per
- * tile, max metadata ints per tile, LDS bytes per workgroup, t_node*1000 + t_link}. */
+ * tile, max metadata ints per tile, LDS bytes per workgroup, t_node*1000 + t_link}.
+ * info8[0] is a bit set over the plans built so far: 1 = <64,64>, 2 = <64,96> and <96,64>, 4 = <96,96>, 8 = <128,128>,
+ * 16 = <128,64> and <64,128>, 32 = the <64,64> plan also fits the wave-specialised d = 64 kernel, the only d = 64 kernel
+ * that takes a remainder (uds_spatial_layer_forward_rem refuses a 64 / 64 layer on a network without this bit). */
 int uds_network_plan_info(const uds_network_t *net, int32_t *info8);
 
 /* Host-only access to the tile planner (integer bookkeeping; works without a GPU).  A plan clusters the

@@ -223,6 +223,8 @@ def test_network_forward_trained_node_edge_bias(dev, networks, precision, embed)
         # layer is 128 wide like the others, and the column-split kernel takes the remainder beside its rows
         first_b2 = 'unfused' if embed == 64 else 'fused+remainder'
         assert paths == ['fused+remainder', 'fused+remainder', first_b2, 'fused+remainder'], paths
+        if embed == 128:
+            assert [ly.last_route for ly in list(emul.block1.layers) + list(emul.block2.layers)] == ['rem-d128'] * 4
     # and the bias matters: the same inputs through the support-only model differ visibly
     for blk in ('block1', 'block2'):
         for q in params[blk]:

@@ -203,17 +203,49 @@ def test_spatial_layer_vs_dense_masked_oracle(dev, networks, name, d, S, precisi
     if d == 64 and precision == 'bf16x3':
         # d = 64 has two carriers for the remainder: the wave-specialised kernel adds it to its aggregate (the call above); the
         # 96-wide split-input kernel takes it as 32 extra input columns (the fallback for tile plans the first one refuses)
-        assert getattr(layer, '_ws_rem_ok', True)
+        assert layer.network().plan_info()['fused'] & 32 and layer.last_route == 'rem-ws'
         layer._ws_rem_ok = False
         ox2, oe2 = layer(x.float().to(dev), e.float().to(dev))
         close(ox2, rx, tol); close(oe2, re, tol)
-        assert layer.last_path == 'fused+remainder'
+        assert layer.last_path == 'fused+remainder' and layer.last_route == 'rem-split96'
         layer._ws_rem_ok = True
     p['ne_e_b'] = torch.zeros_like(p['ne_e_b'])        # trained on the node side only
     rx, re = OD.spatial_layer_dense(x, e, p, torch.from_numpy(gph.adj.to_dense()), torch.from_numpy(gph.edge_adj.to_dense()), ne)
     load_spatial_layer(layer, p, dev)
     ox, oe = layer(x.float().to(dev), e.float().to(dev))
     close(ox, rx, tol); close(oe, re, tol)
+
+
+def _support_only_96(networks, dev):
+    gph = U.DrainageGraph.from_edges(np.array(networks['shunqing']['edges']), networks['shunqing']['n_node'])
+    p = spatial_params(gph.n_node, gph.n_edge, 96, 96, 64, seed=7)
+    layer = load_spatial_layer(U.SpatialLayer(gph, 64, 'relu', fx=96, fe=96, sparse_params=False), p, dev)
+    g = torch.Generator().manual_seed(8)
+    f = lambda rows, width: rnd(g, 2, rows, width).float().to(dev)
+    return layer, f(gph.n_node, 64), f(gph.n_node, 32), f(gph.n_edge, 64), f(gph.n_edge, 32)
+
+
+def test_spatial_layer_dropout_without_grad_keeps_the_split_columns(dev, networks):
+    """Keras' training mode under no_grad (Emulator.forward(training=True) at block 2's first layer): the chain takes xb / eb
+    concatenated, as with gradients.  The same kernels on the same bytes as the 96-wide call, hence equal bit for bit."""
+    from gnn_uds_amd.layers import DropoutStream
+    layer, x, xb, e, eb = _support_only_96(networks, dev)
+    with torch.no_grad():
+        ox, oe = layer(x, e, xb=xb, eb=eb, attn_dropout=DropoutStream(seed=5))
+        assert (layer.last_route, layer.last_path) == ('chain', 'unfused')
+        rx, re = layer(torch.cat([x, xb], dim=-1), torch.cat([e, eb], dim=-1), attn_dropout=DropoutStream(seed=5))
+    assert tuple(ox.shape) == tuple(rx.shape) == (2, x.shape[1], 64)
+    assert torch.equal(ox, rx) and torch.equal(oe, re)
+
+
+def test_spatial_layer_last_path_follows_a_training_forward(dev, networks):
+    layer, x, xb, e, eb = _support_only_96(networks, dev)
+    with torch.no_grad():
+        layer(x, e, xb=xb, eb=eb)
+    assert (layer.last_route, layer.last_path) == ('fused', 'fused')
+    layer.requires_grad_(True)
+    ox, _ = layer(x, e, xb=xb, eb=eb)
+    assert ox.requires_grad and (layer.last_route, layer.last_path) == ('chain', 'unfused')
 
 
 @pytest.mark.parametrize('precision', ['fp32', 'bf16x3'])
