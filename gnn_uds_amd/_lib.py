@@ -81,6 +81,10 @@ SYMBOLS = {
     'uds_remainder_workspace_bytes': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
     'uds_remainder_forward_dense': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_int, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr]),
     'uds_remainder_forward': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_remainder_snapshot_plan': (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, _c_ptr]),
+    'uds_remainder_snapshot': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_int, _c_i64, _c_i64, _c_ptr, _c_ptr]),
+    'uds_remainder_snapshot_pair': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr,
+                                             _c_ptr, _c_i64, _c_int, _c_i64, _c_i64, _c_ptr]),
     'uds_rowgemm_forward': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
     'uds_rowgemm_forward_pair': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64,
                                           _c_i64, _c_i64, _c_int, _c_ptr]),
@@ -856,6 +860,63 @@ def remainder_forward_dense(packed, shape, e, packed_w, bias, act, h):
     """rest @ act(e W + b) without the fp32 x_e in between (uds_remainder_forward_dense): e (..., M, F) with F 64 or 128, packed_w =
     rowgemm_pack(W (F, h)), h 32 or 64 -> (..., R, h)."""
     return _remainder_forward('uds_remainder_forward_dense', packed, shape, e, 'e', h, (packed_w, bias, act))
+
+
+def remainder_snapshot_plan(R, M, F, h):
+    """uds_remainder_snapshot_plan (host only): dict(G = snapshots per workgroup, 0 when the shape is refused; lds = LDS bytes;
+    row_blocks = 16-row blocks of `rest` per wave pass)."""
+    info = (ctypes.c_int32 * 4)()
+    _check(load().uds_remainder_snapshot_plan(int(R), int(M), int(F), int(h), info), 'uds_remainder_snapshot_plan')
+    return dict(G=int(info[0]), lds=int(info[1]), row_blocks=int(info[2]))
+
+
+def _snapshot_side(entry, side):
+    """Checks of one argument group (packed, shape, e, packed_w, bias, act, h) -> (S, F, the ABI's per-side arguments, out)."""
+    packed, shape, e, packed_w, bias, act, h = side
+    R, M = shape
+    if e.dim() < 2 or e.shape[-2] != M:
+        raise UdsError('%s: e %r against rest (%d, %d)' % (entry[4:], tuple(e.shape), R, M))
+    F = e.shape[-1]
+    S = e.numel() // (M * F) if M * F else 0
+    out = torch.empty(tuple(e.shape[:-2]) + (R, h), device=e.device, dtype=torch.float32)
+    if S == 0:
+        _nothing_to_launch(e, 'e', out)
+        return S, F, None, out
+    return S, F, [packed.data_ptr(), R, M, _dev(e, 'e'), packed_w.data_ptr(), _dev(bias, 'bias', True), _dev(out, 'out')], out
+
+
+def remainder_snapshot(packed, shape, e, packed_w, bias, act, h):
+    """rest @ act(e W + b) in one launch with x_e kept in LDS (uds_remainder_snapshot): the operands of remainder_forward_dense, no
+    workspace; shapes remainder_snapshot_plan accepts.  e (..., M, F) -> (..., R, h)."""
+    entry = 'uds_remainder_snapshot'
+    S, F, args, out = _snapshot_side(entry, (packed, shape, e, packed_w, bias, act, h))
+    if S == 0:
+        return out
+    _check(load().uds_remainder_snapshot(args[0], args[1], args[2], args[3], F, args[4], args[5], ACT[act], S, h, args[6], _stream()), entry)
+    return out
+
+
+def remainder_snapshot_pair(side0, side1):
+    """Two remainder_snapshot problems -- the node side and the link side of one layer: argument tuples (packed, shape, e, packed_w,
+    bias, act, h) that share F, h, act and the snapshot count -- in ONE launch (uds_remainder_snapshot_pair).  A side given as None
+    is skipped (its result is None); both None is an error."""
+    entry = 'uds_remainder_snapshot_pair'
+    if side0 is None and side1 is None:
+        raise UdsError('remainder_snapshot_pair: both sides are None')
+    got = [None if sd is None else _snapshot_side(entry, sd) for sd in (side0, side1)]
+    live = [(sd, g) for sd, g in zip((side0, side1), got) if sd is not None]
+    (first, (S, F, _, _)) = live[0]
+    for sd, g in live[1:]:
+        if g[0] != S or g[1] != F or sd[5] != first[5] or sd[6] != first[6]:
+            raise UdsError('remainder_snapshot_pair: the sides must share S, F, act and h: (%d, %d, %r, %d) against (%d, %d, %r, %d)'
+                           % (S, F, first[5], first[6], g[0], g[1], sd[5], sd[6]))
+    outs = tuple(None if g is None else g[3] for g in got)
+    if S == 0:
+        return outs
+    none = [None, 0, 0, None, None, None, None]
+    a0, a1 = (none if g is None else g[2] for g in got)
+    _check(load().uds_remainder_snapshot_pair(*a0, *a1, F, ACT[first[5]], S, first[6], _stream()), entry)
+    return outs
 
 
 def rowgemm_forward(x, packed, bias, f_out, act='linear', taps=1, dilation=1, out=None):

@@ -28,6 +28,7 @@
 #include "kernels_conv_stack.hpp"
 #include "kernels_fused128.hpp"
 #include "kernels_gemm.hpp"
+#include "kernels_remainder_snapshot.hpp"
 #include "kernels_recurrent.hpp"
 #include "kernels_recurrent_bwd.hpp"
 #include "kernels_tail.hpp"
@@ -600,6 +601,96 @@ int uds_remainder_forward_dense(const void *packed, int64_t R, int64_t M, const 
     hipLaunchKernelGGL(uds::k_dense_split_planes<4>, grid, dim3(256), 0, st, e, M, (int)h, Kp, reinterpret_cast<const uint4 *>(packed_w), bias, act, xh, xl);
   if (int rc = launched("uds_remainder_forward_dense", hipGetLastError())) return rc;
   return remainder_gemm_from_planes(packed, R, Kp, Nc, h, workspace, out, st);
+}
+
+// ---- rest @ act(e W + b) with x_e kept on chip: one launch per side, or one for both sides of a layer (kernels_remainder_snapshot.hpp)
+int uds_remainder_snapshot_plan(int64_t R, int64_t M, int64_t F, int64_t h, int32_t *info4) {
+  UDS_REQUIRE(info4 != nullptr, "uds_remainder_snapshot_plan: info4 is NULL");
+  const uds::SnapPlan p = uds::snapshot_plan(R, M, F, h);
+  info4[0] = p.G;
+  info4[1] = (int32_t)p.lds;
+  info4[2] = p.RB;
+  info4[3] = 0;
+  return UDS_OK;
+}
+
+namespace {
+struct SnapSideIn {
+  const void *packed;
+  int64_t R, M;
+  const float *e;
+  const void *packed_w;
+  const float *bias;
+  float *out;
+};
+
+// One checked implementation behind uds_remainder_snapshot and uds_remainder_snapshot_pair: a side with packed == NULL is skipped.
+int remainder_snapshot_run(const char *entry, const SnapSideIn (&in)[2], int64_t F, int act, int64_t S, int64_t h, uds_stream_t stream) {
+  UDS_REQUIRE(in[0].packed || in[1].packed, "%s: both sides are NULL", entry);
+  UDS_REQUIRE((F == 64 || F == 128) && (h == 32 || h == 64), "%s: F = %lld, h = %lld (F 64 or 128, h 32 or 64)", entry, (long long)F, (long long)h);
+  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "%s: unknown activation %d", entry, act);
+  UDS_REQUIRE(S >= 0 && S <= ((int64_t)1 << 24), "%s: S = %lld (0 .. 2^24)", entry, (long long)S);
+  uds::SnapArgs a{};
+  a.h = (int)h;
+  a.act = act;
+  a.S = S;
+  int64_t lds = 0;
+  for (int i = 0; i < 2; ++i) {
+    const SnapSideIn &q = in[i];
+    if (!q.packed) continue;
+    UDS_REQUIRE(q.R > 0 && q.M > 0, "%s: side %d: bad shape (%lld, %lld)", entry, i, (long long)q.R, (long long)q.M);
+    const uds::SnapPlan p = uds::snapshot_plan(q.R, q.M, F, h);
+    UDS_REQUIRE(p.G > 0, "%s: side %d: rest (%lld, %lld) is refused by uds_remainder_snapshot_plan (M <= %lld: the image of 64 columns must fit the LDS)",
+                entry, i, (long long)q.R, (long long)q.M, (long long)((uds::SNAP_LDS_MAX / 256 - uds::SNAP_PAD) / 64 * 64));
+    if (S == 0) continue;
+    UDS_REQUIRE(q.e && q.packed_w && q.out, "%s: side %d: NULL argument", entry, i);
+    UDS_REQUIRE(aligned16(q.packed) && aligned16(q.e) && aligned16(q.packed_w) && aligned16(q.bias) && aligned16(q.out),
+                "%s: side %d: buffers must be 16-byte aligned", entry, i);
+    uds::SnapSide &sd = a.side[i];
+    sd.rest = reinterpret_cast<const __bf16 *>(q.packed);
+    sd.e = q.e;
+    sd.wq = reinterpret_cast<const uint4 *>(q.packed_w);
+    sd.bias = q.bias;
+    sd.out = q.out;
+    sd.R = (int)q.R;
+    sd.M = (int)q.M;
+    sd.Kp = (int)pad_k(q.M);
+    sd.NG = p.NG;
+    sd.RB = p.RB;
+    sd.nwg = (int)((S + p.G - 1) / p.G);
+    lds = std::max(lds, p.lds);
+  }
+  if (S == 0) return UDS_OK;
+  const unsigned grid = (unsigned)(a.side[0].nwg + a.side[1].nwg);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipError_t e = hipSuccess;
+  if (F == 64) {
+    static unsigned long long done = 0;
+    if ((e = uds::set_max_lds_once(reinterpret_cast<const void *>(&uds::k_remainder_snapshot<2>), (int)uds::SNAP_LDS_MAX, done)) != hipSuccess)
+      return fail(UDS_EHIP, "%s: LDS attribute -> %s", entry, hipGetErrorString(e));
+    hipLaunchKernelGGL(uds::k_remainder_snapshot<2>, dim3(grid), dim3(uds::SNAP_WAVES * 64), (size_t)lds, st, a);
+  } else {
+    static unsigned long long done = 0;
+    if ((e = uds::set_max_lds_once(reinterpret_cast<const void *>(&uds::k_remainder_snapshot<4>), (int)uds::SNAP_LDS_MAX, done)) != hipSuccess)
+      return fail(UDS_EHIP, "%s: LDS attribute -> %s", entry, hipGetErrorString(e));
+    hipLaunchKernelGGL(uds::k_remainder_snapshot<4>, dim3(grid), dim3(uds::SNAP_WAVES * 64), (size_t)lds, st, a);
+  }
+  return launched(entry, hipGetLastError());
+}
+}  // namespace
+
+int uds_remainder_snapshot(const void *packed, int64_t R, int64_t M, const float *e, int64_t F, const void *packed_w, const float *bias, int act,
+                           int64_t S, int64_t h, float *out, uds_stream_t stream) {
+  UDS_REQUIRE(packed != nullptr, "uds_remainder_snapshot: NULL argument");
+  const SnapSideIn in[2] = {{packed, R, M, e, packed_w, bias, out}, {nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr}};
+  return remainder_snapshot_run("uds_remainder_snapshot", in, F, act, S, h, stream);
+}
+
+int uds_remainder_snapshot_pair(const void *packed0, int64_t R0, int64_t M0, const float *e0, const void *packed_w0, const float *bias0, float *out0,
+                                const void *packed1, int64_t R1, int64_t M1, const float *e1, const void *packed_w1, const float *bias1, float *out1,
+                                int64_t F, int act, int64_t S, int64_t h, uds_stream_t stream) {
+  const SnapSideIn in[2] = {{packed0, R0, M0, e0, packed_w0, bias0, out0}, {packed1, R1, M1, e1, packed_w1, bias1, out1}};
+  return remainder_snapshot_run("uds_remainder_snapshot_pair", in, F, act, S, h, stream);
 }
 
 int uds_rowgemm_forward(const float *x, int64_t B, int64_t T, int64_t R, int64_t F, const void *packed, const float *bias,

@@ -32,7 +32,7 @@ from . import _lib
 from .graph import DrainageGraph, csr_from_dense
 from . import autograd as _ag
 from .graph import csr_from_dense, edge_based_adj_csr, node_based_adj_csr
-from .layers import Dense, DiffusionConv, Dropout, DropoutStream, GCNConv, GraphBaseBlock, SpatialBlock, _glorot_uniform, _packed_kernel, _param
+from .layers import Dense, DiffusionConv, Dropout, DropoutStream, GCNConv, GraphBaseBlock, SpatialBlock, SpatialLayer, _glorot_uniform, _packed_kernel, _param
 
 
 class Conv1D(nn.Module):
@@ -233,6 +233,8 @@ def _find_keras_weight(weights, lname, kname):
 
 
 class Emulator(nn.Module):
+    _snapshot_remainder = False
+
     def __init__(self, conv=None, resnet=False, recurrent=None, args=None, precision='bf16x3', generator=None):
         super().__init__()
         g = lambda k, d=None: getattr(args, k, d)
@@ -429,6 +431,19 @@ class Emulator(nn.Module):
         self.flood = nn.ModuleList(fl)
         self.flood_out = Dense(1, 'sigmoid', in_features=fi, generator=gen, precision=pr) if self.if_flood else None      # :330
         self.e_out_layer = Dense(self.e_out, 'tanh', in_features=d, generator=gen, precision=pr)              # :336
+
+    @property
+    def snapshot_remainder(self):
+        """True: the SpatialLayers of both blocks compute the dense remainder of a trained NodeEdge bias with the one-launch snapshot
+        kernel (SpatialLayer.snapshot_remainder) where the network's shape allows.  Default False: the tiled GEMM path."""
+        return self._snapshot_remainder
+
+    @snapshot_remainder.setter
+    def snapshot_remainder(self, on):
+        self._snapshot_remainder = bool(on)
+        for m in self.modules():
+            if isinstance(m, SpatialLayer):
+                m.snapshot_remainder = self._snapshot_remainder
 
     # ------------------------------------------------------------------ the non-graph baseline (conv False)
     def _build_mlp(self, d, h, H, L, a, gen, pr):

@@ -559,6 +559,10 @@ class SpatialLayer(nn.Module):
     forward(x, e): x (..., N, Fx), e (..., E, Fe) -> (..., N, d), (..., E, d).  Uses the fused C-ABI
     entry uds_spatial_layer_forward (concats are never materialised)."""
 
+    # True: on the remainder routes, rest @ Dense(.) of both sides runs as one launch of the snapshot kernel
+    # (uds_remainder_snapshot_pair: x_e stays in LDS) where uds_remainder_snapshot_plan accepts the network; Emulator.snapshot_remainder
+    snapshot_remainder = False
+
     def __init__(self, graph, embed_size, activation='relu', fx=None, fe=None, sparse_params=None, net=None,
                  generator=None, precision='bf16x3', conv='GAT', filters=None, attn_heads=1):
         super().__init__()
@@ -611,6 +615,8 @@ class SpatialLayer(nn.Module):
         self._packed = None       # (parameter versions, packed bf16 hi/lo fragments) of the four GEMM kernels
         self.last_path = None     # which kernels the last forward ran: 'fused', 'fused+remainder', 'unfused' (tests, bench)
         self.last_route = None    # ... and the row of the route table (`route`) it took
+        self.last_remainder = None   # per side what computed the dense remainder: 'snapshot', 'gemm' or None (no remainder); None before
+                                     # a forward on a remainder route
         self._ws_rem_ok = None    # override for tests: False sends a d = 64 remainder to 'rem-split96' whatever the plan says
 
     def _packed_weights(self, p, fx, fe, remainder=False):
@@ -756,6 +762,7 @@ class SpatialLayer(nn.Module):
             es = es if ebs is None else torch.cat([es, ebs], dim=-1)
             xbs = ebs = None
         self.last_route, (self.last_path, run) = route, self.ROUTES[route]
+        self.last_remainder = (None, None)      # the remainder routes say what they ran (_remainders)
         if route == 'chain':
             ox, oe = self._chain(xs, es, adj_mask, attn_dropout, return_attn_coef)
         else:
@@ -826,11 +833,18 @@ class SpatialLayer(nn.Module):
     def _remainders(self, ne, xs, es):
         """rest_n @ Dense_xe(es), rest_e @ Dense_ex(xs) (zeros for a side without a remainder): the Dense outputs exist only
         for these products (the fused kernel has its own secondary MLP), so they go straight into the GEMM's operand planes
-        (uds_remainder_forward_dense) when the shapes allow and UDS_REMAINDER_MATERIALISE is unset; else they are materialised first."""
+        (uds_remainder_forward_dense) when the shapes allow and UDS_REMAINDER_MATERIALISE is unset; else they are materialised first.
+        With snapshot_remainder set (and UDS_REMAINDER_MATERIALISE unset) both products are ONE launch that keeps the Dense output in
+        LDS (_snapshot_remainders) where uds_remainder_snapshot_plan accepts the network.  last_remainder says per side what ran."""
         direct = not os.environ.get('UDS_REMAINDER_MATERIALISE')
+        sides = ((ne[0], self.node_edge_n, self.dense_xe, es, xs.shape[1]), (ne[1], self.node_edge_e, self.dense_ex, xs, es.shape[1]))
+        snap = self._snapshot_remainders(sides) if self.snapshot_remainder and direct else None
+        self.last_remainder = tuple(None if rest is None else ('gemm' if snap is None else 'snapshot') for (_, rest), *_ in sides)
+        if snap is not None:
+            return [torch.zeros((xs.shape[0], rows, self.h), device=xs.device, dtype=torch.float32) if rem is None else rem
+                    for rem, (*_, rows) in zip(snap, sides)]
         rems = []
-        for (_, rest), layer, dense, src, rows in ((ne[0], self.node_edge_n, self.dense_xe, es, xs.shape[1]),
-                                                   (ne[1], self.node_edge_e, self.dense_ex, xs, es.shape[1])):
+        for (_, rest), layer, dense, src, rows in sides:
             if rest is None:
                 rem = torch.zeros((xs.shape[0], rows, self.h), device=xs.device, dtype=torch.float32)
             else:
@@ -839,6 +853,27 @@ class SpatialLayer(nn.Module):
                     rem = layer.remainder(dense(src))
             rems.append(rem)
         return rems
+
+    def _snapshot_remainders(self, sides):
+        """The sides that have a remainder in ONE launch with x_e kept on chip (uds_remainder_snapshot_pair) -> per side the
+        remainder or None; None when a side's shape is not one uds_remainder_snapshot_plan accepts (the caller keeps the GEMM path)."""
+        args = []
+        for (_, rest), layer, dense, src, _ in sides:
+            if rest is None:
+                args.append(None)
+                continue
+            F, h = src.shape[-1], dense.units
+            if dense.precision != 'bf16x3' or F not in (64, 128) or h not in (32, 64) or not src.is_cuda \
+                    or not _lib.remainder_snapshot_plan(rest.shape[0], rest.shape[1], F, h)['G']:
+                return None
+            if layer._rest_packed is None:
+                layer._rest_packed = _lib.remainder_pack(rest)
+            args.append((layer._rest_packed, tuple(rest.shape), src.contiguous(), _packed_kernel(dense, dense.kernel), dense.bias,
+                         dense.activation, h))
+        live = [a for a in args if a is not None]
+        if len(live) == 2 and (live[0][2].shape[-1] != live[1][2].shape[-1] or live[0][5] != live[1][5]):
+            return None
+        return _lib.remainder_snapshot_pair(*args)
 
     def _fused_rem(self, ne, xs, es, xbs=None, ebs=None):
         """A trained dense NodeEdge bias (every checkpoint the reference trains, emulator.py:36-45): the dense remainder on the

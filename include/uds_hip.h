@@ -293,6 +293,23 @@ int uds_remainder_forward_dense(const void *packed, int64_t R, int64_t M, const 
                                 const float *bias, int act, int64_t S, int64_t h, void *workspace, float *out,
                                 uds_stream_t stream);
 
+/* The same product for the networks the reference ships (tens to a few hundred rows), in ONE launch and without a workspace: a
+ * workgroup computes x_e = act(e W + b) of G consecutive snapshots into an LDS image, multiplies it by `rest` (streamed from the
+ * planes of uds_remainder_pack, the same `packed` as above) and writes out (S, R, h) once.  F = 64 or 128, h = 32 or 64; no host
+ * synchronisation and no allocation (capturable).
+ * uds_remainder_snapshot_plan is host only (works without a GPU): info4 = {G = snapshots per workgroup, 0 when the shape is refused
+ * (M above 576: the image of 64 columns does not fit the LDS; F or h out of range), LDS bytes, row blocks per wave pass, 0}.
+ * The launch entries return UDS_EINVAL for what the plan refuses.  uds_remainder_snapshot_pair runs two problems that share F, h,
+ * act and S -- the node side and the link side of one layer -- in one launch; a side whose `packed` is NULL is skipped (both NULL
+ * is an error). */
+int uds_remainder_snapshot_plan(int64_t R, int64_t M, int64_t F, int64_t h, int32_t *info4);
+int uds_remainder_snapshot(const void *packed, int64_t R, int64_t M, const float *e, int64_t F, const void *packed_w,
+                           const float *bias, int act, int64_t S, int64_t h, float *out, uds_stream_t stream);
+int uds_remainder_snapshot_pair(const void *packed0, int64_t R0, int64_t M0, const float *e0, const void *packed_w0,
+                                const float *bias0, float *out0, const void *packed1, int64_t R1, int64_t M1, const float *e1,
+                                const void *packed_w1, const float *bias1, float *out1, int64_t F, int act, int64_t S, int64_t h,
+                                uds_stream_t stream);
+
 /* keras Dense(64) (64 inputs) + prefix sum over time + residual + activation in one pass (matrix cores, split-bf16):
  *   out[b,t,r,:] = act( sum_{t' <= t} (x[b,t',r,:] @ kernel + bias) + res[b,0,r,:] ),   x, out: (B,T,R,64), res: (B,1,R,64) or NULL.
  * `packed` = uds_rowgemm_pack of the (64, 64) kernel.  The `dense_resx` layer and the `cumsum(x_out, axis=1) + res` that
