@@ -115,6 +115,9 @@ SYMBOLS = {
     'uds_wgrad': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     'uds_wgrad_wide_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_int]),
     'uds_wgrad_wide': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_node_edge_wgrad_plan': (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64, _c_ptr]),
+    'uds_node_edge_wgrad_workspace_bytes': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    'uds_node_edge_wgrad': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     'uds_network_create': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, ctypes.POINTER(_c_ptr)]),
     'uds_network_destroy': (_c_int, [_c_ptr]),
     'uds_network_prepare': (_c_int, [_c_ptr, _c_i64, _c_i64]),
@@ -1518,6 +1521,39 @@ def wgrad_wide(a, g, shift=0, with_bias=True):
     _check(lib.uds_wgrad_wide(_dev(a, 'a'), _dev(g, 'g'), B, T, R, F, H, shift, int(with_bias), _dev(ws, 'workspace'), _dev(dk, 'd_kernel'),
                               _dev(db, 'd_bias', True), _stream()), 'uds_wgrad_wide')
     return dk, db
+
+
+def node_edge_wgrad_plan(R, M, S, h):
+    """uds_node_edge_wgrad_plan (host only): dict(ksteps = k-steps of 32 per snapshot, the instantiation, 0 when the shape is
+    refused; pieces = pieces of the reduction over S; spp = snapshots per piece; padded = h is no multiple of 32)."""
+    info = (ctypes.c_int32 * 4)()
+    _check(load().uds_node_edge_wgrad_plan(int(R), int(M), int(S), int(h), info), 'uds_node_edge_wgrad_plan')
+    return dict(ksteps=int(info[0]), pieces=int(info[1]), spp=int(info[2]), padded=bool(info[3]))
+
+
+def node_edge_wgrad_supported(h):
+    return load().uds_node_edge_wgrad_workspace_bytes(1, 1, 1, int(h)) > 0
+
+
+def node_edge_wgrad(g, x, inci=None):
+    """(d_bias, d_weight) of a dense-parameter NodeEdge (uds_node_edge_wgrad): d_bias[r, m] = sum_{s, k} g[s, r, k] x[s, m, k] for
+    g (S, R, h), x (S, M, h) in their own layouts, d_weight = d_bias * inci (None without inci).  Matrix cores, split-bf16,
+    deterministic."""
+    lib = load()
+    if g.dim() != 3 or x.dim() != 3 or g.shape[0] != x.shape[0] or g.shape[2] != x.shape[2]:
+        raise UdsError('node_edge_wgrad: g %r and x %r disagree' % (tuple(g.shape), tuple(x.shape)))
+    S, R, h = g.shape
+    M = x.shape[1]
+    if inci is not None and tuple(inci.shape) != (R, M):
+        raise UdsError('node_edge_wgrad: inci %r against (%d, %d)' % (tuple(inci.shape), R, M))
+    if lib.uds_node_edge_wgrad_workspace_bytes(R, M, 1, h) <= 0:
+        raise UdsError('node_edge_wgrad: R=%d, M=%d, h=%d not supported' % (R, M, h))
+    db = torch.empty((R, M), device=g.device, dtype=torch.float32)
+    dw = torch.empty((R, M), device=g.device, dtype=torch.float32) if inci is not None else None
+    ws = torch.empty(max(lib.uds_node_edge_wgrad_workspace_bytes(R, M, S, h) // 4, 1), device=g.device, dtype=torch.float32)
+    _check(lib.uds_node_edge_wgrad(_dev(g, 'g') if S else None, _dev(x, 'x') if S else None, S, R, M, h, _dev(inci, 'inci', True),
+                                   _dev(ws, 'workspace'), _dev(db, 'd_bias'), _dev(dw, 'd_weight', True), _stream()), 'uds_node_edge_wgrad')
+    return db, dw
 
 
 def csr_sddmm(handle, a, b, out=None):

@@ -13,10 +13,11 @@ operator of the forward carries its own backward, so `loss.backward()` on an `Em
     AttnSumPoolFn  GlobalAttnSumPool(x | e)        uds_attn_sum_pool_backward: d x, d e and d attn_kernel in one pass, 2 launches
     CumsumActFn    relu(cumsum_T(x) + res)         reverse cumulative sum
     FlowBalanceFn  post_proc_tf incidence sums     gather along the link end nodes
-    SpatialLayerFn the fused spatial layer forward, backward through the unfused chain above (intermediates recomputed)
 
     RecurrentFn    GRU / LSTM time recurrence     back-propagation through time in one launch (uds_recurrent_backward)
     RemainderFn    dense off-support NodeEdge bias  forward and d x on the split-bf16 MFMA GEMM (uds_remainder_forward)
+    NodeEdgeDenseFn  a whole dense-parameter NodeEdge (NodeEdge.dense_train)  forward and d x the same GEMM on weight o inci + bias,
+                   d bias and d weight in one call of uds_node_edge_wgrad
 
 Weight gradients are GEMMs with a huge reduction dimension (rows) and tiny outputs: the split-K MFMA kernels uds_wgrad (up to
 128 input rows with the bias row, 64 columns) and uds_wgrad_wide (up to 256 + the bias row, 256 columns), chosen by
@@ -167,6 +168,34 @@ class RemainderFn(torch.autograd.Function):
             R, M = rest.shape
             drest = torch.matmul(g.permute(1, 0, 2).reshape(R, -1), xs.permute(1, 0, 2).reshape(M, -1).t())
         return drest, dxs
+
+
+class NodeEdgeDenseFn(torch.autograd.Function):
+    """out = (weight o inci + bias) @ xs for the reference's dense (R, M) parameters (emulator.py:27-45), xs (S, M, h), as ONE
+    operator: the full matrix Mx goes through the split-bf16 MFMA GEMM forward (uds_remainder_forward) and transposed for d xs,
+    and (d bias, d weight) = (sum_s g_s xs_s^T, the same o inci) come from one call of uds_node_edge_wgrad on g and xs as they
+    lie.  No spmm, sddmm, indexed read or mask product; the support entries are split-bf16 here, not exact fp32, which is why
+    the route is a flag (NodeEdge.dense_train).  module: the NodeEdge (its dense incidence)."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, xs, module):
+        xs = xs.contiguous()
+        inci = module.dense_incidence()
+        mx = torch.addcmul(bias, weight, inci)
+        ctx.save_for_backward(mx, xs, inci)
+        return _lib.remainder_forward(_lib.remainder_pack(mx), tuple(mx.shape), xs)
+
+    @staticmethod
+    def backward(ctx, g):
+        mx, xs, inci = ctx.saved_tensors
+        g = g.contiguous()
+        dxs = dw = db = None
+        if ctx.needs_input_grad[2]:
+            mt = mx.t().contiguous()
+            dxs = _lib.remainder_forward(_lib.remainder_pack(mt), tuple(mt.shape), g)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            db, dw = _lib.node_edge_wgrad(g, xs, inci if ctx.needs_input_grad[0] else None)
+        return dw, (db if ctx.needs_input_grad[1] else None), dxs, None
 
 
 class RecurrentFn(torch.autograd.Function):

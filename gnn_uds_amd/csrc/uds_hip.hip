@@ -24,6 +24,7 @@
 #include "kernels_fused_ws.hpp"
 #include "kernels_rowgemm.hpp"
 #include "kernels_wgrad.hpp"
+#include "kernels_node_edge_wgrad.hpp"
 #include "kernels_conv_stream.hpp"
 #include "kernels_conv_stack.hpp"
 #include "kernels_fused128.hpp"
@@ -1511,6 +1512,48 @@ int uds_wgrad_wide(const float *a, const float *g, int64_t B, int64_t T, int64_t
                        p.ld_f + 1, p.ld_n, 1, (int)H, d_bias);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(UDS_EHIP, "uds_wgrad_wide: reduce launch -> %s", hipGetErrorString(e));
+  return UDS_OK;
+}
+
+// ---- d bias, d weight of a dense-parameter NodeEdge from g (S, R, h) and x (S, M, h) in their own layouts (kernels_node_edge_wgrad.hpp)
+int uds_node_edge_wgrad_plan(int64_t R, int64_t M, int64_t S, int64_t h, int32_t *info4) {
+  UDS_REQUIRE(info4 != nullptr, "uds_node_edge_wgrad_plan: info4 is NULL");
+  const uds::NodeEdgeWgradPlan p = uds::node_edge_wgrad_plan(R, M, S, h);
+  info4[0] = p.ks;
+  info4[1] = p.pieces;
+  info4[2] = p.spp;
+  info4[3] = p.padded;
+  return UDS_OK;
+}
+
+int64_t uds_node_edge_wgrad_workspace_bytes(int64_t R, int64_t M, int64_t S, int64_t h) {
+  const uds::NodeEdgeWgradPlan p = uds::node_edge_wgrad_plan(R, M, S, h);
+  return p.ks ? (int64_t)p.pieces * R * M * (int64_t)sizeof(float) : 0;
+}
+
+int uds_node_edge_wgrad(const float *g, const float *x, int64_t S, int64_t R, int64_t M, int64_t h, const float *inci, void *workspace,
+                        float *d_bias, float *d_weight, uds_stream_t stream) {
+  const uds::NodeEdgeWgradPlan p = uds::node_edge_wgrad_plan(R, M, S, h);
+  UDS_REQUIRE(p.ks, "uds_node_edge_wgrad: S=%lld R=%lld M=%lld h=%lld not supported (h %% 4 == 0, 4 <= h <= 64, R, M >= 1, 0 <= S <= 2^24)",
+              (long long)S, (long long)R, (long long)M, (long long)h);
+  UDS_REQUIRE(d_bias != nullptr, "uds_node_edge_wgrad: d_bias is NULL");
+  UDS_REQUIRE(!d_weight || inci, "uds_node_edge_wgrad: d_weight needs inci");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (S == 0) {
+    hipError_t e0 = hipMemsetAsync(d_bias, 0, sizeof(float) * R * M, st);
+    if (e0 == hipSuccess && d_weight) e0 = hipMemsetAsync(d_weight, 0, sizeof(float) * R * M, st);
+    if (e0 != hipSuccess) return fail(UDS_EHIP, "uds_node_edge_wgrad: memset -> %s", hipGetErrorString(e0));
+    return UDS_OK;
+  }
+  UDS_REQUIRE(g && x && workspace, "uds_node_edge_wgrad: NULL argument");
+  UDS_REQUIRE(aligned16(g) && aligned16(x), "uds_node_edge_wgrad: g and x must be 16-byte aligned");
+  uds::NodeEdgeWgradArgs a{g, x, static_cast<float *>(workspace), S, (int)R, (int)M, (int)h, p.spp, (int)p.tiles_m};
+  if (int rc = launched("uds_node_edge_wgrad", uds::launch_node_edge_wgrad(a, p, st))) return rc;
+  const int64_t n_out = R * M;
+  hipLaunchKernelGGL(uds::k_node_edge_wgrad_reduce, dim3((unsigned)((n_out + 15) / 16)), dim3(256), 0, st, a.partial, p.pieces, n_out,
+                     d_weight ? inci : nullptr, d_bias, d_weight);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(UDS_EHIP, "uds_node_edge_wgrad: reduce launch -> %s", hipGetErrorString(e));
   return UDS_OK;
 }
 

@@ -32,7 +32,7 @@ from . import _lib
 from .graph import DrainageGraph, csr_from_dense
 from . import autograd as _ag
 from .graph import csr_from_dense, edge_based_adj_csr, node_based_adj_csr
-from .layers import Dense, DiffusionConv, Dropout, DropoutStream, GCNConv, GraphBaseBlock, SpatialBlock, SpatialLayer, _glorot_uniform, _packed_kernel, _param
+from .layers import Dense, DiffusionConv, Dropout, DropoutStream, GCNConv, GraphBaseBlock, NodeEdge, SpatialBlock, SpatialLayer, _glorot_uniform, _packed_kernel, _param
 
 
 class Conv1D(nn.Module):
@@ -234,6 +234,7 @@ def _find_keras_weight(weights, lname, kname):
 
 class Emulator(nn.Module):
     _snapshot_remainder = False
+    _dense_node_edge_train = False
 
     def __init__(self, conv=None, resnet=False, recurrent=None, args=None, precision='bf16x3', generator=None):
         super().__init__()
@@ -444,6 +445,20 @@ class Emulator(nn.Module):
         for m in self.modules():
             if isinstance(m, SpatialLayer):
                 m.snapshot_remainder = self._snapshot_remainder
+
+    @property
+    def dense_node_edge_train(self):
+        """True: every dense-parameter NodeEdge of the model trains as one autograd Function (NodeEdge.dense_train: the whole
+        weight o inci + bias on the split-bf16 GEMM, d bias and d weight from uds_node_edge_wgrad).  Default False: the support
+        on the exact-fp32 CSR kernels plus the off-support remainder."""
+        return self._dense_node_edge_train
+
+    @dense_node_edge_train.setter
+    def dense_node_edge_train(self, on):
+        self._dense_node_edge_train = bool(on)
+        for m in self.modules():
+            if isinstance(m, NodeEdge):
+                m.dense_train = self._dense_node_edge_train
 
     # ------------------------------------------------------------------ the non-graph baseline (conv False)
     def _build_mlp(self, d, h, H, L, a, gen, pr):

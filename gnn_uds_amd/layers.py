@@ -446,6 +446,10 @@ class NodeEdge(nn.Module):
     (N = 50k: 13 GB each) pass sparse=True: parameters then have one entry per support element
     (columns ascending inside a row)."""
 
+    # True: a dense-parameter layer trains as ONE autograd Function (autograd.NodeEdgeDenseFn: the whole matrix on the split-bf16
+    # GEMM, d bias and d weight from uds_node_edge_wgrad) where _dense_train_ok allows; Emulator.dense_node_edge_train
+    dense_train = False
+
     def __init__(self, inci, sparse=False, device='cpu', generator=None):
         super().__init__()
         if isinstance(inci, CSR):
@@ -469,6 +473,7 @@ class NodeEdge(nn.Module):
         self._val_cache = None
         self._rest_packed = None
         self.precision = 'bf16x3'      # of the dense remainder GEMM; SpatialLayer sets it to its own
+        self.last_train_path = None    # 'dense' or 'support+remainder': what the last forward under autograd ran
 
     def support_values(self):
         """weight*inci + bias on the support (nnz,), plus the off-support remainder of bias or None."""
@@ -518,11 +523,34 @@ class NodeEdge(nn.Module):
             self._handle = _lib.CsrHandle(self.csr)
         return self._handle
 
+    def dense_incidence(self):
+        """The incidence values as a dense (R, M) tensor on the parameters' device: built once per module (a non-persistent buffer)."""
+        if '_inci_dense' not in self._buffers:
+            dense = torch.zeros(self.shape, device=self._flat.device, dtype=torch.float32)
+            dense.reshape(-1)[self._flat] = self._ival
+            self.register_buffer('_inci_dense', dense, persistent=False)
+        if self._inci_dense.device != self.weight.device:
+            self._inci_dense = self._inci_dense.to(self.weight.device)
+        return self._inci_dense
+
+    def _dense_train_ok(self, xs):
+        """The one-Function route (dense_train) takes dense (R, M) parameters that both train, at 'bf16x3', on the GPU, at an h
+        uds_node_edge_wgrad and the GEMM take."""
+        h = xs.shape[-1]
+        return self.dense_train and not self.sparse and self.precision == 'bf16x3' and h % 4 == 0 and 4 <= h <= 64 and xs.is_cuda \
+            and self.weight.is_cuda and self.weight.requires_grad and self.bias.requires_grad
+
     def forward(self, x):
         if x.shape[-2] != self.shape[1]:
             raise _lib.UdsError('NodeEdge expects %d elements on axis -2, got %r' % (self.shape[1], tuple(x.shape)))
         xs, lead = _flatten_snapshots(x)
-        if _ag.grad_on(xs, self.weight, self.bias):
+        grad = _ag.grad_on(xs, self.weight, self.bias)
+        if grad and self._dense_train_ok(xs):
+            self.last_train_path = 'dense'      # the whole layer as one Function
+            out = _ag.NodeEdgeDenseFn.apply(self.weight, self.bias, xs, self)
+            return out.reshape(lead + out.shape[-2:])
+        if grad:
+            self.last_train_path = 'support+remainder'
             # training: the support values are re-derived under autograd (gradients reach `weight` and `bias`); with the
             # reference's dense (R, M) parameters the bias also trains OFF the support (emulator.py:36-39,44), which is
             # a dense GEMM and only feasible for small networks -- sparse=True keeps one trainable entry per support element

@@ -618,6 +618,23 @@ int64_t uds_wgrad_wide_workspace_floats(int64_t rows, int64_t F, int64_t H, int 
 int uds_wgrad_wide(const float *a, const float *g, int64_t B, int64_t T, int64_t R, int64_t F, int64_t H, int64_t shift,
                    int with_bias, float *workspace, float *d_kernel, float *d_bias, uds_stream_t stream);
 
+/* Parameter gradient of a dense-parameter NodeEdge, out[s] = (weight o inci + bias) @ x[s] (emulator.py:27-45 under the tape of
+ * :457-484): d_bias[r, m] = sum_{s, k} g[s, r, k] x[s, m, k] and, when inci and d_weight are both given, d_weight = d_bias * inci
+ * (one fp32 multiply per element).  g (S, R, h) and x (S, M, h) are read where they lie (h contiguous: the MFMA operands' own
+ * layout), no permuted or transposed copy, no library.  Split-bf16 (hi + lo, three products, fp32 accumulate).  The output is cut
+ * into 64 x 64 tiles and the reduction over S into pieces whose count depends on (R, M, S, h) alone; the partials
+ * (uds_node_edge_wgrad_workspace_bytes() bytes of `workspace`, all of them written) are summed in a fixed order by a second
+ * launch: no atomics, the same inputs give the same bits.  No allocation, no synchronisation.
+ * Accepted: h % 4 == 0, 4 <= h <= 64 (an h that is no multiple of 32 is padded with zeros on chip), R, M >= 1, 0 <= S <= 2^24,
+ * at most 2^20 tiles; g and x 16-byte aligned.  S == 0 writes zeros.  Anything else, a NULL d_bias, or d_weight without inci
+ * returns -22, launches nothing and leaves the outputs untouched; the workspace size is then 0.
+ * uds_node_edge_wgrad_plan is host only (works without a GPU): info4 = {k-steps of 32 per snapshot = the instantiation
+ * k_node_edge_wgrad<1 | 2>, 0 when the shape is refused; pieces; snapshots per piece; 1 when h is padded}. */
+int uds_node_edge_wgrad_plan(int64_t R, int64_t M, int64_t S, int64_t h, int32_t *info4);
+int64_t uds_node_edge_wgrad_workspace_bytes(int64_t R, int64_t M, int64_t S, int64_t h);
+int uds_node_edge_wgrad(const float *g, const float *x, int64_t S, int64_t R, int64_t M, int64_t h, const float *inci,
+                        void *workspace, float *d_bias, float *d_weight, uds_stream_t stream);
+
 /* ---- one spatial layer (node side + link side) ---------------------------------------------- */
 typedef struct uds_network uds_network_t;
 
