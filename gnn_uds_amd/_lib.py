@@ -122,6 +122,8 @@ SYMBOLS = {
     'uds_network_destroy': (_c_int, [_c_ptr]),
     'uds_network_prepare': (_c_int, [_c_ptr, _c_i64, _c_i64]),
     'uds_network_plan_info': (_c_int, [_c_ptr, _c_ptr]),
+    'uds_network_fused_launches': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_i64, _c_ptr]),
+    'uds_fused_chunk': (_c_int, [_c_i64, _c_i64, ctypes.POINTER(_c_i64)]),
     'uds_tile_plan_create': (_c_int, [_c_ptr] * 8 + [_c_i64, _c_i64] + [ctypes.c_int32] * 4 + [ctypes.POINTER(_c_ptr)]),
     'uds_tile_plan_destroy': (_c_int, [_c_ptr]),
     'uds_tile_plan_sizes': (_c_int, [_c_ptr, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _c_ptr]),
@@ -355,10 +357,30 @@ class NetworkHandle:
         out['t_node'], out['t_link'] = out['t_code'] // 1000, out['t_code'] % 1000
         return out
 
+    def fused_launches(self, fx, fe, d):
+        """prepare(fx, fe), then the launches a fused forward of a layer (fx, fe, d) makes on this network
+        (include/uds_hip.h: uds_network_fused_launches): a list of 0, 1 or 2 dict(kernel, fp, fs, side_mask, n_tiles), kernel one
+        of FUSED_KERNELS; fused_chunk(S, n_tiles) is the chunk length of such a launch over S snapshots."""
+        self.prepare(fx, fe)
+        info = np.zeros(11, dtype=np.int32)
+        _check(load().uds_network_fused_launches(self._h, int(fx), int(fe), int(d), info.ctypes.data), 'uds_network_fused_launches')
+        return [dict(kernel=FUSED_KERNELS[int(k)], fp=int(fp), fs=int(fs), side_mask=int(m), n_tiles=int(t))
+                for k, fp, fs, m, t in info[1:1 + 5 * int(info[0])].reshape(-1, 5)]
+
     def __del__(self):
         h, self._h = getattr(self, '_h', None), None
         if h is not None and _lib is not None:
             _lib.uds_network_destroy(h)
+
+
+FUSED_KERNELS = {1: 'k_fused_ws', 2: 'k_fused_tile', 3: 'k_fused_cs'}      # UDS_KERNEL_* of include/uds_hip.h
+
+
+def fused_chunk(S, working_tiles):
+    """Snapshots per workgroup of a fused spatial launch of S snapshots over working_tiles tiles (host only, no device needed)."""
+    c = _c_i64()
+    _check(load().uds_fused_chunk(int(S), int(working_tiles), ctypes.byref(c)), 'uds_fused_chunk')
+    return c.value
 
 
 def tile_plan(graph, t_node=48, t_link=48, p_limit=0, q_limit=0, blocks=False):

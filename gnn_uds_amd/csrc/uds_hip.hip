@@ -224,6 +224,50 @@ int64_t pick_chunk(int64_t S, int64_t working_tiles) {
   return chunk;
 }
 
+// One launch of the fused spatial layer: the kernel (UDS_KERNEL_*) and its variant <fp, fs>, the plan slot it reads, the side
+// whose tiles it takes (< 0: the merged list of both sides) and how many those are.
+struct fused_launch {
+  int kernel, fp, fs, slot, side, n_tiles, side_mask;
+};
+
+// The launches of a layer (fx, fe, h, d) on the plans this network holds -> their number, 0 when the fused kernels do not take
+// it.  uds_spatial_layer_forward launches what this returns and uds_network_fused_launches reports it.  (Split inputs are
+// 64 + 32 columns, so a 64 / 64 or a 128-wide layer never has them: the choice does not depend on how the rows arrive.)
+int fused_launches(const uds_network *net, int64_t fx, int64_t fe, int64_t h, int64_t d, fused_launch out[2]) {
+  auto put = [&](int i, int kernel, int fp, int fs, int side) {
+    const int slot = slot_index(fp, fs);
+    const uds::NetworkPlan &pl = net->slot[slot].plan;
+    out[i] = fused_launch{kernel, fp, fs, slot, side, side < 0 ? pl.n_tiles : pl.side[side].n_tiles, side < 0 ? 3 : (1 << side)};
+  };
+  if (h == uds::F128_H && d == uds::F128_D && fx == 128 && (fe == 128 || fe == 64) && net->slot[slot_index(128, (int)fe)].ok &&
+      net->slot[slot_index((int)fe, 128)].ok) {
+    // d = 128: the column-split fused kernel (kernels_fused128.hpp); 64-wide link rows -> one launch per side
+    if (fe == 128) {
+      put(0, UDS_KERNEL_FUSED_CS, 128, 128, -1);
+      return 1;
+    }
+    put(0, UDS_KERNEL_FUSED_CS, 128, 64, 0);      // node tiles: 128-wide nodes fed by 64-wide links
+    put(1, UDS_KERNEL_FUSED_CS, 64, 128, 1);      // link tiles: 64-wide links fed by 128-wide nodes
+    return 2;
+  }
+  // (rows of one snapshot are addressed with a 32-bit byte offset from a per-snapshot base: N, E < 2^31 / 384)
+  const bool shape_ok = h == uds::FUSED_H && d == uds::FUSED_D && (fx == 64 || fx == 96) && (fe == 64 || fe == 96) &&
+                        std::max(net->adj->n_rows, net->edge_adj->n_rows) * 384 < ((int64_t)1 << 31);
+  // node tiles run the variant <fx, fe>, link tiles <fe, fx>: one launch when they coincide, else one per side
+  if (!shape_ok || !net->slot[slot_index((int)fx, (int)fe)].ok || !net->slot[slot_index((int)fe, (int)fx)].ok) return 0;
+  if (fx == fe) {
+    bool ws = fx == 64 && ws_plan_ok(net->slot[0]);
+#ifdef UDS_KNOBS
+    if (std::getenv("UDS_NO_WS")) ws = false;      // experiment builds only: k_fused_tile<64, 64> in place of k_fused_ws
+#endif
+    put(0, ws ? UDS_KERNEL_FUSED_WS : UDS_KERNEL_FUSED_TILE, (int)fx, (int)fe, -1);
+    return 1;
+  }
+  put(0, UDS_KERNEL_FUSED_TILE, (int)fx, (int)fe, 0);      // workgroups go round-robin to the XCDs: a grid of working tiles only keeps the XCDs level
+  put(1, UDS_KERNEL_FUSED_TILE, (int)fe, (int)fx, 1);
+  return 2;
+}
+
 hipError_t pack_weights(const float *W, int K, int F_out, uint4 *out, hipStream_t st) {
   const int total = (K / 32) * (F_out / 16) * 64;
   hipLaunchKernelGGL(uds::k_pack_weight_frags, dim3((total + 255) / 256), dim3(256), 0, st, W, K, F_out, out);
@@ -1672,6 +1716,31 @@ int uds_network_plan_info(const uds_network_t *net, int32_t *info8) {
   return UDS_OK;
 }
 
+int uds_fused_chunk(int64_t S, int64_t working_tiles, int64_t *chunk) {
+  UDS_REQUIRE(chunk != nullptr, "uds_fused_chunk: NULL argument");
+  UDS_REQUIRE(S >= 1 && working_tiles >= 1 && S < ((int64_t)1 << 31) && working_tiles < ((int64_t)1 << 31),
+              "uds_fused_chunk: bad sizes S=%lld tiles=%lld (1 .. 2^31 - 1)", (long long)S, (long long)working_tiles);
+  *chunk = pick_chunk(S, working_tiles);
+  return UDS_OK;
+}
+
+int uds_network_fused_launches(const uds_network_t *net, int64_t fx, int64_t fe, int64_t d, int32_t *info11) {
+  UDS_REQUIRE(net && info11, "uds_network_fused_launches: NULL argument");
+  fused_launch l[2];
+  const int n = fused_launches(net, fx, fe, d / 2, d, l);
+  std::fill(info11, info11 + 11, 0);
+  info11[0] = n;
+  for (int i = 0; i < n; ++i) {
+    int32_t *o = info11 + 1 + 5 * i;
+    o[0] = l[i].kernel;
+    o[1] = l[i].fp;
+    o[2] = l[i].fs;
+    o[3] = l[i].side_mask;
+    o[4] = l[i].n_tiles;
+  }
+  return UDS_OK;
+}
+
 // ---- host-only tile planner access (integer bookkeeping, testable without a GPU) ----
 int uds_tile_plan_create(const int32_t *adj_rowptr, const int32_t *adj_col, const int32_t *eadj_rowptr, const int32_t *eadj_col,
                          const int32_t *incn_rowptr, const int32_t *incn_col, const int32_t *ince_rowptr, const int32_t *ince_col,
@@ -1826,8 +1895,10 @@ static int spatial_forward_impl(const uds_network_t *net, const uds_spatial_para
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (S == 0) return UDS_OK;
 
-  if (h == uds::F128_H && d == uds::F128_D && fx == 128 && (fe == 128 || fe == 64) && !xb && !eb && !(flags & UDS_FLAG_EXACT_FP32) &&
-      net->slot[slot_index(128, (int)fe)].ok && net->slot[slot_index((int)fe, 128)].ok) {
+  // which kernels, on which tiles: decided in one place (fused_launches), which uds_network_fused_launches reports
+  fused_launch launches[2];
+  const int n_launch = (flags & UDS_FLAG_EXACT_FP32) ? 0 : fused_launches(net, fx, fe, h, d, launches);
+  if (n_launch && launches[0].kernel == UDS_KERNEL_FUSED_CS) {
     // d = 128: the column-split fused kernel (kernels_fused128.hpp); 64-wide link rows -> one launch per side
     UDS_REQUIRE(aligned16(p->xe_b) && aligned16(p->ex_b) && aligned16(p->gx_as) && aligned16(p->gx_an) && aligned16(p->gx_b) &&
                     aligned16(p->ge_as) && aligned16(p->ge_an) && aligned16(p->ge_b),
@@ -1850,46 +1921,34 @@ static int spatial_forward_impl(const uds_network_t *net, const uds_spatial_para
 #ifdef UDS_PHASE_TIMING
     a.dbg = reinterpret_cast<unsigned long long *>(ws + PACKED_WEIGHT_FLOATS);
 #endif
-    auto launch_side = [&](const uds_plan_slot &u, int side, auto FP_, auto FS_) {       // side < 0: both sides in one launch
-      a.hdr = side < 0 ? u.d_hdr : u.d_hdr_side[side];
+    auto launch_side = [&](const fused_launch &l) {       // l.side < 0: both sides in one launch
+      const uds_plan_slot &u = net->slot[l.slot];
+      a.hdr = l.side < 0 ? u.d_hdr : u.d_hdr_side[l.side];
       a.pool = u.d_pool;
-      a.n_tiles = side < 0 ? u.plan.n_tiles : u.plan.side[side].n_tiles;
+      a.n_tiles = l.n_tiles;
       a.p_cap = u.plan.p_cap;
       a.q_cap = u.plan.q_cap;
       a.meta_cap = u.plan.meta_cap;
-      a.side_mask = side < 0 ? 3 : (1 << side);
+      a.side_mask = l.side_mask;
       if ((rem_x || rem_e) && a.p_cap > 64) return hipErrorInvalidValue;      // one P1.5 unit per wave (kernels_fused128.hpp)
-      const int64_t chunk = pick_chunk(S, a.n_tiles);
+      const int64_t chunk = pick_chunk(S, l.n_tiles);
       a.chunk = (int)chunk;
-      const int grid = (int)(((S + chunk - 1) / chunk) * a.n_tiles);
-      return launch_fused128<decltype(FP_)::value, decltype(FS_)::value>(a, grid, u.lds_bytes, st);
+      const int grid = (int)(((S + chunk - 1) / chunk) * l.n_tiles);
+      if (l.fp == 128) return l.fs == 128 ? launch_fused128<128, 128>(a, grid, u.lds_bytes, st) : launch_fused128<128, 64>(a, grid, u.lds_bytes, st);
+      return launch_fused128<64, 128>(a, grid, u.lds_bytes, st);
     };
-    using I64 = std::integral_constant<int, 64>;
-    using I128 = std::integral_constant<int, 128>;
-    hipError_t he;
-    if (fe == 128) {
-      he = launch_side(net->slot[4], -1, I128{}, I128{});
-    } else {
-      he = launch_side(net->slot[5], 0, I128{}, I64{});                       // node tiles: 128-wide nodes fed by 64-wide links
-      if (he == hipSuccess) he = launch_side(net->slot[6], 1, I64{}, I128{});   // link tiles: 64-wide links fed by 128-wide nodes
-    }
+    hipError_t he = hipSuccess;
+    for (int i = 0; i < n_launch && he == hipSuccess; ++i) he = launch_side(launches[i]);
     if (he != hipSuccess) return fail(UDS_EHIP, "uds_spatial_layer_forward: fused d=128 launch -> %s", hipGetErrorString(he));
     return UDS_OK;
   }
   UDS_REQUIRE((!rem_x && !rem_e) || (h == uds::FUSED_H && d == uds::FUSED_D && fxa == 64 && fea == 64),
               "uds_spatial_layer_forward_rem: the remainder goes into the d = 128 fused kernel or the 64-wide d = 64 one (fx=%lld fe=%lld h=%lld d=%lld, plan %d)",
               (long long)fxa, (long long)fea, (long long)h, (long long)d, (int)(net->slot[4].ok));
-  // (rows of one snapshot are addressed with a 32-bit byte offset from a per-snapshot base: N, E < 2^31 / 384)
-  const bool shape_ok = h == uds::FUSED_H && d == uds::FUSED_D && (fx == 64 || fx == 96) && (fe == 64 || fe == 96) &&
-                        std::max(N, E) * 384 < ((int64_t)1 << 31);
-  // node tiles run the variant <fx, fe>, link tiles <fe, fx>: one launch when they coincide, else one per side
-  const uds_plan_slot &sl = net->slot[slot_index((int)fx, (int)fe)];
-  const uds_plan_slot &sl_link = net->slot[slot_index((int)fe, (int)fx)];
   if (flags & UDS_FLAG_REQUIRE_FUSED)
-    UDS_REQUIRE(sl.ok && sl_link.ok && shape_ok && !(flags & UDS_FLAG_EXACT_FP32),
-                "uds_spatial_layer_forward: fused kernel unavailable (plan %d, fx=%lld fe=%lld h=%lld d=%lld)", (int)sl.ok,
-                (long long)fx, (long long)fe, (long long)h, (long long)d);
-  if (sl.ok && sl_link.ok && shape_ok && !(flags & UDS_FLAG_EXACT_FP32)) {
+    UDS_REQUIRE(n_launch, "uds_spatial_layer_forward: fused kernel unavailable (plan %d, fx=%lld fe=%lld h=%lld d=%lld)",
+                (int)net->slot[slot_index((int)fx, (int)fe)].ok, (long long)fx, (long long)fe, (long long)h, (long long)d);
+  if (n_launch) {
     UDS_REQUIRE(aligned16(p->xe_b) && aligned16(p->ex_b) && aligned16(p->gx_as) && aligned16(p->gx_an) && aligned16(p->gx_b) &&
                     aligned16(p->ge_as) && aligned16(p->ge_an) && aligned16(p->ge_b),
                 "uds_spatial_layer_forward: bias / attention vectors must be 16-byte aligned");
@@ -1909,17 +1968,18 @@ static int spatial_forward_impl(const uds_network_t *net, const uds_spatial_para
     a.side[0] = uds::FusedSide{x, e, xb, eb, out_x, w_small_n, w_big_n, has32 ? wq + WS_BIG32_OFF : nullptr, has32 ? wq + WS_SMALL32_OFF : nullptr, p->xe_b, p->gx_as, p->gx_an, p->gx_b, p->ne_n_val, (int)N, (int)E, rem_x};
     a.side[1] = uds::FusedSide{e, x, eb, xb, out_e, w_small_e, w_big_e, has32 ? wq + WS_BIG32_OFF + WS_BIG32_LEN : nullptr, has32 ? wq + WS_SMALL32_OFF + WS_SMALL32_LEN : nullptr, p->ex_b, p->ge_as, p->ge_an, p->ge_b, p->ne_e_val, (int)E, (int)N, rem_e};
     int64_t lds_need = 0;
-    auto use_plan = [&](const uds_plan_slot &u, int side) {     // side < 0: both sides (merged tile list), else that side's tiles only
+    auto use_plan = [&](const fused_launch &l) {     // l.side < 0: both sides (merged tile list), else that side's tiles only
+      const uds_plan_slot &u = net->slot[l.slot];
+      const int side = l.side;
       a.hdr = side < 0 ? u.d_hdr : u.d_hdr_side[side];
       a.pool = u.d_pool;
-      a.n_tiles = side < 0 ? u.plan.n_tiles : u.plan.side[side].n_tiles;
+      a.n_tiles = l.n_tiles;
       a.p_cap = u.plan.p_cap;
       a.q_cap = u.plan.q_cap;
       a.meta_cap = u.blk_cap;      // LDS ints of the tile block (header + fixed-width index lists)
       a.blocks = side < 0 ? u.d_blocks : u.d_blocks_side[side];
       lds_need = u.lds_bytes;
     };
-    use_plan(sl, -1);
     a.S = (int)S;
     a.act = act;
     a.dbg = nullptr;
@@ -1934,29 +1994,19 @@ static int spatial_forward_impl(const uds_network_t *net, const uds_spatial_para
       a.chunk = (int)chunk;
       return (int)(((S + chunk - 1) / chunk) * a.n_tiles);
     };
-    if (fx == fe) {
-      a.side_mask = 3;
-      const int grid = set_chunk(a.n_tiles);
+    he = hipSuccess;
+    for (int i = 0; i < n_launch && he == hipSuccess; ++i) {      // one launch, or node tiles <fx, fe> then link tiles <fe, fx>
+      const fused_launch &l = launches[i];
+      use_plan(l);
+      a.side_mask = l.side_mask;
+      const int grid = set_chunk(l.n_tiles);
+      const bool ws = l.kernel == UDS_KERNEL_FUSED_WS;
       const int64_t ws_lds = uds::fused_ws_lds_bytes(a.p_cap, a.q_cap, a.meta_cap);
-      bool ws = fx == 64 && !xb && !eb && ws_plan_ok(sl);
-#ifdef UDS_KNOBS
-      if (std::getenv("UDS_NO_WS")) ws = false;      // experiment builds only: k_fused_tile<64, 64> in place of k_fused_ws
-#endif
       UDS_REQUIRE(ws || (!rem_x && !rem_e), "uds_spatial_layer_forward_rem: the wave-specialised d = 64 kernel cannot take this network's plan (p_cap %d, q_cap %d, %lld B of LDS)",
                   a.p_cap, a.q_cap, (long long)ws_lds);
       if (ws) he = launch_fused_ws(a, grid, ws_lds, st);
-      else he = (fx == 64) ? launch_fused<64, 64>(a, grid, lds_need, st) : launch_fused<96, 96>(a, grid, lds_need, st);
-    } else {   // node tiles: FP = fx, FS = fe; link tiles: FP = fe, FS = fx -> one launch per side
-      a.side_mask = 1;
-      use_plan(sl, 0);      // workgroups go round-robin to the XCDs: a grid of working tiles only keeps the XCDs level
-      int grid = set_chunk(a.n_tiles);
-      he = (fx == 64) ? launch_fused<64, 96>(a, grid, lds_need, st) : launch_fused<96, 64>(a, grid, lds_need, st);
-      if (he == hipSuccess) {
-        a.side_mask = 2;
-        use_plan(sl_link, 1);
-        grid = set_chunk(a.n_tiles);
-        he = (fe == 64) ? launch_fused<64, 96>(a, grid, lds_need, st) : launch_fused<96, 64>(a, grid, lds_need, st);
-      }
+      else if (l.fp == l.fs) he = (l.fp == 64) ? launch_fused<64, 64>(a, grid, lds_need, st) : launch_fused<96, 96>(a, grid, lds_need, st);
+      else he = (l.fp == 64) ? launch_fused<64, 96>(a, grid, lds_need, st) : launch_fused<96, 64>(a, grid, lds_need, st);
     }
     if (he != hipSuccess) return fail(UDS_EHIP, "uds_spatial_layer_forward: fused launch -> %s", hipGetErrorString(he));
     return UDS_OK;

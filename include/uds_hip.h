@@ -731,6 +731,26 @@ int uds_spatial_layer_forward_rem(const uds_network_t *net, const uds_spatial_pa
                                   int64_t d, int act, int flags, float *workspace, float *out_x, float *out_e,
                                   uds_stream_t stream);
 
+/* Which launches a fused spatial layer makes (host-only bookkeeping: neither entry touches a device).
+ *
+ * The snapshots of a launch are cut into chunks and one workgroup handles one (tile, chunk) pair: *chunk = the chunk
+ * length of a launch of S snapshots over working_tiles tiles (1 whenever S * working_tiles <= 256; the last chunk holds
+ * the S % chunk left-over snapshots).  S, working_tiles in [1, 2^31). */
+int uds_fused_chunk(int64_t S, int64_t working_tiles, int64_t *chunk);
+/* kernels of the fused spatial layer */
+enum {
+  UDS_KERNEL_FUSED_WS = 1,   /* k_fused_ws: the wave-specialised d = 64 kernel, 64-wide rows on both sides */
+  UDS_KERNEL_FUSED_TILE = 2, /* k_fused_tile<FP, FS>: d = 64, primary / secondary rows of FP / FS in {64, 96} floats */
+  UDS_KERNEL_FUSED_CS = 3    /* k_fused_cs<128, FP, FS>: the column-split d = 128 kernel, FP / FS in {64, 128} */
+};
+/* The launches uds_spatial_layer_forward (flags 0, single-tensor or split inputs alike) makes on this network for a layer
+ * with fx / fe-wide node / link rows, h = d / 2 and output width d, from the plans built so far (uds_network_prepare):
+ * info11 = {n, then for each of the n launches: kernel (UDS_KERNEL_*), FP, FS, side mask (1 = node tiles, 2 = link tiles,
+ * 3 = both), tiles of the launch}; n = 0 when the layer runs unfused, 1 when both sides share a variant, 2 (node tiles,
+ * then link tiles) when fx != fe.  Entries past the n-th launch are 0.  The chunk length of a launch over S snapshots is
+ * uds_fused_chunk(S, tiles).  The forward decides with the same code. */
+int uds_network_fused_launches(const uds_network_t *net, int64_t fx, int64_t fe, int64_t d, int32_t *info11);
+
 #ifdef __cplusplus
 }
 #endif

@@ -301,6 +301,8 @@ NULL_HANDLE = (
     ('uds_csr_sddmm', 'uds_csr_sddmm: NULL argument'),
     ('uds_network_prepare', 'uds_network_prepare: NULL network'),
     ('uds_network_plan_info', 'uds_network_plan_info: NULL argument'),
+    ('uds_network_fused_launches', 'uds_network_fused_launches: NULL argument'),
+    ('uds_fused_chunk', 'uds_fused_chunk: NULL argument'),
     ('uds_tile_plan_sizes', 'uds_tile_plan_sizes: NULL plan'),
     ('uds_tile_plan_copy', 'uds_tile_plan_copy: NULL argument'),
     ('uds_tile_plan_blocks', 'uds_tile_plan_blocks: NULL plan'),
