@@ -36,6 +36,7 @@ SYMBOLS = {
     'uds_csr_row_order': (_c_int, [_c_ptr, _c_ptr]),
     'uds_dense_act': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_i64, _c_int, _c_ptr, _c_ptr,
                                _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_dense_route': (_c_int, [_c_i64, _c_i64, _c_i64, _c_int, _c_i64, _c_i64, _c_int, _c_ptr]),
     'uds_csr_spmm': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_int, _c_ptr, _c_ptr]),
     'uds_conv1d_causal': (_c_int, [_c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr,
                                    _c_ptr]),
@@ -416,9 +417,23 @@ def tile_plan(graph, t_node=48, t_link=48, p_limit=0, q_limit=0, blocks=False):
     return hdr, pool, out
 
 
-def dense_act(xa, kernel, bias=None, act='linear', xb=None, attn=None):
+DENSE_KERNELS = {0: 'tiled', 1: 'embed'}      # kernel 0 / 1 of uds_dense_route: k_dense_act<CG> / k_embed_act<F>
+
+
+def dense_route(fa, f_out, rows, fb=0, taps=0, attn=False, aligned=True):
+    """uds_dense_route (host only, no device needed): what uds_dense_act (taps = 0) or uds_conv1d_causal (taps > 0, rows = B T R)
+    launches for a shape.  aligned: W and bias are 16-byte aligned.  dict(kernel = 'tiled' or 'embed', param = CG or F,
+    rows_per_wg (tiled, else 0), workgroups, stride = the embed kernel's grid stride in lanes (tiled: 0))."""
+    info = (ctypes.c_int32 * 5)()
+    _check(load().uds_dense_route(int(fa), int(fb), int(taps), int(bool(attn)), int(f_out), int(rows), int(bool(aligned)), info),
+           'uds_dense_route')
+    return dict(kernel=DENSE_KERNELS[int(info[0])], param=int(info[1]), rows_per_wg=int(info[2]), workgroups=int(info[3]),
+                stride=int(info[4]))
+
+
+def dense_act(xa, kernel, bias=None, act='linear', xb=None, attn=None, out=None, s_out=None):
     """act([xa | xb] @ kernel + bias) on the last axis.  attn=(a_self, a_nbr) also returns the
-    GAT attention scalars of the pre-activation rows."""
+    GAT attention scalars of the pre-activation rows.  out / s_out=(s_self, s_nbr): the caller's result tensors."""
     lib = load()
     fa = xa.shape[-1]
     fb = 0 if xb is None else xb.shape[-1]
@@ -428,11 +443,13 @@ def dense_act(xa, kernel, bias=None, act='linear', xb=None, attn=None):
         raise UdsError('kernel has %d input features, inputs give %d' % (kernel.shape[0], fa + fb))
     if xb is not None and xb.shape[:-1] != xa.shape[:-1]:
         raise UdsError('xa %r and xb %r disagree on leading dims' % (tuple(xa.shape), tuple(xb.shape)))
-    out = torch.empty(xa.shape[:-1] + (fo,), device=xa.device, dtype=torch.float32)
+    out = _out(out, xa.shape[:-1] + (fo,), xa, 'out')
     s_self = s_nbr = None
     if attn is not None:
-        s_self = torch.empty(xa.shape[:-1], device=xa.device, dtype=torch.float32)
-        s_nbr = torch.empty_like(s_self)
+        s_self = _out(s_out[0] if s_out else None, xa.shape[:-1], xa, 's_self')
+        s_nbr = _out(s_out[1] if s_out else None, xa.shape[:-1], xa, 's_nbr')
+    elif s_out is not None:
+        raise UdsError('dense_act: s_out is given without attn')
     if rows == 0:
         return _nothing_to_launch(xa, 'xa', (out, s_self, s_nbr) if attn is not None else out)
     _check(lib.uds_dense_act(_dev(xa, 'xa'), fa, _dev(xb, 'xb', True), fb, rows, _dev(kernel, 'kernel'),
@@ -443,14 +460,15 @@ def dense_act(xa, kernel, bias=None, act='linear', xb=None, attn=None):
     return (out, s_self, s_nbr) if attn is not None else out
 
 
-def conv1d_causal(x, kernel, bias=None, dilation=1, act='linear'):
-    """keras Conv1D(padding='causal', dilation_rate) along axis 1 of x (B,T,R,F), no transposes; kernel (taps,F,H)."""
+def conv1d_causal(x, kernel, bias=None, dilation=1, act='linear', out=None):
+    """keras Conv1D(padding='causal', dilation_rate) along axis 1 of x (B,T,R,F), no transposes; kernel (taps,F,H).
+    out: the caller's result tensor."""
     lib = load()
     if x.dim() != 4 or kernel.dim() != 3 or kernel.shape[1] != x.shape[-1]:
         raise UdsError('conv1d_causal: x %r / kernel %r' % (tuple(x.shape), tuple(kernel.shape)))
     B, T, R, F = x.shape
     taps, _, H = kernel.shape
-    out = torch.empty((B, T, R, H), device=x.device, dtype=torch.float32)
+    out = _out(out, (B, T, R, H), x, 'out')
     if out.numel() == 0:
         return _nothing_to_launch(x, 'x', out)
     _check(lib.uds_conv1d_causal(_dev(x, 'x'), B, T, R, F, _dev(kernel, 'kernel'), _dev(bias, 'bias', True), taps, dilation, H,
@@ -1088,13 +1106,13 @@ def conv_stack_forward(x, layers, act='linear', n_seg=0, out=None):
     return out
 
 
-def cumsum_act(x, res=None, act='linear'):
-    """act(cumsum over axis 1 of x (B,T,R,F) + res (B,1,R,F))."""
+def cumsum_act(x, res=None, act='linear', out=None):
+    """act(cumsum over axis 1 of x (B,T,R,F) + res (B,1,R,F)).  out: the caller's result tensor."""
     lib = load()
     B, T, R, F = x.shape
     if res is not None and tuple(res.shape) != (B, 1, R, F):
         raise UdsError('cumsum_act: res must be %r, got %r' % ((B, 1, R, F), tuple(res.shape)))
-    out = torch.empty_like(x)
+    out = _out(out, x.shape, x, 'out')
     if out.numel() == 0:
         return _nothing_to_launch(x, 'x', out)
     _check(lib.uds_cumsum_act(_dev(x, 'x'), _dev(res, 'res', True), B, T, R, F, ACT[act], _dev(out, 'out'), _stream()),
@@ -1316,10 +1334,10 @@ def csr_spmm(handle, val, x, bias=None, act='linear', out=None):
     return out
 
 
-def gat_forward(handle, xa, kernel, a_self, a_nbr, bias=None, act='relu', xb=None, return_workspace=False):
+def gat_forward(handle, xa, kernel, a_self, a_nbr, bias=None, act='relu', xb=None, return_workspace=False, out=None, workspace=None):
     """Single-head GATConv over a CSR pattern with self loops; xa:(S,n,fa) [| xb:(S,n,fb)] -> (S,n,d).
     return_workspace=True also returns (hx (S,n,d), s_self (S,n), s_nbr (S,n)) -- views of the workspace, for the
-    backward pass."""
+    backward pass.  out / workspace (uds_gat_workspace_floats(n, S, d) floats): the caller's tensors."""
     lib = load()
     if xa.dim() != 3 or xa.shape[1] != handle.n_rows:
         raise UdsError('x must be (S,%d,F), got %r' % (handle.n_rows, tuple(xa.shape)))
@@ -1328,10 +1346,10 @@ def gat_forward(handle, xa, kernel, a_self, a_nbr, bias=None, act='relu', xb=Non
     d = kernel.shape[-1]
     if kernel.numel() != (fa + fb) * d:
         raise UdsError('kernel %r does not match %d input features' % (tuple(kernel.shape), fa + fb))
-    out = torch.empty((S, n, d), device=xa.device, dtype=torch.float32)
+    out = _out(out, (S, n, d), xa, 'out')
     if out.numel() == 0:
         return _nothing_to_launch(xa, 'xa', out)
-    ws = torch.empty(lib.uds_gat_workspace_floats(n, S, d), device=xa.device, dtype=torch.float32)
+    ws = _out(workspace, (lib.uds_gat_workspace_floats(n, S, d),), xa, 'workspace')
     _check(lib.uds_gat_forward(handle.ptr, _dev(xa, 'xa'), fa, _dev(xb, 'xb', True), fb, S, _dev(kernel, 'kernel'),
                                _dev(a_self, 'a_self'), _dev(a_nbr, 'a_nbr'), _dev(bias, 'bias', True), d, ACT[act],
                                _dev(ws, 'workspace'), _dev(out, 'out'), _stream()), 'uds_gat_forward')

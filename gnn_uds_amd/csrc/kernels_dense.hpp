@@ -176,12 +176,56 @@ __global__ __launch_bounds__(256) void k_dense_act(DenseArgs a) {
   }
 }
 
+// Which kernel a dense / causal-conv launch runs and over which grid: the ONE place that decides.  launch_dense_act launches
+// what dense_route() returns and uds_dense_route reports it, so the two cannot drift.
+enum { DENSE_KERNEL_TILED = 0, DENSE_KERNEL_EMBED = 1 };
+struct DenseRoute {
+  int kernel;           // DENSE_KERNEL_*
+  int param;            // k_dense_act<CG>: CG; k_embed_act<F>: F
+  int rows_per_wg;      // tiled: rows one workgroup owns (0 for the embed kernel)
+  int64_t blocks;       // workgroups launched
+  int64_t stride;       // embed: the grid stride in lanes, 256 * blocks (0 for the tiled kernel)
+};
+
+constexpr int dense_tile_rows(int cg) { return ((256 / cg) < 32 ? (256 / cg) : 32) * 4; }      // RT * TM of k_dense_act<cg>
+
+// wb_aligned: W and bias (NULL counts) are 16-byte aligned.  k_embed_act loads both as float4, k_dense_act with scalar loads,
+// so a misaligned W or bias runs on the tiled kernel: the same ascending-k fmaf chain, the same bits.
+inline DenseRoute dense_route(int fa, int fb, int taps, bool attn, int fo, int64_t rows, bool wb_aligned) {
+  DenseRoute r{};
+  if (fb == 0 && taps == 0 && !attn && fa <= 8 && (fo & 3) == 0 && rows >= 64 && wb_aligned) {
+    const int f4 = fo / 4;
+    const int64_t total = rows * f4;
+    int64_t blocks = std::min<int64_t>((total + 255) / 256, 256 * 16);      // 16 workgroups of 4 waves per CU
+    // grid stride a multiple of f4 so a lane keeps its column chunk: 256 * blocks % f4 == 0 needs blocks % (f4 / gcd(256, f4)) == 0
+    int g = f4;
+    for (int x = 256; x % 2 == 0 && g % 2 == 0; x /= 2) g /= 2;
+    blocks = std::max<int64_t>(g, blocks / g * g);
+    r.kernel = DENSE_KERNEL_EMBED;
+    r.param = fa;
+    r.blocks = blocks;
+    r.stride = blocks * 256;
+    return r;
+  }
+  const int groups = (fo + 3) / 4;
+  int cg = 64;
+  for (int c = 1; c < 64; c *= 2)
+    if (groups <= c) {
+      cg = c;
+      break;
+    }
+  r.kernel = DENSE_KERNEL_TILED;
+  r.param = cg;
+  r.rows_per_wg = dense_tile_rows(cg);
+  r.blocks = (rows + r.rows_per_wg - 1) / r.rows_per_wg;
+  return r;
+}
+
 template <int CG>
-inline hipError_t launch_dense_cg(const DenseArgs &a, hipStream_t st) {
+inline hipError_t launch_dense_cg(const DenseArgs &a, const DenseRoute &r, hipStream_t st) {
   constexpr int RT = (256 / CG) < 32 ? (256 / CG) : 32;
-  constexpr int ROWS = RT * 4;
-  const int64_t blocks = (a.rows + ROWS - 1) / ROWS;
-  hipLaunchKernelGGL(k_dense_act<CG>, dim3((unsigned)blocks), dim3(RT * CG), 0, st, a);
+  static_assert(RT * 4 == dense_tile_rows(CG), "dense_route reports the rows of k_dense_act<CG>");
+  hipLaunchKernelGGL(k_dense_act<CG>, dim3((unsigned)r.blocks), dim3(RT * CG), 0, st, a);
   return hipGetLastError();
 }
 
@@ -225,39 +269,35 @@ __global__ __launch_bounds__(256) void k_embed_act(DenseArgs a) {
 }
 
 template <int F>
-inline hipError_t launch_embed_f(const DenseArgs &a, hipStream_t st) {
-  const int f4 = a.fo / 4;
-  const int64_t total = a.rows * f4;
-  int64_t blocks = std::min<int64_t>((total + 255) / 256, 256 * 16);      // 16 workgroups of 4 waves per CU
-  // grid stride a multiple of f4 so a lane keeps its column chunk: 256 * blocks % f4 == 0 needs blocks % (f4 / gcd(256, f4)) == 0
-  int g = f4;
-  for (int x = 256; x % 2 == 0 && g % 2 == 0; x /= 2) g /= 2;
-  blocks = std::max<int64_t>(g, blocks / g * g);
-  hipLaunchKernelGGL(k_embed_act<F>, dim3((unsigned)blocks), dim3(256), 0, st, a);
+inline hipError_t launch_embed_f(const DenseArgs &a, const DenseRoute &r, hipStream_t st) {
+  hipLaunchKernelGGL(k_embed_act<F>, dim3((unsigned)r.blocks), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 
 inline hipError_t launch_dense_act(const DenseArgs &a, hipStream_t st) {
-  if (a.fb == 0 && a.taps == 0 && a.a_self == nullptr && a.fa <= 8 && (a.fo & 3) == 0 && a.rows >= 64) {
-    switch (a.fa) {
-      case 1: return launch_embed_f<1>(a, st);
-      case 2: return launch_embed_f<2>(a, st);
-      case 3: return launch_embed_f<3>(a, st);
-      case 4: return launch_embed_f<4>(a, st);
-      case 5: return launch_embed_f<5>(a, st);
-      case 6: return launch_embed_f<6>(a, st);
-      case 7: return launch_embed_f<7>(a, st);
-      default: return launch_embed_f<8>(a, st);
+  const bool wb_aligned = ((reinterpret_cast<uintptr_t>(a.W) | reinterpret_cast<uintptr_t>(a.bias)) & 15u) == 0;
+  const DenseRoute r = dense_route(a.fa, a.fb, a.taps, a.a_self != nullptr, a.fo, a.rows, wb_aligned);
+  if (r.kernel == DENSE_KERNEL_EMBED) {
+    switch (r.param) {
+      case 1: return launch_embed_f<1>(a, r, st);
+      case 2: return launch_embed_f<2>(a, r, st);
+      case 3: return launch_embed_f<3>(a, r, st);
+      case 4: return launch_embed_f<4>(a, r, st);
+      case 5: return launch_embed_f<5>(a, r, st);
+      case 6: return launch_embed_f<6>(a, r, st);
+      case 7: return launch_embed_f<7>(a, r, st);
+      default: return launch_embed_f<8>(a, r, st);
     }
   }
-  const int groups = (a.fo + 3) / 4;
-  if (groups <= 1) return launch_dense_cg<1>(a, st);
-  if (groups <= 2) return launch_dense_cg<2>(a, st);
-  if (groups <= 4) return launch_dense_cg<4>(a, st);
-  if (groups <= 8) return launch_dense_cg<8>(a, st);
-  if (groups <= 16) return launch_dense_cg<16>(a, st);
-  if (groups <= 32) return launch_dense_cg<32>(a, st);
-  return launch_dense_cg<64>(a, st);
+  switch (r.param) {
+    case 1: return launch_dense_cg<1>(a, r, st);
+    case 2: return launch_dense_cg<2>(a, r, st);
+    case 4: return launch_dense_cg<4>(a, r, st);
+    case 8: return launch_dense_cg<8>(a, r, st);
+    case 16: return launch_dense_cg<16>(a, r, st);
+    case 32: return launch_dense_cg<32>(a, r, st);
+    default: return launch_dense_cg<64>(a, r, st);
+  }
 }
 
 // keras GRU / LSTM(units, return_sequences=True) along the time axis (emulator.py:158-161: the `recurrent` alternatives to

@@ -403,6 +403,26 @@ int uds_conv1d_causal(const float *x, int64_t B, int64_t T, int64_t R, int64_t F
   return launched("uds_conv1d_causal", uds::launch_dense_act(a, static_cast<hipStream_t>(stream)));
 }
 
+// Host only: what launch_dense_act would launch for this shape (the same uds::dense_route), under the size checks of the two entries
+int uds_dense_route(int64_t fa, int64_t fb, int64_t taps, int attn, int64_t f_out, int64_t rows, int wb_aligned, int32_t *info5) {
+  UDS_REQUIRE(info5 != nullptr, "uds_dense_route: info5 is NULL");
+  UDS_REQUIRE(fa > 0 && fb >= 0 && rows >= 0 && rows <= ((int64_t)1 << 40) && f_out > 0 && f_out <= 256 && fa + fb <= 4096,
+              "uds_dense_route: fa=%lld fb=%lld rows=%lld (max 2^40) f_out=%lld (max 256) f_in=%lld (max 4096)", (long long)fa, (long long)fb,
+              (long long)rows, (long long)f_out, (long long)(fa + fb));
+  UDS_REQUIRE(taps >= 0 && taps <= 16 && (taps == 0 || (fb == 0 && !attn && taps * fa <= 4096)),
+              "uds_dense_route: taps=%lld (0 .. 16; a convolution has no xb and no attention scalars, taps * fa = %lld <= 4096)",
+              (long long)taps, (long long)(taps * fa));
+  const uds::DenseRoute r = uds::dense_route((int)fa, (int)fb, (int)taps, attn != 0, (int)f_out, rows, wb_aligned != 0);
+  UDS_REQUIRE(r.blocks <= INT32_MAX, "uds_dense_route: rows=%lld need %lld workgroups, more than a launch grid holds", (long long)rows,
+              (long long)r.blocks);
+  info5[0] = r.kernel;
+  info5[1] = r.param;
+  info5[2] = r.rows_per_wg;
+  info5[3] = (int32_t)r.blocks;
+  info5[4] = (int32_t)r.stride;
+  return UDS_OK;
+}
+
 int uds_recurrent_fused(const float *x, int64_t F, const void *packed, const float *b_in, const float *b_rec, int64_t B, int64_t T, int64_t R,
                         int kind, float *out, uds_stream_t stream) {
   UDS_REQUIRE(x && packed && out && (F == 0 || b_in), "uds_recurrent_fused: NULL argument");

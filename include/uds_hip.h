@@ -74,11 +74,29 @@ int uds_csr_row_order(const uds_csr_t *csr, int32_t *out_host);
 /* out[r,:] = act([xa[r,:] | xb[r,:]] @ W + bias), r < rows.   W is (fa+fb, f_out) row-major.
  * xb may be NULL with fb = 0; bias may be NULL.  When a_self/a_nbr (f_out each) are given,
  * s_self[r] = <pre-activation row, a_self> and s_nbr[r] likewise are written too (the GAT
- * attention scalars); they must be NULL together. */
+ * attention scalars); they must be NULL together.
+ * Alignment: `out` must be 16-byte aligned when f_out % 4 == 0 (float4 stores), else UDS_EINVAL.  No other operand has to
+ * be.  The narrow-input kernel (below) loads W and bias as float4, so it runs only when both are 16-byte aligned; a
+ * misaligned W or bias runs on the tiled kernel, which reads them with scalar loads and gives the same bits. */
 int uds_dense_act(const float *xa, int64_t fa, const float *xb, int64_t fb, int64_t rows,
                   const float *W, const float *bias, int64_t f_out, int act, const float *a_self,
                   const float *a_nbr, float *out, float *s_self, float *s_nbr,
                   uds_stream_t stream);
+
+/* Which kernel uds_dense_act (taps = 0) or uds_conv1d_causal (taps > 0: fa = F, fb = 0, f_out = H, rows = B * T * R) runs
+ * for a shape, and over which grid.  Host only (works without a GPU); the launch decides with the same code.
+ *   attn        non-zero when the attention scalars are asked for
+ *   wb_aligned  non-zero when W and bias (NULL counts as aligned) are 16-byte aligned
+ *   info5 = {kernel, parameter, rows per workgroup, workgroups launched, grid stride in lanes}
+ *     kernel 0  the tiled kernel k_dense_act<CG>: parameter = CG, the power of two >= ceil(f_out / 4) in 1 .. 64; a workgroup
+ *               owns 128 rows (CG <= 8), 64 (16), 32 (32) or 16 (64); the stride is 0
+ *     kernel 1  the narrow-input stream k_embed_act<F>: parameter = F = fa.  Taken when fb = 0, taps = 0, no attention
+ *               scalars, fa <= 8, f_out % 4 == 0, rows >= 64 and wb_aligned.  One lane per float4 of the output, at most
+ *               4096 workgroups of 256 lanes, their number a multiple of (f_out / 4) / gcd(256, f_out / 4) so that the
+ *               stride, 256 * workgroups, is a multiple of f_out / 4; rows per workgroup is 0
+ * UDS_EINVAL for the sizes the two entries refuse, and for a grid of more than 2^31 - 1 workgroups. */
+int uds_dense_route(int64_t fa, int64_t fb, int64_t taps, int attn, int64_t f_out, int64_t rows, int wb_aligned,
+                    int32_t *info5);
 
 /* out[s,r,:] = act(sum_{p in row r} val[p] * x[s, col[p], :] + bias);  x is (S, n_cols, F),
  * out is (S, n_rows, F).  val (nnz) may be NULL (all ones); bias (F) may be NULL.  F % 4 == 0. */

@@ -27,6 +27,7 @@ GOOD = {
     'uds_dense_act': ('xa fa xb fb rows W bias f_out act a_self a_nbr out s_self s_nbr',
                       dict(xa=P, fa=8, xb=None, fb=0, rows=3, W=P, bias=None, f_out=8, act=0, a_self=None, a_nbr=None, out=P, s_self=None,
                            s_nbr=None)),
+    'uds_dense_route': ('fa fb taps attn f_out rows wb_aligned info5', dict(fa=8, fb=0, taps=0, attn=0, f_out=8, rows=3, wb_aligned=1, info5=P)),
     'uds_conv1d_causal': ('x B T R F kernel bias taps dil H act out', dict(x=P, B=2, T=3, R=5, F=8, kernel=P, bias=None, taps=2, dil=1, H=16, act=0, out=P)),
     'uds_recurrent_fused': ('x F packed b_in b_rec B T R kind out', dict(x=P, F=64, packed=P, b_in=P, b_rec=P, B=2, T=3, R=5, kind=0, out=P)),
     'uds_recurrent_forward': ('xp U rb B T R H kind out', dict(xp=P, U=P, rb=None, B=2, T=3, R=5, H=32, kind=0, out=P)),
@@ -72,6 +73,8 @@ GOOD = {
                                 dict(buf=P, S=2, F=8, off_x=P, off_e=P, P=4, tgt_x=P, tx=1, tgt_e=P, te=3, ptr=P, src=P, n_src=6, x=P, n_x=9, e=P,
                                      n_e=7)),
 }
+
+NO_STREAM = {'uds_dense_route'}      # host-only entries of the table: their argument list does not end in a stream
 
 BIG = 1 << 31
 
@@ -261,6 +264,20 @@ CASES = (
        ('uds_dense_act', dict(f_out=257), 'uds_dense_act: rows=3 f_out=257 (max 256) f_in=8'),
        ('uds_dense_act', dict(act=9), 'uds_dense_act: unknown activation 9'),
        ('uds_dense_act', dict(a_self=P), 'uds_dense_act: a_self/a_nbr/s_self/s_nbr must be given together'),
+       ('uds_dense_route', dict(info5=None), 'uds_dense_route: info5 is NULL'),
+       ('uds_dense_route', dict(fa=0), 'uds_dense_route: fa=0 fb=0 rows=3 (max 2^40) f_out=8 (max 256) f_in=0 (max 4096)'),
+       ('uds_dense_route', dict(fb=-1), 'uds_dense_route: fa=8 fb=-1 rows=3'),
+       ('uds_dense_route', dict(rows=-1), 'uds_dense_route: fa=8 fb=0 rows=-1'),
+       ('uds_dense_route', dict(rows=(1 << 40) + 1), 'uds_dense_route: fa=8 fb=0 rows=1099511627777 (max 2^40)'),
+       ('uds_dense_route', dict(f_out=257), 'uds_dense_route: fa=8 fb=0 rows=3 (max 2^40) f_out=257 (max 256)'),
+       ('uds_dense_route', dict(f_out=0), 'uds_dense_route: fa=8 fb=0 rows=3 (max 2^40) f_out=0 (max 256)'),
+       ('uds_dense_route', dict(fa=4000, fb=97), 'uds_dense_route: fa=4000 fb=97 rows=3 (max 2^40) f_out=8 (max 256) f_in=4097 (max 4096)'),
+       ('uds_dense_route', dict(taps=17), 'uds_dense_route: taps=17 (0 .. 16;'),
+       ('uds_dense_route', dict(taps=-1), 'uds_dense_route: taps=-1 (0 .. 16;'),
+       ('uds_dense_route', dict(taps=2, fb=4), 'uds_dense_route: taps=2 (0 .. 16; a convolution has no xb and no attention scalars'),
+       ('uds_dense_route', dict(taps=2, attn=1), 'uds_dense_route: taps=2 (0 .. 16; a convolution has no xb and no attention scalars'),
+       ('uds_dense_route', dict(taps=16, fa=257), 'taps * fa = 4112 <= 4096)'),
+       ('uds_dense_route', dict(rows=1 << 40, f_out=256, fa=9), 'uds_dense_route: rows=1099511627776 need 68719476736 workgroups, more than a launch grid holds'),
        ('uds_conv1d_causal', dict(kernel=None), 'uds_conv1d_causal: NULL x/kernel/out'),
        ('uds_conv1d_causal', dict(taps=17), 'uds_conv1d_causal: bad sizes B=2 T=3 R=5 F=8 taps=17 dil=1 H=16'),
        ('uds_conv1d_causal', dict(act=9), 'uds_conv1d_causal: unknown activation 9'),
@@ -314,12 +331,12 @@ NULL_HANDLE = (
 
 
 def call_args(entry, changes):
-    """The ABI-order argument list of `entry`: GOOD with `changes` applied, and a NULL stream."""
+    """The ABI-order argument list of `entry`: GOOD with `changes` applied, and a NULL stream (none for the NO_STREAM entries)."""
     names, good = GOOD[entry]
     names = names.split()
     assert set(names) == set(good) and set(changes) <= set(good), entry
     args = dict(good, **changes)
-    return [args[n] for n in names] + [None]
+    return [args[n] for n in names] + ([] if entry in NO_STREAM else [None])
 
 
 def null_args(entry):
