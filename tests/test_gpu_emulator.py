@@ -142,6 +142,38 @@ def test_network_forward(dev, networks, precision, tol):
     close(y, ry, tol); close(ey, rey, tol)
 
 
+_RELU_PATHS = {}      # embed_size -> last_path of every spatial layer of the relu model of that shape
+
+
+def _spatial_paths(emul):
+    return [ly.last_path for ly in list(emul.block1.layers) + list(emul.block2.layers)]
+
+
+@pytest.mark.parametrize('embed_size', [64, 128])
+@pytest.mark.parametrize('activation', ['linear', 'tanh', 'sigmoid', 'hard_sigmoid'])
+def test_network_forward_activations(dev, networks, activation, embed_size):
+    """args.activation other than relu through the whole network (the embeddings, every spatial layer, the temporal stack, the
+    resnet prefix sum and the flood chain take it): the forward against the oracle, and every spatial layer the relu model of the
+    same shape runs fused still runs fused (the run-time-activation instantiations of the fused kernels).  Measured on an MI355X:
+    0.45-0.59 of the bound at embed_size 64, 0.31-0.42 at 128."""
+    over = dict(embed_size=embed_size, hidden_dim=64)
+    f = lambda t: t.float().to(dev)
+    if embed_size not in _RELU_PATHS:
+        args, _, emul, _ = _setup(networks, 'astlingen', dev, **over)
+        X, Bd, Ex, a = _inputs(args, 2)
+        emul(f(X), f(Bd), f(Ex), emul.get_edge_action(f(a)))
+        _RELU_PATHS[embed_size] = _spatial_paths(emul)
+        assert 'fused' in _RELU_PATHS[embed_size]
+    args, params, emul, _ = _setup(networks, 'astlingen', dev, activation=activation, **over)
+    assert emul.activation == activation
+    X, Bd, Ex, a = _inputs(args, 2)
+    ry, rey = OE.forward(args, params, X, Bd, Ex, OE.get_edge_action(OE.config(args), a))
+    y, ey = emul(f(X), f(Bd), f(Ex), emul.get_edge_action(f(a)))
+    close(y, ry, TOL_FWD['bf16x3']); close(ey, rey, TOL_FWD['bf16x3'])
+    for got, relu in zip(_spatial_paths(emul), _RELU_PATHS[embed_size]):
+        assert got == 'fused' or relu != 'fused', (_spatial_paths(emul), _RELU_PATHS[embed_size])
+
+
 def test_network_forward_gcn_and_plain_variants(dev, networks):
     """conv = GCN (emulator.py:131-134), no actions / flood / resnet / edge fusion, seq_in > seq_out."""
     args, params, emul, _ = _setup(networks, 'astlingen', dev, conv='GCN', act=False, if_flood=0, resnet=False, edge_fusion=False,

@@ -267,7 +267,9 @@ def test_recurrent_backward_matches_autograd_of_the_oracle(dev, kind):
                                        ('hague', dict(act=False, if_flood=0, edge_fusion=False, resnet=False, n_sp_layer=1)),
                                        ('astlingen', dict(roll=2, seq_in=4, seq_out=2, n_sp_layer=1)),
                                        ('astlingen', dict(conv='GCN', act=False, if_flood=0, resnet=False, n_sp_layer=1)),
-                                       ('astlingen', dict(conv='False', seq_in=5, seq_out=5, n_sp_layer=2))])      # the non-graph baseline
+                                       ('astlingen', dict(conv='False', seq_in=5, seq_out=5, n_sp_layer=2)),      # the non-graph baseline
+                                       ('astlingen', dict(activation='tanh', n_sp_layer=1)),      # args.activation other than relu
+                                       ('astlingen', dict(activation='sigmoid', n_sp_layer=1, n_tp_layer=1))])
 def test_emulator_gradients(dev, networks, name, over):
     args, norms, params, emul, cpu_in, dev_in = _problem(networks, name, dev, **over)
     x, a, b, y, ex, ey = cpu_in
