@@ -107,6 +107,9 @@ SYMBOLS = {
     'uds_gat_aggregate_ex': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr]),
     'uds_gat_backward_ex': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
                                      _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_gat_backward_act_workspace_floats': (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    'uds_gat_backward_act': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr,
+                                      _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_ptr]),
     'uds_gat_aggregate_heads': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _c_ptr,
                                          _c_ptr, _c_ptr]),
     'uds_gat_backward_heads': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64,
@@ -1453,6 +1456,54 @@ def gat_backward_ex(handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a
     _check_entry_operand('gat_backward_ex: coef', coef, S, handle)
     return _gat_backward('uds_gat_backward_ex', handle, handle_t, perm_t, grad, hx, s_self, s_nbr, a_self, a_nbr,
                          [(edge_mask, 'edge_mask', True), (coef, 'coef', True)], out, workspace)
+
+
+def gat_backward_act_workspace_floats(S, n, nnz, d):
+    """Floats of workspace gat_backward_act needs: alpha, de, g and the partials of db / da (host-only, no device)."""
+    return load().uds_gat_backward_act_workspace_floats(S, n, nnz, d)
+
+
+def gat_backward_act(handle, handle_t, perm_t, out, gout, act, hx, s_self, s_nbr, a_self, a_nbr, edge_mask=None, coef=None, want_db=True,
+                     want_da=True, outputs=None, workspace=None):
+    """The reverse mode of a single-head GAT layer after its projection as one operator (uds_gat_backward_act): out (S,n,d) is
+    the layer's output, gout = dL/dout, act its activation.  Returns (d_hx, ds_self, ds_nbr, db, da): the first three bitwise
+    those of gat_backward[_ex] on act_grad(out, gout, act), db (d,) the bias gradient and da (2,d) the gradients of the
+    attention kernels (a_self, a_nbr), each None when not wanted.  outputs: the caller's (d_hx, ds_self, ds_nbr, db, da);
+    workspace: the caller's flat tensor of gat_backward_act_workspace_floats(S, n, nnz, d) floats or more."""
+    if not isinstance(out, torch.Tensor) or not isinstance(gout, torch.Tensor) or out.dim() != 3 or tuple(gout.shape) != tuple(out.shape):
+        raise UdsError('gat_backward_act: out and gout must be (S,n,d) tensors of one shape')
+    if act not in ACT:
+        raise UdsError('gat_backward_act: unknown activation %r' % (act,))
+    S, n, d = out.shape
+    if n != handle.n_rows or tuple(hx.shape) != (S, n, d) or tuple(s_self.shape) != (S, n) or tuple(s_nbr.shape) != (S, n):
+        raise UdsError('gat_backward_act: out %r, hx %r, s_self %r, s_nbr %r do not match a %d-row pattern' %
+                       (tuple(out.shape), tuple(hx.shape), tuple(s_self.shape), tuple(s_nbr.shape), handle.n_rows))
+    if a_self.numel() != d or a_nbr.numel() != d:
+        raise UdsError('gat_backward_act: a_self %r / a_nbr %r, expected %d values' % (tuple(a_self.shape), tuple(a_nbr.shape), d))
+    _check_entry_operand('gat_backward_act: edge_mask', edge_mask, S, handle)
+    _check_entry_operand('gat_backward_act: coef', coef, S, handle)
+    o = outputs if outputs is not None else (None,) * 5
+    d_hx, ds_self, ds_nbr = _gat_backward_outputs(gout, o[:3])
+    db = _out(o[3], (d,), gout, 'db') if want_db else None
+    da = _out(o[4], (2, d), gout, 'da') if want_da else None
+    need = gat_backward_act_workspace_floats(S, n, handle.nnz, d)
+    if workspace is None:
+        workspace = torch.empty(max(need, 4), device=gout.device, dtype=torch.float32)
+    elif not isinstance(workspace, torch.Tensor) or workspace.dim() != 1 or workspace.numel() < need:
+        raise UdsError('gat_backward_act: workspace must be a flat tensor of at least %d floats' % need)
+    if gout.numel() == 0:
+        _dev(gout, 'gout')
+        for t in (db, da):
+            if t is not None:
+                t.zero_()
+        return d_hx, ds_self, ds_nbr, db, da
+    _check(load().uds_gat_backward_act(handle.ptr, handle_t.ptr, _dev_i32(perm_t, 'perm_t'), _dev(out, 'out'), _dev(gout, 'gout'), ACT[act],
+                                       _dev(hx, 'hx'), _dev(s_self, 's_self'), _dev(s_nbr, 's_nbr'), _dev(a_self, 'a_self'),
+                                       _dev(a_nbr, 'a_nbr'), _dev(edge_mask, 'edge_mask', True), _dev(coef, 'coef', True), S, d,
+                                       _dev(d_hx, 'd_hx'), _dev(ds_self, 'ds_self'), _dev(ds_nbr, 'ds_nbr'), _dev(db, 'db', True),
+                                       _dev(da, 'da', True), _dev(workspace, 'workspace'), workspace.numel(), _stream()),
+           'uds_gat_backward_act')
+    return d_hx, ds_self, ds_nbr, db, da
 
 
 def _check_heads_operands(name, handle, hx, s_self, s_nbr, edge_mask, coef):

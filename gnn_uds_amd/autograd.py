@@ -86,6 +86,9 @@ def rows_matmul(x, w, precision='bf16x3'):
 WIDE_WGRAD = True
 # calls of weight_grad per route since the dict was last reset by hand (tests, tools/wgrad_wide_time.py)
 ROUTE_COUNTS = {'wgrad': 0, 'wgrad_wide': 0, 'library': 0}
+# GatFn.backward calls per path since the dict was last reset by hand: 'fused' = one uds_gat_backward_act call (fused_bwd),
+# 'chain' = act_grad, uds_gat_backward[_ex], the bias sum and the attention-kernel weight_grad as separate steps
+GAT_BWD_COUNTS = {'fused': 0, 'chain': 0}
 
 
 def weight_grad_route(F, H, want_bias, precision):
@@ -302,10 +305,12 @@ class SpmmFn(torch.autograd.Function):
 
 class GatFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, xa, xb, kernel, a_self, a_nbr, bias, act, handle, precision, coef=None, edge_mask=None):
+    def forward(ctx, xa, xb, kernel, a_self, a_nbr, bias, act, handle, precision, coef=None, edge_mask=None, fused_bwd=False):
         """coef (S, nnz) or None: multiplier of the normalised attention coefficients (Spektral's attention dropout).
         edge_mask (S, nnz) or None: per-snapshot edge mask of a `use_adj` layer (entry p of snapshot s takes part iff
-        edge_mask[s, p] != 0 or p is the diagonal); forward and backward then run on uds_gat_aggregate_ex / _backward_ex."""
+        edge_mask[s, p] != 0 or p is the diagonal); forward and backward then run on uds_gat_aggregate_ex / _backward_ex.
+        fused_bwd: backward takes activation, attention / aggregation, bias and attention-kernel gradients from ONE
+        uds_gat_backward_act call instead of four steps (the forward pass is the same)."""
         xa = xa.contiguous()
         xb = None if xb is None else xb.contiguous()
         fin, d = xa.shape[-1] + (0 if xb is None else xb.shape[-1]), kernel.shape[-1]
@@ -333,11 +338,42 @@ class GatFn(torch.autograd.Function):
                 out = _lib.gat_aggregate(handle, hx, s_self, s_nbr, bias, act, coef=coef)
         ctx.save_for_backward(xa, xb, kernel, a_self, a_nbr, out, hx, s_self, s_nbr)
         ctx.act, ctx.handle, ctx.precision, ctx.has_bias, ctx.coef = act, handle, precision, bias is not None, coef
-        ctx.edge_mask = edge_mask
+        ctx.edge_mask, ctx.fused_bwd = edge_mask, bool(fused_bwd)
         return out
 
     @staticmethod
+    def _backward_fused(ctx, gout):
+        """backward with fused_bwd: d_hx, the attention-kernel gradients and the bias gradient from uds_gat_backward_act; the
+        input and kernel gradients from d_hx as in backward."""
+        xa, xb, kernel, a_self, a_nbr, out, hx, s_self, s_nbr = ctx.saved_tensors
+        d = out.shape[-1]
+        GAT_BWD_COUNTS['fused'] += 1
+        ht, perm = ctx.handle.transposed(gout.device)
+        d_hx, _, _, db, da = _lib.gat_backward_act(
+            ctx.handle, ht, perm, out, gout.contiguous(), ctx.act, hx, s_self, s_nbr, a_self.reshape(-1).contiguous(),
+            a_nbr.reshape(-1).contiguous(), edge_mask=ctx.edge_mask, coef=ctx.coef, want_db=ctx.has_bias and ctx.needs_input_grad[5],
+            want_da=ctx.needs_input_grad[3] or ctx.needs_input_grad[4])
+        fa = xa.shape[-1]
+        w2 = kernel.reshape(-1, d)
+        dxa = dxb = dk = das = dan = None
+        if ctx.needs_input_grad[0]:
+            dxa = rows_matmul(d_hx, w2[:fa].t(), ctx.precision)
+        if xb is not None and ctx.needs_input_grad[1]:
+            dxb = rows_matmul(d_hx, w2[fa:].t(), ctx.precision)
+        if ctx.needs_input_grad[2]:
+            dk = weight_grad(xa, d_hx, ctx.precision, False)[0]
+            if xb is not None:
+                dk = torch.cat([dk, weight_grad(xb, d_hx, ctx.precision, False)[0]], dim=0)
+            dk = dk.reshape(kernel.shape)
+        if da is not None:
+            das, dan = da[0].reshape(a_self.shape), da[1].reshape(a_nbr.shape)
+        return dxa, dxb, dk, das, dan, db, None, None, None, None, None, None
+
+    @staticmethod
     def backward(ctx, gout):
+        if ctx.fused_bwd:
+            return GatFn._backward_fused(ctx, gout)
+        GAT_BWD_COUNTS['chain'] += 1
         xa, xb, kernel, a_self, a_nbr, out, hx, s_self, s_nbr = ctx.saved_tensors
         S, n, d = out.shape
         g = act_grad(out, gout.contiguous(), ctx.act).contiguous()
@@ -367,7 +403,7 @@ class GatFn(torch.autograd.Function):
             das, dan = da[0].reshape(a_self.shape), da[1].reshape(a_nbr.shape)
         if ctx.has_bias and ctx.needs_input_grad[5]:
             db = g.reshape(-1, d).sum(0)
-        return dxa, dxb, dk, das, dan, db, None, None, None, None, None
+        return dxa, dxb, dk, das, dan, db, None, None, None, None, None, None
 
 
 def heads_score_matrix(a_self, a_nbr):

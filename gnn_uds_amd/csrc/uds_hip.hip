@@ -1465,6 +1465,47 @@ int uds_gat_backward_ex(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *
                       d_hx, ds_self, ds_nbr, stream);
 }
 
+// workspace of uds_gat_backward_act: alpha | de (S * nnz each, rounded up to 4) | g (S * n * d) | the partials
+static int64_t gat_act_parts(int64_t S, int64_t n) { return S * n < uds::GAT_ACT_WG_MAX ? S * n : uds::GAT_ACT_WG_MAX; }
+
+int64_t uds_gat_backward_act_workspace_floats(int64_t S, int64_t n, int64_t nnz, int64_t d) {
+  if (S <= 0 || n <= 0 || nnz < 0 || d <= 0) return 0;
+  return 2 * align4(S * nnz) + S * n * d + 3 * d * gat_act_parts(S, n);
+}
+
+int uds_gat_backward_act(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *perm_t, const float *out, const float *gout, int act,
+                         const float *hx, const float *s_self, const float *s_nbr, const float *a_self, const float *a_nbr,
+                         const float *edge_mask, const float *coef, int64_t S, int64_t d, float *d_hx, float *ds_self, float *ds_nbr,
+                         float *db, float *da, float *workspace, int64_t workspace_floats, uds_stream_t stream) {
+  const char *what = "uds_gat_backward_act";
+  const bool ptrs = perm_t && out && gout && hx && s_self && s_nbr && a_self && a_nbr && d_hx && ds_self && ds_nbr && workspace;
+  if (int rc = gat_backward_check(what, ptrs, g, gt, false, 1, d, S, gout, hx, d_hx, a_self, a_nbr)) return rc;
+  UDS_REQUIRE(act >= UDS_ACT_LINEAR && act <= UDS_ACT_HARD_SIGMOID, "%s: unknown activation %d", what, act);
+  UDS_REQUIRE(aligned16(out) && aligned16(workspace), "%s: out/workspace must be 16-byte aligned", what);
+  const int64_t n = g->n_rows, need = uds_gat_backward_act_workspace_floats(S, n, g->nnz, d);
+  UDS_REQUIRE(workspace_floats >= need, "%s: workspace of %lld floats, %lld needed (uds_gat_backward_act_workspace_floats)", what,
+              (long long)workspace_floats, (long long)need);
+  if (S == 0 || n == 0) {       // nothing to walk: the parameter gradients are sums over no rows
+    hipStream_t st0 = static_cast<hipStream_t>(stream);
+    hipError_t e0 = db ? hipMemsetAsync(db, 0, sizeof(float) * d, st0) : hipSuccess;
+    if (e0 == hipSuccess && da) e0 = hipMemsetAsync(da, 0, sizeof(float) * 2 * d, st0);
+    if (e0 != hipSuccess) return fail(UDS_EHIP, "%s: memset -> %s", what, hipGetErrorString(e0));
+    return UDS_OK;
+  }
+  const int d4 = (int)(d / 4);
+  float *alpha_ws = workspace, *de_ws = alpha_ws + align4(S * g->nnz), *g_ws = de_ws + align4(S * g->nnz), *parts = g_ws + S * n * d;
+  const bool linear = act == UDS_ACT_LINEAR;          // g = gout: nothing to store, the column pass gathers gout
+  uds::GatBwdRowsActArgs ra;
+  static_cast<uds::GatBwdRowsArgs &>(ra) = uds::GatBwdRowsArgs{g->d_rowptr, g->d_col, nullptr, hx, s_self, s_nbr, alpha_ws, de_ws, ds_self,
+                                                               (int)n, d4, (int)S, uds::lanes_per_item(d4), g->nnz, coef, edge_mask};
+  ra.out = out, ra.gout = gout, ra.gw = linear ? nullptr : g_ws, ra.bpart = nullptr, ra.act = act;
+  uds::GatBwdColsActArgs ca;
+  static_cast<uds::GatBwdColsArgs &>(ca) = uds::GatBwdColsArgs{gt->d_rowptr, gt->d_col, perm_t, linear ? gout : g_ws, alpha_ws, de_ws, ds_self,
+                                                               a_self, a_nbr, d_hx, ds_nbr, (int)n, d4, (int)S, g->nnz};
+  ca.hx = hx, ca.apart = nullptr;
+  return launched(what, uds::launch_gat_bwd_act(ra, ca, db, da, parts, static_cast<hipStream_t>(stream)));
+}
+
 int uds_gat_aggregate_heads(const uds_csr_t *g, const float *hx, const float *s_self, const float *s_nbr, const float *bias,
                             const float *edge_mask, const float *coef, int64_t S, int64_t H, int64_t C, int concat, int act,
                             float *out, float *alpha_out, uds_stream_t stream) {

@@ -32,7 +32,7 @@ from . import _lib
 from .graph import DrainageGraph, csr_from_dense
 from . import autograd as _ag
 from .graph import csr_from_dense, edge_based_adj_csr, node_based_adj_csr
-from .layers import Dense, DiffusionConv, Dropout, DropoutStream, GCNConv, GraphBaseBlock, NodeEdge, SpatialBlock, SpatialLayer, _glorot_uniform, _packed_kernel, _param
+from .layers import Dense, DiffusionConv, Dropout, DropoutStream, GATConv, GCNConv, GraphBaseBlock, NodeEdge, SpatialBlock, SpatialLayer, _glorot_uniform, _packed_kernel, _param
 
 
 class Conv1D(nn.Module):
@@ -235,6 +235,7 @@ def _find_keras_weight(weights, lname, kname):
 class Emulator(nn.Module):
     _snapshot_remainder = False
     _dense_node_edge_train = False
+    _fused_gat_backward = False
 
     def __init__(self, conv=None, resnet=False, recurrent=None, args=None, precision='bf16x3', generator=None):
         super().__init__()
@@ -459,6 +460,20 @@ class Emulator(nn.Module):
         for m in self.modules():
             if isinstance(m, NodeEdge):
                 m.dense_train = self._dense_node_edge_train
+
+    @property
+    def fused_gat_backward(self):
+        """True: every single-head GATConv of the model -- both spatial blocks and the graph_base block -- takes its backward from
+        one uds_gat_backward_act call (GATConv.fused_backward: activation, attention / aggregation, bias and attention-kernel
+        gradients in three launches).  Default False: the chain of separate steps.  The forward pass is the same."""
+        return self._fused_gat_backward
+
+    @fused_gat_backward.setter
+    def fused_gat_backward(self, on):
+        self._fused_gat_backward = bool(on)
+        for m in self.modules():
+            if isinstance(m, GATConv):
+                m.fused_backward = self._fused_gat_backward
 
     # ------------------------------------------------------------------ the non-graph baseline (conv False)
     def _build_mlp(self, d, h, H, L, a, gen, pr):

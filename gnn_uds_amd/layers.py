@@ -162,6 +162,9 @@ class GATConv(nn.Module):
         self._gen = generator
         self._graphs = _GraphArg()
         self.precision = 'fp32'      # numerics of the backward row GEMMs (the forward linear part is the exact kernel)
+        # True: the single-head layer's backward is one uds_gat_backward_act call (activation, attention / aggregation, bias and
+        # attention-kernel gradients); False: the chain of separate steps.  The forward pass is the same.
+        self.fused_backward = False
         self.kernel = self.attn_kernel_self = self.attn_kernel_neighs = self.bias = None
         if in_channels is not None:
             self.build(in_channels, 'cpu')
@@ -232,7 +235,7 @@ class GATConv(nn.Module):
         fin = xs.shape[-1] + (0 if xbs is None else xbs.shape[-1])
         if coef is not None or _ag.grad_on(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias):
             out = _ag.GatFn.apply(xs, xbs, self.kernel, self.attn_kernel_self, self.attn_kernel_neighs, self.bias,
-                                  self.activation, h, self.precision, coef, mk)
+                                  self.activation, h, self.precision, coef, mk, self.fused_backward)
         elif mk is not None:
             hx, s_self, s_nbr = _lib.dense_act(xs, self.kernel.reshape(fin, self.channels), None, 'linear', xbs,
                                                attn=(self.attn_kernel_self.reshape(-1), self.attn_kernel_neighs.reshape(-1)))

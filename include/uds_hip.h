@@ -584,6 +584,29 @@ int uds_gat_backward_ex(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *
                         const float *edge_mask, const float *coef, int64_t S, int64_t d, float *alpha_ws, float *de_ws,
                         float *d_hx, float *ds_self, float *ds_nbr, uds_stream_t stream);
 
+/* The whole reverse mode of a single-head GAT layer after its projection, as ONE operator: uds_gat_backward_ex with the
+ * activation backward, the bias gradient and the attention-kernel gradients folded into its two passes (the tape through
+ * GATConv of emulator.py:225-230 in the training step, emulator.py:457-484).  out (S,n,d) = the layer's output, gout = dL/dout,
+ * act = the layer's UDS_ACT_* code; edge_mask / coef (S,nnz) or NULL as in uds_gat_backward_ex.
+ *   g     = gout * act'(out)           in registers of the row pass, in fp32 with the operation order of the element-wise form
+ *                                      (relu: out > 0 ? gout : 0; tanh: gout * (1 - out * out), no FMA; ...)
+ *   d_hx, ds_self, ds_nbr              bitwise those of uds_gat_backward_ex on that g with an edge_mask, of uds_gat_backward[_coef]
+ *                                      without one (the row pass takes the kernel those entries take)
+ *   db (d,)    = sum_{s,i} g[s,i,:]                                                      or NULL: not computed
+ *   da (2,d)   = [sum_{s,i} ds_self[s,i] hx[s,i,:], sum_{s,i} ds_nbr[s,i] hx[s,i,:]]     or NULL: not computed
+ * db and da are summed in fp32: per thread over its rows, per workgroup over its threads in LDS, then over the workgroups'
+ * partials by a third launch, each in a fixed order -- no atomics, the same inputs give the same bits.  Three launches: rows,
+ * columns, reduce.  workspace: uds_gat_backward_act_workspace_floats(S, n, nnz, d) floats, 16-byte aligned, holding alpha and
+ * de (S * nnz each), g (S * n * d) and the partials (3 * d * min(S * n, 2048) floats: a workgroup owns consecutive row blocks,
+ * so their number does not grow with the batch); workspace_floats = its size.  Returns -22 and touches nothing for a NULL
+ * argument, d not a multiple of 4 or above 256, S outside [0, 65535], a transposed handle of another shape or entry count, an
+ * unknown activation code, misaligned tensors or a workspace that is too small.  S = 0 or an empty pattern: db = da = 0. */
+int64_t uds_gat_backward_act_workspace_floats(int64_t S, int64_t n, int64_t nnz, int64_t d);
+int uds_gat_backward_act(const uds_csr_t *g, const uds_csr_t *gt, const int32_t *perm_t, const float *out, const float *gout, int act,
+                         const float *hx, const float *s_self, const float *s_nbr, const float *a_self, const float *a_nbr,
+                         const float *edge_mask, const float *coef, int64_t S, int64_t d, float *d_hx, float *ds_self,
+                         float *ds_nbr, float *db, float *da, float *workspace, int64_t workspace_floats, uds_stream_t stream);
+
 /* MULTI-HEAD attention / aggregation: spektral GATConv with attn_heads = H, concat_heads true or false and return_attn_coef
  * (GATConv._call_dense; the reference builds its layers with one head, emulator.py:229-230, so H > 1 is an extension of it).
  * hx (S, n, H*C) with head-major columns (x @ kernel.reshape(F, H*C)), s_self / s_nbr (S, n, H), edge_mask (S, nnz) or NULL shared
