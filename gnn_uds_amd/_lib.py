@@ -49,6 +49,8 @@ SYMBOLS = {
     'uds_attn_sum_pool_backward': (_c_int, [_c_ptr, _c_i64, _c_ptr, _c_i64, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr,
                                             _c_ptr, _c_ptr]),
     'uds_dropout': (_c_int, [_c_ptr, _c_i64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _c_ptr, _c_ptr]),
+    'uds_adam_workspace_floats': (_c_i64, [_c_ptr, _c_i64]),
+    'uds_adam_step': (_c_int, [_c_ptr, _c_i64, _c_ptr] + [ctypes.c_double] * 5 + [_c_ptr, _c_ptr, _c_i64, _c_ptr]),
     'uds_recurrent_forward_train': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
     'uds_recurrent_backward': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
     'uds_recurrent_bwd_packed_bytes': (_c_i64, [_c_i64, _c_int]),
@@ -156,6 +158,11 @@ class SpatialParams(ctypes.Structure):
     """uds_spatial_params_t"""
     _fields_ = [(n, _c_ptr) for n in ('xe_k', 'xe_b', 'ex_k', 'ex_b', 'ne_n_val', 'ne_e_val',
                                       'gx_k', 'gx_as', 'gx_an', 'gx_b', 'ge_k', 'ge_as', 'ge_an', 'ge_b', 'packed')]
+
+
+class AdamTensor(ctypes.Structure):
+    """uds_adam_tensor_t"""
+    _fields_ = [('p', _c_ptr), ('g', _c_ptr), ('m', _c_ptr), ('v', _c_ptr), ('numel', _c_i64)]
 
 
 class UdsError(RuntimeError):
@@ -1121,6 +1128,45 @@ def cumsum_act(x, res=None, act='linear', out=None):
     _check(lib.uds_cumsum_act(_dev(x, 'x'), _dev(res, 'res', True), B, T, R, F, ACT[act], _dev(out, 'out'), _stream()),
            'uds_cumsum_act')
     return out
+
+
+ADAM_SPAN, ADAM_TABLE = 4096, 64      # elements per workgroup and tensors per launch of uds_adam_step (csrc/kernels_optim.hpp)
+
+
+def adam_workspace_floats(numels):
+    """Floats of workspace uds_adam_step needs for tensors of these sizes (one double per workgroup)."""
+    arr = (_c_i64 * len(numels))(*[int(n) for n in numels])
+    need = int(load().uds_adam_workspace_floats(arr, len(numels)))
+    if need < 0:
+        raise UdsError('uds_adam_workspace_floats: bad sizes %r' % (list(numels),))
+    return need
+
+
+def adam_step(ps, gs, ms, vs, state, workspace, loss=None, lr=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None):
+    """One Keras-Adam step with per-variable clipnorm on lists of contiguous fp32 device tensors (include/uds_hip.h:
+    uds_adam_step), in place on ps, ms, vs.  state: int32[4] device tensor ([0] step count, [1] status of this call), zero
+    before the first step; workspace: fp32 device tensor of adam_workspace_floats(...) elements whose storage is 8-byte
+    aligned; loss: a 0-d / 1-element fp32 device tensor or None.  No allocation, copy or synchronisation: capture-safe."""
+    if not (len(ps) == len(gs) == len(ms) == len(vs)):
+        raise UdsError('adam_step: %d parameters, %d gradients, %d / %d moments' % (len(ps), len(gs), len(ms), len(vs)))
+    if not isinstance(state, torch.Tensor) or not state.is_cuda or state.dtype != torch.int32 or state.numel() != 4 or not state.is_contiguous():
+        raise UdsError('state must be a contiguous int32 HIP tensor of 4 elements')
+    _same_device(state.device.index, 'state')
+    table = (AdamTensor * max(len(ps), 1))()
+    for i, (p, g, m, v) in enumerate(zip(ps, gs, ms, vs)):
+        if not (tuple(g.shape) == tuple(p.shape) == tuple(m.shape) == tuple(v.shape)):
+            raise UdsError('adam_step: tensor %d: parameter %r, gradient %r, moments %r / %r' % (i, tuple(p.shape), tuple(g.shape), tuple(m.shape),
+                                                                                                 tuple(v.shape)))
+        if p.numel() == 0:
+            for t, name in ((p, 'p'), (g, 'g'), (m, 'm'), (v, 'v')):
+                _nothing_to_launch(t, '%s[%d]' % (name, i), None)
+            continue
+        table[i] = AdamTensor(_dev(p, 'p[%d]' % i), _dev(g, 'g[%d]' % i), _dev(m, 'm[%d]' % i), _dev(v, 'v[%d]' % i), p.numel())
+    if loss is not None and loss.numel() != 1:
+        raise UdsError('loss must hold one element, got %r' % (tuple(loss.shape),))
+    _check(load().uds_adam_step(table, len(ps), _dev(loss, 'loss', True), float(lr), float(beta_1), float(beta_2), float(epsilon),
+                                0.0 if clipnorm is None else float(clipnorm), state.data_ptr(), _dev(workspace, 'workspace'), workspace.numel(),
+                                _stream()), 'uds_adam_step')
 
 
 def flow_balance(handle, sign, flow, scale_in, scale_out):

@@ -34,6 +34,7 @@
 #include "kernels_recurrent_bwd.hpp"
 #include "kernels_tail.hpp"
 #include "kernels_fit_tail.hpp"
+#include "kernels_optim.hpp"
 #include "tile_plan.hpp"
 
 namespace {
@@ -993,6 +994,79 @@ int uds_dropout(const float *x, int64_t n, float rate, uint64_t seed, uint64_t o
                      (unsigned)std::min<double>(4294967295.0, std::ceil((double)rate * 4294967296.0)), 1.0f / (1.0f - rate)};
   hipLaunchKernelGGL(uds::k_dropout, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   return launched("uds_dropout", hipGetLastError());
+}
+
+// ---- Keras Adam with per-variable clipnorm over a list of tensors (kernels_optim.hpp).  Workgroups per tensor: one per
+// ADAM_SPAN elements; the partial of workgroup b of launch k sits at partial[first block of launch k + b].
+namespace {
+inline int64_t adam_blocks(int64_t numel) { return (numel + uds::ADAM_SPAN - 1) / uds::ADAM_SPAN; }
+}  // namespace
+
+int64_t uds_adam_workspace_floats(const int64_t *numel, int64_t n_tensors) {
+  if (!numel || n_tensors < 0) return -1;
+  int64_t blocks = 0;
+  for (int64_t i = 0; i < n_tensors; ++i) {
+    if (numel[i] < 0) return -1;
+    blocks += adam_blocks(numel[i]);
+  }
+  return 2 * blocks;                                  // one double per workgroup
+}
+
+int uds_adam_step(const uds_adam_tensor_t *tensors, int64_t n_tensors, const float *loss, double lr, double beta_1, double beta_2,
+                  double epsilon, double clipnorm, int32_t *state, float *workspace, int64_t workspace_floats, uds_stream_t stream) {
+  const char *what = "uds_adam_step";
+  UDS_REQUIRE(n_tensors >= 0 && (n_tensors == 0 || tensors) && state, "%s: NULL argument", what);
+  UDS_REQUIRE((reinterpret_cast<uintptr_t>(state) & 3) == 0 && (reinterpret_cast<uintptr_t>(loss) & 3) == 0, "%s: state / loss not 4-byte aligned", what);
+  UDS_REQUIRE(lr == lr && beta_1 >= 0 && beta_1 < 1 && beta_2 >= 0 && beta_2 < 1 && epsilon >= 0, "%s: lr=%g beta_1=%g beta_2=%g epsilon=%g", what, lr,
+              beta_1, beta_2, epsilon);
+  int64_t blocks = 0;
+  for (int64_t i = 0; i < n_tensors; ++i) {
+    const uds_adam_tensor_t &x = tensors[i];
+    UDS_REQUIRE(x.numel >= 0, "%s: tensor %lld has numel=%lld", what, (long long)i, (long long)x.numel);
+    if (x.numel == 0) continue;
+    UDS_REQUIRE(x.p && x.g && x.m && x.v, "%s: tensor %lld has a NULL pointer", what, (long long)i);
+    UDS_REQUIRE(((reinterpret_cast<uintptr_t>(x.p) | reinterpret_cast<uintptr_t>(x.g) | reinterpret_cast<uintptr_t>(x.m) | reinterpret_cast<uintptr_t>(x.v)) & 3) == 0,
+                "%s: tensor %lld is not 4-byte aligned", what, (long long)i);
+    UDS_REQUIRE(adam_blocks(x.numel) < INT32_MAX / 2, "%s: tensor %lld (numel=%lld) too large for one launch", what, (long long)i, (long long)x.numel);
+    blocks += adam_blocks(x.numel);
+  }
+  UDS_REQUIRE(blocks == 0 || (workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0), "%s: workspace NULL or not 8-byte aligned", what);
+  UDS_REQUIRE(workspace_floats >= 2 * blocks, "%s: workspace of %lld floats, %lld needed (uds_adam_workspace_floats)", what, (long long)workspace_floats,
+              (long long)(2 * blocks));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  double *partial = reinterpret_cast<double *>(workspace);
+  uds::AdamHyper h{lr, beta_1, beta_2, (float)beta_1, (float)(1.0 - beta_1), (float)beta_2, (float)(1.0 - beta_2), (float)epsilon,
+                   clipnorm > 0 ? (float)clipnorm : 0.f};
+  // both passes cut the list into the same launches: up to ADAM_TABLE tensors and 2^30 workgroups each
+  for (int pass = 0; pass < 2; ++pass) {
+    int64_t i = 0, base = 0;
+    while (i < n_tensors) {
+      uds::AdamTable t;
+      std::memset(&t, 0, sizeof t);
+      int32_t grid = 0;
+      for (; i < n_tensors && t.n < uds::ADAM_TABLE; ++i) {
+        const uds_adam_tensor_t &x = tensors[i];
+        if (x.numel == 0) continue;
+        const int64_t nb = adam_blocks(x.numel);
+        if (t.n > 0 && grid + nb > (int64_t)1 << 30) break;
+        t.p[t.n] = x.p; t.g[t.n] = x.g; t.m[t.n] = x.m; t.v[t.n] = x.v;
+        t.numel[t.n] = x.numel;
+        t.block0[t.n] = grid;
+        grid += (int32_t)nb;
+        t.block0[++t.n] = grid;
+      }
+      if (t.n == 0) break;
+      if (pass == 0)
+        hipLaunchKernelGGL(uds::k_adam_sumsq, dim3((unsigned)grid), dim3(uds::ADAM_THREADS), 0, st, t, partial + base, state);
+      else
+        hipLaunchKernelGGL(uds::k_adam_update, dim3((unsigned)grid), dim3(uds::ADAM_THREADS), 0, st, t, (const double *)(partial + base), loss,
+                           (const int32_t *)state, h);
+      if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(UDS_EHIP, "%s: pass %d launch -> %s", what, pass + 1, hipGetErrorString(e));
+      base += grid;
+    }
+  }
+  hipLaunchKernelGGL(uds::k_adam_commit, dim3(1), dim3(64), 0, st, loss, state);
+  return launched(what, hipGetLastError());
 }
 
 int uds_flow_balance(const uds_csr_t *inc_n, const float *sign, const float *flow, int64_t S, const float *scale_in,

@@ -203,6 +203,66 @@ class KerasAdam:
         torch._foreach_addcdiv_(ps, ms, den, value=-lr_t)
 
 
+class HipKerasAdam:
+    """`KerasAdam` as ONE HIP operator (uds_adam_step: per-variable norms, clipping, moments and update in two passes over the
+    whole parameter list) with the step count and a status word on the device, so that a captured graph can replay a step:
+    nothing per step is computed on the host.  Same constructor and the same `state_dict` format as `KerasAdam` (a checkpoint
+    written by either loads into the other); `step(loss)` never synchronises -- a non-finite loss or gradient norm leaves every
+    parameter, moment and the step count as they were and is reported by `raise_if_not_finite()`, the one 4-byte read of a step."""
+
+    def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None):
+        self.params = list(params)
+        self.lr, self.b1, self.b2, self.eps, self.clipnorm = learning_rate, beta_1, beta_2, epsilon, clipnorm
+        self.m = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.v = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        dev = self.params[0].device if self.params else torch.device('cpu')
+        self.state = torch.zeros(4, dtype=torch.int32, device=dev)        # [0] t, [1] status of the last step, [2..3] kernel scratch
+        self._ws = torch.empty(_lib.adam_workspace_floats([p.numel() for p in self.params]), dtype=torch.float32, device=dev)
+
+    @property
+    def t(self):
+        return int(self.state[0])
+
+    @t.setter
+    def t(self, value):
+        self.state[0] = int(value)
+
+    def state_dict(self):
+        return {'t': self.t, 'm': [t.detach().cpu() for t in self.m], 'v': [t.detach().cpu() for t in self.v]}
+
+    def load_state_dict(self, sd):
+        if len(sd['m']) != len(self.params) or any(tuple(a.shape) != tuple(p.shape) for a, p in zip(sd['m'], self.params)):
+            raise ValueError('optimizer state does not match the model parameters')
+        self.t = int(sd['t'])
+        for dst, src in zip(self.m, sd['m']):
+            dst.copy_(src)
+        for dst, src in zip(self.v, sd['v']):
+            dst.copy_(src)
+
+    @torch.no_grad()
+    def step(self, loss=None):
+        """One update of every parameter that has a gradient (in place; gradients are only read).  loss: the step's 0-d loss
+        tensor, tested for NaN / Inf on the device, or None."""
+        idx = [i for i, p in enumerate(self.params) if p.grad is not None]
+        for i in idx:
+            if not self.params[i].is_contiguous():
+                raise _lib.UdsError('HipKerasAdam: parameter %d is not contiguous' % i)
+        _lib.adam_step([self.params[i] for i in idx], [self.params[i].grad.contiguous() for i in idx], [self.m[i] for i in idx],
+                       [self.v[i] for i in idx], self.state, self._ws, None if loss is None else loss.detach().reshape(1), self.lr, self.b1,
+                       self.b2, self.eps, self.clipnorm)
+        for i in idx:           # the kernel wrote the parameters behind autograd's back: caches keyed on `_version` must see a change
+            torch.autograd.graph.increment_version(self.params[i])
+
+    def raise_if_not_finite(self):
+        """The exceptions of the eager step for the last `step`: `fit_eval`'s for a non-finite loss, `KerasAdam.step`'s for a
+        non-finite gradient norm.  In either case that step changed nothing."""
+        status = int(self.state[1])
+        if status & 1:
+            raise FloatingPointError('Loss contains NaN or Inf values.')
+        if status & 2:
+            raise FloatingPointError('grads contain NaN/Inf!')
+
+
 def _numeric_suffix(name):
     tail = name.rsplit('_', 1)[-1]
     return int(tail) if tail.isdigit() else 0
@@ -236,6 +296,10 @@ class Emulator(nn.Module):
     _snapshot_remainder = False
     _dense_node_edge_train = False
     _fused_gat_backward = False
+    _graphed_fit = False
+    FIT_GRAPHS = 4             # captured `fit_eval` graphs kept per model (least recently used out)
+    last_fit_path = None       # 'graph' (replayed), 'graph-capture' (captured, then replayed) or 'eager' after a fit_eval call
+    last_fit_refusal = None    # with graphed_fit: why the last fit_eval call ran eager (fit_graph_refusal), or None
 
     def __init__(self, conv=None, resnet=False, recurrent=None, args=None, precision='bf16x3', generator=None):
         super().__init__()
@@ -474,6 +538,26 @@ class Emulator(nn.Module):
         for m in self.modules():
             if isinstance(m, GATConv):
                 m.fused_backward = self._fused_gat_backward
+
+    @property
+    def graphed_fit(self):
+        """True: `fit_eval` replays ONE captured HIP graph per step (forward, tail, backward and `HipKerasAdam` for fit=True;
+        forward and tail for fit=False) where `fit_graph_refusal()` allows, and runs the eager step with the same
+        `HipKerasAdam` where it does not.  Default False: the eager step with `KerasAdam`.  Switching converts an existing
+        optimizer through its `state_dict`; switching off frees the graphs."""
+        return self._graphed_fit
+
+    @graphed_fit.setter
+    def graphed_fit(self, on):
+        on = bool(on)
+        want = HipKerasAdam if on else KerasAdam
+        if self._optimizer is not None and on != self._graphed_fit and type(self._optimizer) is not want:
+            new = want(self._optimizer.params, self.learning_rate, clipnorm=1.0)
+            new.load_state_dict(self._optimizer.state_dict())
+            self._optimizer = new
+        if not on:
+            self.drop_fit_graphs()
+        self._graphed_fit = on
 
     # ------------------------------------------------------------------ the non-graph baseline (conv False)
     def _build_mlp(self, d, h, H, L, a, gen, pr):
@@ -800,13 +884,19 @@ class Emulator(nn.Module):
         an entry survives iff trunc(value) != 0, so with a 0/1 adjacency any setting below 1 removes it."""
         csr, raw, pos = self._adj_pattern()
         dev = a.device
-        base = torch.as_tensor(np.trunc(raw) != 0, dtype=torch.float32, device=dev)
-        mask = base.expand(tuple(a.shape[:-1]) + (csr.nnz,)).clone()
         ok = pos >= 0
+        key = ('adj_action', str(dev), a.dtype)
+        hit = self._idx_cache.get(key)               # constants of the model, uploaded once (a captured step cannot upload)
+        if hit is None:
+            hit = self._idx_cache[key] = (torch.as_tensor(np.trunc(raw) != 0, dtype=torch.float32, device=dev),
+                                          torch.as_tensor(raw[pos[ok]], dtype=a.dtype, device=dev),
+                                          torch.as_tensor(np.nonzero(ok)[0], device=dev), torch.as_tensor(pos[ok], device=dev))
+        base, raw_w, src, dst = hit
+        mask = base.expand(tuple(a.shape[:-1]) + (csr.nnz,)).clone()
         if ok.any():
-            w = torch.as_tensor(raw[pos[ok]], dtype=a.dtype, device=dev) if g else torch.ones(int(ok.sum()), dtype=a.dtype, device=dev)
-            val = a[..., torch.as_tensor(np.nonzero(ok)[0], device=dev)] * w
-            mask[..., torch.as_tensor(pos[ok], device=dev)] = (torch.trunc(val) != 0).to(torch.float32)
+            w = raw_w if g else torch.ones(int(ok.sum()), dtype=a.dtype, device=dev)
+            val = a[..., src] * w
+            mask[..., dst] = (torch.trunc(val) != 0).to(torch.float32)
         return mask
 
     def _adj_mask_from(self, adj, device):
@@ -861,7 +951,7 @@ class Emulator(nn.Module):
         s_in, s_out = hit[1], hit[2]
         lead = flow.shape[:-2]
         if _ag.grad_on(flow):
-            edges = torch.as_tensor(self.edges, dtype=torch.int64, device=flow.device)
+            edges = self._dev_index('edges', self.edges, flow.device)
             q_in, q_out = _ag.FlowBalanceFn.apply(flow.reshape(-1, self.n_edge), self._inc_handle, self._inc_sign, s_in, s_out, edges)
         else:
             q_in, q_out = _lib.flow_balance(self._inc_handle, self._inc_sign, flow.reshape(-1, self.n_edge).contiguous(), s_in, s_out)
@@ -1342,10 +1432,28 @@ class Emulator(nn.Module):
         fl_loss = sums[1] / (rows * self.n_node) if self.if_flood and not self.balance else None
         return node_loss, fl_loss, edge_loss
 
+    def _fit_total_loss(self, node_loss, fl_loss, edge_loss):
+        """The scalar a training step differentiates (emulator.py:466-473)."""
+        loss = node_loss + edge_loss
+        if self.gradnorm:                    # GradNorm task weights (emulator.py:470-473): constants for this step
+            alpha = self._alphas(node_loss.device)
+            loss = alpha[0].detach() * loss
+        if self.if_flood:
+            if fl_loss is None:
+                raise NotImplementedError('if_flood with balance: the reference leaves fl_loss undefined here (emulator.py:466,473)')
+            loss = loss + (alpha[1].detach() * fl_loss if self.gradnorm else fl_loss)
+        return loss
+
     def fit_eval(self, x, a, b, y, ex, ey, fit=True):
         """One training (fit=True) or evaluation step on NORMALISED tensors (emulator.py:457-484): forward through
         `_model`, node MSE (+ weighted flood BCE) + link MSE, reverse mode through the HIP operators (autograd.py), Adam with
-        per-variable clipnorm=1.  Returns [node_loss, (flood_loss,) edge_loss] as 0-d tensors."""
+        per-variable clipnorm=1.  Returns [node_loss, (flood_loss,) edge_loss] as 0-d tensors.  With `graphed_fit` the step is one
+        replay of a captured graph (`_fit_eval_graph`) unless `fit_graph_refusal` names a reason."""
+        if self._graphed_fit:
+            self.last_fit_refusal = self.fit_graph_refusal(x, a, b, y, ex, ey)
+            if self.last_fit_refusal is None:
+                return self._fit_eval_graph(x, a, b, y, ex, ey, fit)
+        self.last_fit_path = 'eager'
         params = [p for p in self.parameters()]
         if fit:
             for p in params:
@@ -1354,14 +1462,7 @@ class Emulator(nn.Module):
             ae = self.get_edge_action(a, True) if self.act else None
             node_loss, fl_loss, edge_loss = self._fit_losses(x, a, b, y, ex, ey, ae, fit)
             if fit:
-                loss = node_loss + edge_loss
-                if self.gradnorm:                    # GradNorm task weights (emulator.py:470-473): constants for this step
-                    alpha = self._alphas(node_loss.device)
-                    loss = alpha[0].detach() * loss
-                if self.if_flood:
-                    if fl_loss is None:
-                        raise NotImplementedError('if_flood with balance: the reference leaves fl_loss undefined here (emulator.py:466,473)')
-                    loss = loss + (alpha[1].detach() * fl_loss if self.gradnorm else fl_loss)
+                loss = self._fit_total_loss(node_loss, fl_loss, edge_loss)
                 from .dist import all_ranks_finite, allreduce_gradients
                 if not all_ranks_finite(loss):       # agreed over the data-parallel ranks: all raise or none does
                     raise FloatingPointError('Loss contains NaN or Inf values.')
@@ -1370,10 +1471,147 @@ class Emulator(nn.Module):
                 loss.backward()
                 allreduce_gradients(params)          # data-parallel ranks: one bucketed all-reduce (no-op on one rank)
                 if self._optimizer is None:
-                    self._optimizer = KerasAdam(params, self.learning_rate, clipnorm=1.0)
+                    self._optimizer = (HipKerasAdam if self._graphed_fit else KerasAdam)(params, self.learning_rate, clipnorm=1.0)
                 self._optimizer.step()
+                if isinstance(self._optimizer, HipKerasAdam):
+                    self._optimizer.raise_if_not_finite()
         out = [node_loss.detach()] + ([fl_loss.detach()] if self.if_flood and fl_loss is not None else []) + [edge_loss.detach()]
         return out
+
+    # ------------------------------------------------------------------ fit_eval as one captured graph per step
+    def fit_graph_refusal(self, *tensors):
+        """Why a `fit_eval` step of this model (on these tensors, if given) cannot be captured -- it then runs eager -- or None:
+        every reason is a piece of HOST state the step reads, and the decision is made before anything is captured."""
+        if self.dropout:
+            return 'dropout > 0: the mask offsets of the dropout stream are host counters that advance per call'
+        from torch import distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            return 'a process group with %d ranks: the gradient all-reduce and the agreed finite flag run between host steps' % dist.get_world_size()
+        where = [p for p in self.parameters()] + [t for t in tensors if isinstance(t, torch.Tensor)]
+        if any(not t.is_cuda for t in where):
+            return 'CPU tensors: a graph is captured on the device stream'
+        return None
+
+    def _fit_graph_key(self, x, a, b, y, ex, ey, fit):
+        """What a captured step depends on beyond the values in device memory: shapes and device of the inputs, `fit`, the parameters
+        (their storage and which of them train), the objects whose storage the graph reads (optimizer state, norms, GradNorm
+        weights), the hyper-parameters and route flags read on the host, and for an evaluation step which dense NodeEdge layers
+        have a bias off their support (a host decision of `NodeEdge.support_values`)."""
+        shapes = tuple(None if t is None else (tuple(t.shape), str(t.dtype)) for t in (x, a, b, y, ex, ey))
+        params = tuple((p.data_ptr(), bool(p.requires_grad or fit)) for p in self.parameters())
+        opt = self._optimizer
+        held = (None if opt is None or not fit else (id(opt), opt.m[0].data_ptr() if opt.m else 0),
+                tuple((k, id(v)) for k, v in sorted(self._norms.items())),
+                None if not (self.gradnorm and fit) or getattr(self, '_alpha', None) is None else self._alpha.data_ptr())
+        rest = None if fit else tuple(m.support_values()[1] is None for m in self.modules() if isinstance(m, NodeEdge) and not m.sparse)
+        return (shapes, str(x.device), bool(fit), params, held, self.roll, self.gradnorm, self.learning_rate, self.fused_fit_tail,
+                self.dense_node_edge_train, self.fused_gat_backward, self.fused_temporal, self.snapshot_remainder, rest)
+
+    def _invalidate_weight_packs(self):
+        """Forget every packed or derived copy of a weight that is cached per parameter version, so that the next forward rebuilds
+        it: inside a capture that makes every pack a node of the graph (a replay bumps no `_version`)."""
+        for m in self.modules():
+            for name in ('_packed', '_blocks', '_wide', '_val_cache', '_rest_packed', '_vals'):
+                if name in m.__dict__:
+                    setattr(m, name, None)
+
+    def _fit_graph_body(self, inputs, fit, params):
+        """The step itself, as the eager `fit_eval` runs it on one rank, with the finite tests left to `HipKerasAdam` on the device."""
+        x, a, b, y, ex, ey = inputs
+        with torch.set_grad_enabled(bool(fit)):
+            ae = self.get_edge_action(a, True) if self.act else None
+            node_loss, fl_loss, edge_loss = self._fit_losses(x, a, b, y, ex, ey, ae, fit)
+            if fit:
+                loss = self._fit_total_loss(node_loss, fl_loss, edge_loss)
+                for p in params:
+                    p.grad = None
+                loss.backward()
+                self._optimizer.step(loss)
+        return [node_loss.detach()] + ([fl_loss.detach()] if self.if_flood and fl_loss is not None else []) + [edge_loss.detach()]
+
+    def _capture_fit_graph(self, inputs, fit, params):
+        """Static input buffers, two warm-up steps on a side stream that leave the model as it was, then the capture on ONE stream
+        (nothing forks inside it: the graph is a chain).  An error during warm-up or capture propagates."""
+        dev = inputs[0].device
+        G = dict(inputs=[None if t is None else t.detach().clone() for t in inputs], params=params)
+        opt = self._optimizer
+        if fit and not isinstance(opt, HipKerasAdam):
+            raise TypeError('graphed_fit needs a HipKerasAdam optimizer, the model holds a %s' % type(opt).__name__)
+        ne_dense = [m for m in self.modules() if isinstance(m, NodeEdge) and not m.sparse]
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            if fit:
+                with torch.no_grad():
+                    saved = [t.detach().clone() for t in params + opt.m + opt.v + [opt.state]]
+            for _ in range(2):                              # caches, handles, tile plans, kernel code objects, library workspaces
+                self._fit_graph_body(G['inputs'], fit, params)
+            if fit:
+                with torch.no_grad():
+                    for dst, src in zip(params + opt.m + opt.v + [opt.state], saved):
+                        dst.copy_(src)
+                for p in params:
+                    p.grad = None
+            else:
+                for m in ne_dense:                          # asked of the device here: a capture cannot
+                    m._capture_rest_none = m.support_values()[1] is None
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self._invalidate_weight_packs()
+        G['graph'] = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(G['graph']):
+                G['out'] = self._fit_graph_body(G['inputs'], fit, params)
+        finally:
+            self._invalidate_weight_packs()                 # a pack made while capturing holds nothing until a replay
+            for m in ne_dense:
+                m._capture_rest_none = None
+        return G
+
+    def _fit_eval_graph(self, x, a, b, y, ex, ey, fit):
+        inputs = (x, a if self.act else None, b, y, ex, ey)
+        params = [p for p in self.parameters()]
+        if fit:
+            for p in params:
+                p.requires_grad_(True)
+            if self.gradnorm:
+                self._alphas(x.device)                      # created before the capture; fit_grad_norm updates it in place
+            if self._optimizer is None:                     # before the key: the graph reads its moments and state
+                self._optimizer = HipKerasAdam(params, self.learning_rate, clipnorm=1.0)
+        if getattr(self, '_fit_graphs', None) is None:
+            from collections import OrderedDict
+            self._fit_graphs = OrderedDict()
+        for item in list(self._norms):                      # on the device before the key names them (`_norm` moves them on first use)
+            self._norm(item, x.device)
+        key = self._fit_graph_key(*inputs, fit)
+        G = self._fit_graphs.get(key)
+        if G is None:
+            G = self._capture_fit_graph(inputs, fit, params)
+            self._fit_graphs[key] = G
+            while len(self._fit_graphs) > self.FIT_GRAPHS:
+                self._fit_graphs.popitem(last=False)
+            self.last_fit_path = 'graph-capture'
+        else:
+            self._fit_graphs.move_to_end(key)
+            self.last_fit_path = 'graph'
+        with torch.no_grad():
+            for dst, src in zip(G['inputs'], inputs):
+                if dst is not None:
+                    dst.copy_(src)
+        G['graph'].replay()
+        out = [t.clone() for t in G['out']]
+        if fit:
+            for p in params:                                # no kernel: eager code that caches per `_version` re-packs from the new weights
+                torch.autograd.graph.increment_version(p)
+            self._optimizer.raise_if_not_finite()
+        return out
+
+    def drop_fit_graphs(self):
+        """Free the captured `fit_eval` graphs (and the gradients that live in their memory pools)."""
+        if getattr(self, '_fit_graphs', None):
+            self._fit_graphs.clear()
+            for p in self.parameters():
+                p.grad = None
 
     # ------------------------------------------------------------------ GradNorm (:118-125,486-519)
     def _alphas(self, device):
@@ -1566,6 +1804,7 @@ class Emulator(nn.Module):
         """emulator.py:833-852; `retrain=True` also restores the optimizer moments / step count and the GradNorm state, so
         that training resumes where it stopped (`--load_model`, main.py:199-205)."""
         model_dir = model_dir if model_dir is not None else self.model_dir
+        self.drop_fit_graphs()
         keras = None
         if model_dir.endswith('.h5'):                     # the reference's own layout: a Keras weight file (:835-838)
             keras, model_dir = model_dir, os.path.dirname(model_dir)
@@ -1588,7 +1827,7 @@ class Emulator(nn.Module):
         path = os.path.join(model_dir, 'optim.pt')
         if retrain and os.path.exists(path):
             if self._optimizer is None:
-                self._optimizer = KerasAdam([p for p in self.parameters()], self.learning_rate, clipnorm=1.0)
+                self._optimizer = (HipKerasAdam if self._graphed_fit else KerasAdam)([p for p in self.parameters()], self.learning_rate, clipnorm=1.0)
             self._optimizer.load_state_dict(torch.load(path, weights_only=True))
         path = os.path.join(model_dir, 'gradnorm.pt')
         if retrain and self.gradnorm and os.path.exists(path):

@@ -489,8 +489,12 @@ class NodeEdge(nn.Module):
         else:
             val = self.weight.reshape(-1)[flat] * ival + self.bias.reshape(-1)[flat]
             rest = self.bias.clone()
-            rest.reshape(-1)[flat] = 0.0
-            if not bool((rest != 0).any()):
+            rest.reshape(-1).index_fill_(0, flat, 0.0)      # (an indexed store of a Python scalar uploads it: not capturable)
+            if self.weight.is_cuda and torch.cuda.is_current_stream_capturing():
+                # a capture cannot ask the device: Emulator._capture_fit_graph asked before it began (None: keep the remainder)
+                if getattr(self, '_capture_rest_none', None):
+                    rest = None
+            elif not bool((rest != 0).any()):
                 rest = None
         self._val_cache = (key, val.contiguous(), rest)
         self._rest_packed = None
@@ -566,7 +570,7 @@ class NodeEdge(nn.Module):
                 out = _ag.SpmmFn.apply(val, xs, self.handle())
                 if self.bias.requires_grad:
                     off = torch.ones_like(self.bias)
-                    off.reshape(-1)[flat] = 0.0
+                    off.reshape(-1).index_fill_(0, flat, 0.0)
                     rest = self.bias * off
                     if self.precision == 'bf16x3' and xs.shape[-1] % 4 == 0 and xs.shape[-1] <= 64:
                         out = out + _ag.RemainderFn.apply(rest, xs)      # the N x E x (S h) products on the HIP MFMA GEMM

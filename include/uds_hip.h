@@ -772,6 +772,31 @@ int uds_spatial_layer_forward_rem(const uds_network_t *net, const uds_spatial_pa
                                   int64_t d, int act, int flags, float *workspace, float *out_x, float *out_e,
                                   uds_stream_t stream);
 
+/* keras.optimizers.Adam(learning_rate, beta_1, beta_2, epsilon, clipnorm) as TF 2.10 applies it (emulator.py:111), on a whole
+ * list of tensors with the step count on the device -- nothing per step is computed on the host, so a captured graph replays it:
+ *   n_i = ||g_i||_2;  g_i *= clipnorm / max(n_i, clipnorm) (per tensor; clipnorm <= 0: no clipping);
+ *   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;  p -= lr_t m / (sqrt(v) + eps),  lr_t = lr sqrt(1 - b2^t) / (1 - b1^t) (in double),
+ *   t = state[0] + 1.
+ * tensors: a HOST array of n_tensors records of DEVICE pointers (contiguous fp32, 4-byte aligned: 16-byte alignment and a length
+ * that is a multiple of 4 are used where present, not assumed; numel = 0 records are skipped).  The records are copied into the
+ * kernel arguments (64 tensors per launch): the array may be freed when the call returns.  g is only read.
+ * loss: one device float or NULL.  state: int32[4] on the device, zero before the first call: [0] t, [1] status of this call
+ * (bit 0: *loss is NaN / Inf, bit 1: some gradient element is NaN / Inf, i.e. a gradient norm is not finite), [2], [3] scratch.
+ * With a status bit set the call changes none of p, m, v, t.  Otherwise t becomes t + 1, also when n_tensors = 0.
+ * Two passes over the same workgroups (one per 4096 elements of a tensor): sums of squares in double into the workspace, then
+ * the tensor's partials added in index order and the update; no atomics (two calls on the same inputs give the same bits), no
+ * allocation, no copy, no synchronisation.  workspace: uds_adam_workspace_floats(numel, n_tensors) floats, 8-byte aligned. */
+typedef struct {
+  float *p;
+  const float *g;
+  float *m;
+  float *v;
+  int64_t numel;
+} uds_adam_tensor_t;
+int64_t uds_adam_workspace_floats(const int64_t *numel, int64_t n_tensors);   /* HOST array; -1 on a bad argument */
+int uds_adam_step(const uds_adam_tensor_t *tensors, int64_t n_tensors, const float *loss, double lr, double beta_1, double beta_2,
+                  double epsilon, double clipnorm, int32_t *state, float *workspace, int64_t workspace_floats, uds_stream_t stream);
+
 /* Which launches a fused spatial layer makes (host-only bookkeeping: neither entry touches a device).
  *
  * The snapshots of a launch are cut into chunks and one workgroup handles one (tile, chunk) pair: *chunk = the chunk
