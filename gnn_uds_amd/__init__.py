@@ -16,5 +16,7 @@ from . import inp                                                     # noqa: F4
 from .agent import ConvNet, GlobalAttnSumPool                         # noqa: F401,E402
 from . import mpc                                                     # noqa: F401,E402
 from . import mbrl                                                    # noqa: F401,E402
+from .data import WindowStore, WindowTable                            # noqa: F401,E402
+from .train import emulate_event, fit                                 # noqa: F401,E402
 
 __version__ = '0.1.0'

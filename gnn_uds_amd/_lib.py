@@ -51,6 +51,8 @@ SYMBOLS = {
     'uds_dropout': (_c_int, [_c_ptr, _c_i64, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, _c_ptr, _c_ptr]),
     'uds_adam_workspace_floats': (_c_i64, [_c_ptr, _c_i64]),
     'uds_adam_step': (_c_int, [_c_ptr, _c_i64, _c_ptr] + [ctypes.c_double] * 5 + [_c_ptr, _c_ptr, _c_i64, _c_ptr]),
+    'uds_window_batch': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int] + [_c_ptr] * 7),
+    'uds_window_draw': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, ctypes.c_uint64, _c_ptr, _c_ptr, _c_ptr]),
     'uds_recurrent_forward_train': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
     'uds_recurrent_backward': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
     'uds_recurrent_bwd_packed_bytes': (_c_i64, [_c_i64, _c_int]),
@@ -163,6 +165,16 @@ class SpatialParams(ctypes.Structure):
 class AdamTensor(ctypes.Structure):
     """uds_adam_tensor_t"""
     _fields_ = [('p', _c_ptr), ('g', _c_ptr), ('m', _c_ptr), ('v', _c_ptr), ('numel', _c_i64)]
+
+
+class WindowSeries(ctypes.Structure):
+    """uds_window_series_t"""
+    _fields_ = [(n, _c_ptr) for n in ('states', 'flood', 'edge_states', 'settings', 'tide')] + [(n, _c_i64) for n in ('Ttot', 'N', 'E', 'n_act')]
+
+
+class WindowNorm(ctypes.Structure):
+    """uds_window_norm_t"""
+    _fields_ = [(n, _c_ptr) for n in ('span_x', 'min_x', 'span_b', 'min_b', 'span_y', 'min_y', 'span_e', 'min_e')]
 
 
 class UdsError(RuntimeError):
@@ -1167,6 +1179,80 @@ def adam_step(ps, gs, ms, vs, state, workspace, loss=None, lr=1e-3, beta_1=0.9, 
     _check(load().uds_adam_step(table, len(ps), _dev(loss, 'loss', True), float(lr), float(beta_1), float(beta_2), float(epsilon),
                                 0.0 if clipnorm is None else float(clipnorm), state.data_ptr(), _dev(workspace, 'workspace'), workspace.numel(),
                                 _stream()), 'uds_adam_step')
+
+
+WINDOW_DRAW_MAX = 4096                # starts per uds_window_draw call (csrc/kernels_data.hpp)
+
+
+def _dev_i64(t, name):
+    """Device pointer of a contiguous int64 HIP tensor (the 64-bit prefix sums and the draw count of uds_window_draw)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous():
+        raise UdsError('%s must be a contiguous int64 HIP tensor' % name)
+    _same_device(t.device.index, name)
+    return t.data_ptr()
+
+
+def window_batch(states, flood, edge_states, settings, tide, starts, seq_in, t_out, if_flood, norms=None, out=None):
+    """(x, a, b, y, ex, ey) of the B sliding windows at `starts` (int32 device tensor) of the time-major device series, in ONE
+    launch (uds_window_batch; include/uds_hip.h gives the channels).  norms: None (raw) or {'x' | 'b' | 'y' | 'e': (span, min)}
+    device tensors of the output's channel count ('e': 4).  `a` is None without settings.  A start outside the series fills its
+    window with NaN.  out: the six tensors of an earlier call (a: None without settings) to fill again."""
+    what = 'window_batch'
+    if not (isinstance(states, torch.Tensor) and states.dim() == 3 and states.shape[2] == 4):
+        raise UdsError('%s: states must be (Ttot, N, 4)' % what)
+    Ttot, N = states.shape[:2]
+    if not (isinstance(edge_states, torch.Tensor) and edge_states.dim() == 3 and edge_states.shape[0] == Ttot and edge_states.shape[2] == 4):
+        raise UdsError('%s: edge_states must be (%d, E, 4)' % (what, Ttot))
+    E = edge_states.shape[1]
+    for name, t in (('flood', flood), ('tide', tide)):
+        if not (name == 'tide' and t is None) and (not isinstance(t, torch.Tensor) or tuple(t.shape) != (Ttot, N)):
+            raise UdsError('%s: %s must be (%d, %d)' % (what, name, Ttot, N))
+    if settings is not None and (settings.dim() != 2 or settings.shape[0] != Ttot or settings.shape[1] < 1):
+        raise UdsError('%s: settings must be (%d, n_act >= 1)' % (what, Ttot))
+    n_act = 0 if settings is None else settings.shape[1]
+    if starts.dim() != 1:
+        raise UdsError('%s: starts must be one-dimensional' % what)
+    B, cx, cb = starts.shape[0], 5 if if_flood else 4, 1 if tide is None else 2
+    shapes = ((B, seq_in, N, cx), (B, t_out, n_act), (B, t_out, N, cb), (B, t_out, N, cx), (B, seq_in, E, 4), (B, t_out, E, 3))
+    out = [None] * 6 if out is None else list(out)
+    for i, name in enumerate(('x', 'a', 'b', 'y', 'ex', 'ey')):
+        out[i] = None if name == 'a' and settings is None else _out(out[i], shapes[i], states, name)
+    series = WindowSeries(_dev(states, 'states'), _dev(flood, 'flood'), _dev(edge_states, 'edge_states'), _dev(settings, 'settings', True),
+                          _dev(tide, 'tide', True), Ttot, N, E, n_act)
+    norm = None
+    if norms is not None:
+        norm = WindowNorm()
+        for item, c, rows in (('x', cx, N), ('b', cb, N), ('y', cx, N), ('e', 4, E)):
+            if norms.get(item) is not None:
+                for part, t in zip(('span', 'min'), norms[item]):
+                    if tuple(t.shape) != (rows, c):
+                        raise UdsError('%s: norm %r %s must be (%d, %d), got %r' % (what, item, part, rows, c, tuple(t.shape)))
+                    setattr(norm, '%s_%s' % (part, item), _dev(t, 'norm %s %s' % (item, part)))
+    if B == 0:
+        return tuple(out)
+    _check(load().uds_window_batch(ctypes.byref(series), None if norm is None else ctypes.byref(norm), _dev_i32(starts, 'starts'), B,
+                                   int(seq_in), int(t_out), int(bool(if_flood)), *[None if t is None else t.data_ptr() for t in out], _stream()),
+           'uds_window_batch')
+    return tuple(out)
+
+
+def window_draw(table, cum, seed, count, B, out=None):
+    """B window starts (int32 device tensor) drawn from `table` (W int32 starts) with the inclusive 64-bit prefix sums `cum` of
+    their integer weights (uds_window_draw): draw i uses the stream index count + i (Philox4x32-10, key = seed); afterwards
+    count (one int64 device element) is count + B.  Device only; nothing is read back."""
+    if not isinstance(table, torch.Tensor) or not isinstance(cum, torch.Tensor) or table.dim() != 1 or tuple(cum.shape) != tuple(table.shape):
+        raise UdsError('window_draw: table and cum must be one-dimensional tensors of one length')
+    if not isinstance(count, torch.Tensor) or count.numel() != 1:
+        raise UdsError('window_draw: count must be one int64 device element')
+    if out is None:
+        _dev_i32(table, 'table')
+        out = torch.empty(int(B), device=table.device, dtype=torch.int32)
+    elif tuple(out.shape) != (int(B),):
+        raise UdsError('window_draw: out must be (%d,), got %r' % (int(B), tuple(out.shape)))
+    _check(load().uds_window_draw(_dev_i32(table, 'table'), _dev_i64(cum, 'cum'), table.shape[0], int(B),
+                                  int(seed) & 0xFFFFFFFFFFFFFFFF, _dev_i64(count, 'count'), _dev_i32(out, 'out'), _stream()),
+           'uds_window_draw')
+    return out
 
 
 def flow_balance(handle, sign, flow, scale_in, scale_out):

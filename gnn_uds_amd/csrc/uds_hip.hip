@@ -35,6 +35,7 @@
 #include "kernels_tail.hpp"
 #include "kernels_fit_tail.hpp"
 #include "kernels_optim.hpp"
+#include "kernels_data.hpp"
 #include "tile_plan.hpp"
 
 namespace {
@@ -1066,6 +1067,65 @@ int uds_adam_step(const uds_adam_tensor_t *tensors, int64_t n_tensors, const flo
     }
   }
   hipLaunchKernelGGL(uds::k_adam_commit, dim3(1), dim3(64), 0, st, loss, state);
+  return launched(what, hipGetLastError());
+}
+
+// ---- Device-resident training data (kernels_data.hpp).  uds_window_batch: x, a, b, y, ex, ey of B sliding windows, normalised, in
+// one launch (the windows of dataloader.py:93-95,144-169, the batch of dataloader.py:106-143, the normalisations and uploads of
+// main.py:209-232).
+int uds_window_batch(const uds_window_series_t *series, const uds_window_norm_t *norm, const int32_t *starts, int64_t B, int64_t seq_in,
+                     int64_t t_out, int if_flood, float *x, float *a, float *b, float *y, float *ex, float *ey, uds_stream_t stream) {
+  const char *what = "uds_window_batch";
+  UDS_REQUIRE(series && starts && x && b && y && ex && ey, "%s: NULL argument", what);
+  const uds_window_series_t &s = *series;
+  UDS_REQUIRE(s.states && s.flood && s.edge_states, "%s: NULL series (states, flood and edge_states are required)", what);
+  UDS_REQUIRE(s.Ttot >= 1 && s.N >= 1 && s.E >= 1 && s.n_act >= 0 && s.N <= INT32_MAX / 8 && s.E <= INT32_MAX / 8 && s.n_act <= 65536,
+              "%s: Ttot=%lld N=%lld E=%lld n_act=%lld", what, (long long)s.Ttot, (long long)s.N, (long long)s.E, (long long)s.n_act);
+  UDS_REQUIRE((s.n_act > 0) == (s.settings != nullptr) && (s.n_act > 0) == (a != nullptr), "%s: settings / a must be given exactly when n_act > 0 (n_act=%lld)",
+              what, (long long)s.n_act);
+  UDS_REQUIRE(seq_in >= 1 && t_out >= 1 && seq_in + t_out <= 65536, "%s: seq_in=%lld t_out=%lld", what, (long long)seq_in, (long long)t_out);
+  UDS_REQUIRE(B >= 1 && B <= (INT32_MAX - 1) / (seq_in + t_out), "%s: B=%lld outside [1, %lld]", what, (long long)B,
+              (long long)((INT32_MAX - 1) / (seq_in + t_out)));
+  UDS_REQUIRE(aligned16(s.states) && aligned16(s.flood) && aligned16(s.edge_states) && aligned16(s.settings) && aligned16(s.tide),
+              "%s: every series must be 16-byte aligned", what);
+  UDS_REQUIRE(aligned16(x) && aligned16(a) && aligned16(b) && aligned16(y) && aligned16(ex) && aligned16(ey), "%s: every output must be 16-byte aligned", what);
+  UDS_REQUIRE((reinterpret_cast<uintptr_t>(starts) & 3) == 0, "%s: starts not 4-byte aligned", what);
+  uds::WindowBatchArgs k{};
+  if (norm) {
+    const float *q[8] = {norm->span_x, norm->min_x, norm->span_b, norm->min_b, norm->span_y, norm->min_y, norm->span_e, norm->min_e};
+    for (int i = 0; i < 8; i += 2)
+      UDS_REQUIRE((q[i] != nullptr) == (q[i + 1] != nullptr), "%s: norm pair %d needs both its span and its minimum, or neither", what, i / 2);
+    for (int i = 0; i < 8; ++i) UDS_REQUIRE((reinterpret_cast<uintptr_t>(q[i]) & 3) == 0, "%s: norm pointer %d not 4-byte aligned", what, i);
+    k.span_x = q[0]; k.min_x = q[1]; k.span_b = q[2]; k.min_b = q[3]; k.span_y = q[4]; k.min_y = q[5]; k.span_e = q[6]; k.min_e = q[7];
+  }
+  const int64_t chunks = (s.N + s.E + s.n_act + uds::WINDOW_THREADS - 1) / uds::WINDOW_THREADS;
+  UDS_REQUIRE(chunks <= 65535, "%s: N + E + n_act = %lld too large for one launch", what, (long long)(s.N + s.E + s.n_act));
+  k.states = s.states; k.flood = s.flood; k.edge_states = s.edge_states; k.settings = s.settings; k.tide = s.tide;
+  k.starts = starts;
+  k.x = x; k.a = a; k.b = b; k.y = y; k.ex = ex; k.ey = ey;
+  k.Ttot = s.Ttot;
+  k.N = (int)s.N; k.E = (int)s.E; k.n_act = (int)s.n_act; k.seq_in = (int)seq_in; k.t_out = (int)t_out; k.if_flood = if_flood ? 1 : 0;
+  hipLaunchKernelGGL(uds::k_window_batch, dim3((unsigned)(B * (seq_in + t_out)), (unsigned)chunks), dim3(uds::WINDOW_THREADS), 0,
+                     static_cast<hipStream_t>(stream), k);
+  return launched(what, hipGetLastError());
+}
+
+// uds_window_draw: the weighted random draw of a batch of window starts (DataGenerator.prepare_batch, dataloader.py:106-143 over
+// the windows of dataloader.py:93-95,144-169; once per epoch and table, main.py:209-232), then the count bump as a launch of its own.
+int uds_window_draw(const int32_t *starts_table, const uint64_t *cum, int64_t W, int64_t B, uint64_t seed, uint64_t *count, int32_t *out,
+                    uds_stream_t stream) {
+  const char *what = "uds_window_draw";
+  UDS_REQUIRE(starts_table && cum && count && out, "%s: NULL argument", what);
+  UDS_REQUIRE(W >= 1 && W < INT32_MAX, "%s: W=%lld (a table needs at least one window)", what, (long long)W);
+  UDS_REQUIRE(B >= 1 && B <= uds::WINDOW_DRAW_MAX, "%s: B=%lld outside [1, %d]", what, (long long)B, uds::WINDOW_DRAW_MAX);
+  UDS_REQUIRE(((reinterpret_cast<uintptr_t>(cum) | reinterpret_cast<uintptr_t>(count)) & 7) == 0, "%s: cum / count not 8-byte aligned", what);
+  UDS_REQUIRE(((reinterpret_cast<uintptr_t>(starts_table) | reinterpret_cast<uintptr_t>(out)) & 3) == 0, "%s: starts_table / out not 4-byte aligned", what);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  uds::WindowDrawArgs k{starts_table, reinterpret_cast<const unsigned long long *>(cum), reinterpret_cast<const unsigned long long *>(count), out,
+                        (unsigned long long)seed, (int)W, (int)B};
+  hipLaunchKernelGGL(uds::k_window_draw, dim3((unsigned)((B + uds::WINDOW_THREADS - 1) / uds::WINDOW_THREADS)), dim3(uds::WINDOW_THREADS), 0, st, k);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(UDS_EHIP, "%s: draw launch -> %s", what, hipGetErrorString(e));
+  hipLaunchKernelGGL(uds::k_window_bump, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned long long *>(count), (unsigned long long)B);
   return launched(what, hipGetLastError());
 }
 

@@ -797,6 +797,45 @@ int64_t uds_adam_workspace_floats(const int64_t *numel, int64_t n_tensors);   /*
 int uds_adam_step(const uds_adam_tensor_t *tensors, int64_t n_tensors, const float *loss, double lr, double beta_1, double beta_2,
                   double epsilon, double clipnorm, int32_t *state, float *workspace, int64_t workspace_floats, uds_stream_t stream);
 
+/* A training batch of sliding windows on the device.  The reference builds every training batch on the host: sliding windows cut from the event series
+ * (dataloader.py:93-95,144-169), one random batch of them per epoch (DataGenerator.prepare_batch, dataloader.py:106-143), five
+ * normalisations and the uploads (main.py:209-232).  Here the series stay on the device, time-major, all events concatenated
+ * into Ttot rows: states (Ttot, N, 4) = [h, q_totin, q_ds, r], flood (Ttot, N) >= 0, edge_states (Ttot, E, 4) = [depth, volume,
+ * flow, setting], settings (Ttot, n_act) or NULL (n_act = 0), tide (Ttot, N) or NULL.
+ *
+ * uds_window_batch fills the six tensors of B windows in ONE launch.  The window at start s = starts[w] (device int32) covers
+ * rows s .. s + seq_in + t_out - 1; with cx = if_flood ? 5 : 4 and cb = tide ? 2 : 1:
+ *   x  (B, seq_in, N, cx)  row s + t:           [h, q_totin - r, q_ds, (flood > 0 ? 1 : 0, with if_flood), r]
+ *   b  (B, t_out, N, cb)   row s + seq_in + t:  [r, (tide)]
+ *   y  (B, t_out, N, cx)   row s + seq_in + t:  [h, q_totin - r, q_ds, (flood bit), flood]
+ *   ex (B, seq_in, E, 4)   row s + t            ey (B, t_out, E, 3)  row s + seq_in + t, the first three link channels
+ *   a  (B, t_out, n_act)   row s + seq_in + t of settings, never normalised (NULL exactly when n_act = 0)
+ * norm (NULL = everything raw): device (span, min) pairs, span = max - min formed by the caller: x (N, cx), b (N, cb), y (N, cx),
+ * e (E, 4) (ey uses its first three channels); a NULL pair leaves that tensor raw.  Each value becomes (v - min) / span with a
+ * correctly rounded division (Emulator.normalize).  A window with s < 0 or s + seq_in + t_out > Ttot reads nothing and gets
+ * EVERY output element set to NaN -- starts are device values the host cannot check; whether a window stays inside one event
+ * is the caller's business.  Series and outputs 16-byte aligned; all offsets are 64-bit.  No allocation, no copy, no
+ * synchronisation, no host read of a device value (safe inside a stream capture). */
+typedef struct {
+  const float *states, *flood, *edge_states, *settings, *tide;
+  int64_t Ttot, N, E, n_act;
+} uds_window_series_t;
+typedef struct {
+  const float *span_x, *min_x, *span_b, *min_b, *span_y, *min_y, *span_e, *min_e;
+} uds_window_norm_t;
+int uds_window_batch(const uds_window_series_t *series, const uds_window_norm_t *norm, const int32_t *starts, int64_t B, int64_t seq_in,
+                     int64_t t_out, int if_flood, float *x, float *a, float *b, float *y, float *ex, float *ey, uds_stream_t stream);
+
+/* The random batch of DataGenerator.prepare_batch (dataloader.py:106-143, over the windows of dataloader.py:93-95,144-169; one
+ * draw per epoch and table in main.py:209-232), on the device: B (1 .. 4096) starts from a table of W windows with integer
+ * weights.  Draw i of the call has the index j = *count + i and takes Philox4x32-10 (as uds_dropout) with key = seed, counter =
+ * (j, 0), r = word0 << 32 | word1, u = (r * total) >> 64 with total = cum[W - 1]; out[i] = starts_table[k] for the smallest k
+ * with cum[k] > u (cum: the inclusive 64-bit prefix sums of the weights, device).  A second one-thread launch on the same stream
+ * then sets *count += B (count: one device uint64), so no thread reads count after it moved.  All integer arithmetic.  No
+ * allocation, no copy, no synchronisation, no host read of a device value (safe inside a stream capture). */
+int uds_window_draw(const int32_t *starts_table, const uint64_t *cum, int64_t W, int64_t B, uint64_t seed, uint64_t *count, int32_t *out,
+                    uds_stream_t stream);
+
 /* Which launches a fused spatial layer makes (host-only bookkeeping: neither entry touches a device).
  *
  * The snapshots of a launch are cut into chunks and one workgroup handles one (tile, chunk) pair: *chunk = the chunk
