@@ -23,6 +23,7 @@ GeneralConv (a sparse-mode-only Spektral layer the reference's dense call cannot
 baseline, its shipped `*_nncat_*` models -- runs on the same Dense / temporal / cumsum kernels (`_forward_mlp`).
 """
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -57,6 +58,11 @@ class Conv1D(nn.Module):
             return _lib.rowgemm_forward(x, _packed_kernel(self, self.kernel.reshape(k * f, h)), self.bias, h, self.activation,
                                         taps=k, dilation=self.dilation_rate)
         return _lib.conv1d_causal(x, self.kernel, self.bias, self.dilation_rate, self.activation)
+
+
+# what `Emulator.temporal_route` reads of a temporal layer: is it a Conv1D, its kernel shape (k0, k1, k2), dilation and activation
+# (None for GRU / LSTM), precision, output width
+TemporalLayer = namedtuple('TemporalLayer', 'conv1d kernel dilation activation precision out')
 
 
 class _DenseShim:
@@ -156,16 +162,8 @@ class LSTM(_Recurrent):
     KIND, G = 'LSTM', 4
 
 
-class KerasAdam:
-    """keras.optimizers.Adam(learning_rate, clipnorm) as TF 2.10 applies it (emulator.py:111): every gradient is clipped
-    by ITS OWN norm (tf.clip_by_norm), then m, v are updated and var -= lr * sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + 1e-7)."""
-
-    def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None):
-        self.params = list(params)
-        self.lr, self.b1, self.b2, self.eps, self.clipnorm = learning_rate, beta_1, beta_2, epsilon, clipnorm
-        self.t = 0
-        self.m = [torch.zeros_like(p) for p in self.params]
-        self.v = [torch.zeros_like(p) for p in self.params]
+class _AdamState:
+    """The checkpoint format `KerasAdam` and `HipKerasAdam` share: one written by either loads into the other."""
 
     def state_dict(self):
         """Iteration count + first / second moments (what `optimizer.get_weights()` holds in Keras, emulator.py:826)."""
@@ -179,6 +177,18 @@ class KerasAdam:
             dst.copy_(src)
         for dst, src in zip(self.v, sd['v']):
             dst.copy_(src)
+
+
+class KerasAdam(_AdamState):
+    """keras.optimizers.Adam(learning_rate, clipnorm) as TF 2.10 applies it (emulator.py:111): every gradient is clipped
+    by ITS OWN norm (tf.clip_by_norm), then m, v are updated and var -= lr * sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + 1e-7)."""
+
+    def __init__(self, params, learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=None):
+        self.params = list(params)
+        self.lr, self.b1, self.b2, self.eps, self.clipnorm = learning_rate, beta_1, beta_2, epsilon, clipnorm
+        self.t = 0
+        self.m = [torch.zeros_like(p) for p in self.params]
+        self.v = [torch.zeros_like(p) for p in self.params]
 
     @torch.no_grad()
     def step(self):
@@ -203,7 +213,7 @@ class KerasAdam:
         torch._foreach_addcdiv_(ps, ms, den, value=-lr_t)
 
 
-class HipKerasAdam:
+class HipKerasAdam(_AdamState):
     """`KerasAdam` as ONE HIP operator (uds_adam_step: per-variable norms, clipping, moments and update in two passes over the
     whole parameter list) with the step count and a status word on the device, so that a captured graph can replay a step:
     nothing per step is computed on the host.  Same constructor and the same `state_dict` format as `KerasAdam` (a checkpoint
@@ -226,18 +236,6 @@ class HipKerasAdam:
     @t.setter
     def t(self, value):
         self.state[0] = int(value)
-
-    def state_dict(self):
-        return {'t': self.t, 'm': [t.detach().cpu() for t in self.m], 'v': [t.detach().cpu() for t in self.v]}
-
-    def load_state_dict(self, sd):
-        if len(sd['m']) != len(self.params) or any(tuple(a.shape) != tuple(p.shape) for a, p in zip(sd['m'], self.params)):
-            raise ValueError('optimizer state does not match the model parameters')
-        self.t = int(sd['t'])
-        for dst, src in zip(self.m, sd['m']):
-            dst.copy_(src)
-        for dst, src in zip(self.v, sd['v']):
-            dst.copy_(src)
 
     @torch.no_grad()
     def step(self, loss=None):
@@ -444,6 +442,8 @@ class Emulator(nn.Module):
         d, h, H, L, gen = self.embed_size, self.embed_size // 2, self.hidden_dim, self.n_sp_layer, generator
         a = self.activation
         pr = precision
+        if not (self.recurrent in ('Conv1D', 'GRU', 'LSTM') and self.n_tp_layer):
+            H = d                                                                               # no temporal net: widths stay d
         if not self.conv:
             self._build_mlp(d, h, H, L, a, gen, pr)
             return
@@ -462,20 +462,7 @@ class Emulator(nn.Module):
             self.block1 = SpatialBlock(self.graph, d, L, a, sparse_params=sp, generator=gen, precision=precision,
                                        conv=self.conv_kind, filters=(self.filter, self.edge_filter),
                                        attn_heads=self.attn_heads)                                                    # :219-235
-        rec = self.recurrent if self.recurrent in ('Conv1D', 'GRU', 'LSTM') else None              # get_tem_nets, :154-163
-
-        def tem(f):
-            if rec == 'Conv1D':
-                mods = [Conv1D(H, self.kernel_size, 2 ** i, a, in_features=(f if i == 0 else H), generator=gen, precision=pr)
-                        for i in range(self.n_tp_layer)]
-            elif rec:
-                mods = [(GRU if rec == 'GRU' else LSTM)(H, in_features=(f if i == 0 else H), generator=gen, precision=pr) for i in range(self.n_tp_layer)]
-            else:
-                mods = []                                                                       # no temporal net: widths stay d
-            return nn.ModuleList(mods)
-        if not (rec and self.n_tp_layer):
-            H = d
-        self.tem1_x, self.tem1_e = tem(d), tem(d)                                               # :247,254
+        self.tem1_x, self.tem1_e = self._tem_net(d, H, gen, pr), self._tem_net(d, H, gen, pr)     # :247,254
         fx2, fe2 = H + h, H + (h if self.act else 0)
         if self.graph_base:
             if fx2 != fe2:
@@ -486,17 +473,30 @@ class Emulator(nn.Module):
             self.block2 = SpatialBlock(self.graph, d, L, a, fx=fx2, fe=fe2, sparse_params=sp, generator=gen, precision=precision,
                                        conv=self.conv_kind, filters=(self.filter, self.edge_filter),
                                        attn_heads=self.attn_heads)                                                    # :272-288
-        self.tem2_x, self.tem2_e = tem(d), tem(d)                                               # :302,308
+        self.tem2_x, self.tem2_e = self._tem_net(d, H, gen, pr), self._tem_net(d, H, gen, pr)     # :302,308
+        self._build_heads(d, h, H, a, gen, pr)
+
+    def _tem_net(self, f, H, gen, pr):
+        """`get_tem_nets` (:154-163) on an f-wide input: n_tp_layer causal Conv1D layers with dilation 2**i, or GRU / LSTM layers."""
+        def layer(i):
+            fi = f if i == 0 else H
+            if self.recurrent == 'Conv1D':
+                return Conv1D(H, self.kernel_size, 2 ** i, self.activation, in_features=fi, generator=gen, precision=pr)
+            return (GRU if self.recurrent == 'GRU' else LSTM)(H, in_features=fi, generator=gen, precision=pr)
+        return nn.ModuleList([layer(i) for i in range(self.n_tp_layer if self.recurrent in ('Conv1D', 'GRU', 'LSTM') else 0)])
+
+    def _build_heads(self, d, h, H, a, gen, pr, N=1, E=1):
+        """The output stage (:313-337).  N, E: the MLP model's heads emit all nodes / links of a step at once."""
         self.res_x = Dense(d, 'linear' if self.resnet else a, in_features=H, generator=gen, precision=pr)     # :313 'dense_resx'
         self.res_e = Dense(d, 'linear' if self.resnet else a, in_features=H, generator=gen, precision=pr)     # :317
-        self.out = Dense(self.n_out, 'hard_sigmoid', in_features=d, generator=gen, precision=pr)              # :324
+        self.out = Dense(self.n_out * N, 'hard_sigmoid', in_features=d, generator=gen, precision=pr)          # :322-325
         fl, fi = [], d
         for _ in range(self.if_flood):
             fl.append(Dense(h, a, in_features=fi, generator=gen, precision=pr))                               # :329
             fi = h
         self.flood = nn.ModuleList(fl)
-        self.flood_out = Dense(1, 'sigmoid', in_features=fi, generator=gen, precision=pr) if self.if_flood else None      # :330
-        self.e_out_layer = Dense(self.e_out, 'tanh', in_features=d, generator=gen, precision=pr)              # :336
+        self.flood_out = Dense(N, 'sigmoid', in_features=fi, generator=gen, precision=pr) if self.if_flood else None      # :327-330
+        self.e_out_layer = Dense(self.e_out * E, 'tanh', in_features=d, generator=gen, precision=pr)          # :335-337
 
     @property
     def snapshot_remainder(self):
@@ -572,49 +572,18 @@ class Emulator(nn.Module):
         self.embed_b = Dense(h, a, in_features=N * self.b_in, generator=gen)                    # :202-203
         self.embed_e = Dense(d, 'linear', in_features=E * self.e_in, generator=gen)             # :205-206
         self.embed_ae = Dense(h, a, in_features=E, generator=gen) if self.act else None         # :211-212
-        rec = self.recurrent if self.recurrent in ('Conv1D', 'GRU', 'LSTM') else None
-
-        def tem(f):
-            if rec == 'Conv1D':
-                return nn.ModuleList([Conv1D(H, self.kernel_size, 2 ** i, a, in_features=(f if i == 0 else H), generator=gen, precision=pr)
-                                      for i in range(self.n_tp_layer)])
-            if rec:
-                return nn.ModuleList([(GRU if rec == 'GRU' else LSTM)(H, in_features=(f if i == 0 else H), generator=gen, precision=pr)
-                                      for i in range(self.n_tp_layer)])
-            return nn.ModuleList([])
-        if not (rec and self.n_tp_layer):
-            H = d
         self.block1 = nn.ModuleList([Dense(2 * d, a, in_features=2 * d, generator=gen, precision=pr) for _ in range(L)])          # :236-237
-        self.tem1_x, self.tem1_e = tem(d), tem(d)
+        self.tem1_x, self.tem1_e = self._tem_net(d, H, gen, pr), self._tem_net(d, H, gen, pr)
         f2 = (H + h) + (H + (h if self.act else 0))
         self.block2 = nn.ModuleList([Dense(2 * d, a, in_features=(f2 if i == 0 else 2 * d), generator=gen, precision=pr) for i in range(L)])
-        self.tem2_x, self.tem2_e = tem(d), tem(d)
-        self.res_x = Dense(d, 'linear' if self.resnet else a, in_features=H, generator=gen, precision=pr)     # :313
-        self.res_e = Dense(d, 'linear' if self.resnet else a, in_features=H, generator=gen, precision=pr)     # :317
-        self.out = Dense(self.n_out * N, 'hard_sigmoid', in_features=d, generator=gen, precision=pr)          # :322-325
-        fl, fi = [], d
-        for _ in range(self.if_flood):
-            fl.append(Dense(h, a, in_features=fi, generator=gen, precision=pr))
-            fi = h
-        self.flood = nn.ModuleList(fl)
-        self.flood_out = Dense(N, 'sigmoid', in_features=fi, generator=gen, precision=pr) if self.if_flood else None      # :327-330
-        self.e_out_layer = Dense(self.e_out * E, 'tanh', in_features=d, generator=gen, precision=pr)          # :335-337
+        self.tem2_x, self.tem2_e = self._tem_net(d, H, gen, pr), self._tem_net(d, H, gen, pr)
+        self._build_heads(d, h, H, a, gen, pr, N, E)
 
-    def _forward_mlp(self, X, B, E, AE=None, training=False):
-        nb, T = X.shape[0], self.seq_out
-        drop = bool(self.dropout) and training
-        d02 = (lambda t: self._drop02(t, True)) if drop else (lambda t: t)
+    def _forward_mlp(self, X, B, E, AE, drop):
+        T = self.seq_out
         dr = (lambda t: self._drop(t, True)) if drop else (lambda t: t)
         flat = lambda t: t.reshape(t.shape[0], t.shape[1], 1, -1).contiguous()        # (B, T, N, c) -> one row of N * c per step
-        xl = d02(self.embed_x(flat(X), 'linear'))                                     # masks drawn in the reference's order x, b, e, ae
-        b = d02(self.embed_b(flat(B)))
-        el = d02(self.embed_e(flat(E), 'linear'))
-        ae = d02(self.embed_ae(flat(AE))) if self.act else None
-        x_lin_last, e_lin_last = xl[:, -1:].contiguous(), el[:, -1:].contiguous()
-        if drop:      # the activation follows the dropout (:199-201)
-            x, e = _ag.apply_activation(xl, self.activation), _ag.apply_activation(el, self.activation)
-        else:
-            x, e = self.embed_x(flat(X), self.activation), self.embed_e(flat(E), self.activation)
+        x, e, b, ae, x_lin_last, e_lin_last = self._embed(X, B, E, AE, drop, flat)
 
         def spatial(layers, x, e):
             for ly in layers:
@@ -622,33 +591,15 @@ class Emulator(nn.Module):
                 x, e = dr(z[..., :z.shape[-1] // 2].contiguous()), dr(z[..., z.shape[-1] // 2:].contiguous())
             return x, e
 
-        def chain(mods, t):
-            for ly in mods:
-                t = ly(t)
-            return t
-
         x, e = spatial(self.block1, x, e)
-        x, e = chain(self.tem1_x, x)[:, -T:], chain(self.tem1_e, e)[:, -T:]
-        x = torch.cat([x, b], dim=-1)                                                 # :260
-        if self.act:
-            e = torch.cat([e, ae], dim=-1)                                            # :262
+        x, e = self._temporal(self.tem1_x, self.tem1_e, x, e, mlp=True)
+        x = torch.cat([x[:, -T:], b], dim=-1)                                         # :260
+        e = torch.cat([e[:, -T:], ae], dim=-1) if self.act else e[:, -T:]             # :262
         x, e = spatial(self.block2, x, e)
-        x, e = chain(self.tem2_x, x), chain(self.tem2_e, e)
-
-        def res_head(layer, t, lin_last):
-            y = dr(layer(t))                                                          # :314,318
-            if not self.resnet:
-                return y
-            if _ag.grad_on(y, lin_last):
-                return _ag.CumsumActFn.apply(y, lin_last, self.activation)
-            return _lib.cumsum_act(y.contiguous(), lin_last.contiguous(), self.activation)
-
-        x, e = res_head(self.res_x, x, x_lin_last), res_head(self.res_e, e, e_lin_last)
-        out = self.out(x).reshape(nb, T, self.n_node, self.n_out)                     # :322-325
-        if self.if_flood:
-            flood = self.flood_out(chain(self.flood, x)).reshape(nb, T, self.n_node, 1)
-            out = torch.cat([out, flood], dim=-1)
-        return out, self.e_out_layer(e).reshape(nb, T, self.n_edge, self.e_out)
+        x, e = self._temporal(self.tem2_x, self.tem2_e, x, e, mlp=True)
+        pgrad = _ag.grad_on(*self.parameters())
+        return (self._output(x, x_lin_last, self.res_x, self.out, list(self.flood), self.flood_out, drop, pgrad, self.n_node),     # :313-333
+                self._output(e, e_lin_last, self.res_e, self.e_out_layer, [], None, drop, pgrad, self.n_edge))                     # :317-337
 
     # ------------------------------------------------------------------ network forward (build_network)
     def attention_coefficients(self, X, B, E, AE=None, ADJ=None):
@@ -672,35 +623,19 @@ class Emulator(nn.Module):
         """ADJ: the per-time-step node adjacency of `use_adj` (emulator.py:178-180,268-271; block 2 only): the edge mask
         (B, T_out, nnz) of `get_adj_action`, or the reference's dense (B, T_out, n, n) integer array (small networks).
         training: keras' `training=` flag -- switches the Dropout layers on when the model was built with `dropout` > 0."""
-        if not self.conv:
-            return self._forward_mlp(X, B, E, AE, training)
         drop = bool(self.dropout) and training
-        d02 = (lambda t: self._drop02(t, True)) if drop else (lambda t: t)
+        self.last_temporal_route, self.last_head_route = [], []
+        if not self.conv:
+            return self._forward_mlp(X, B, E, AE, drop)
         dr = (lambda t: self._drop(t, True)) if drop else None
         nb = X.shape[0]
         c = lambda t: t.contiguous()
-        self.last_temporal_path = 'layers'
         adj_mask = None
         if ADJ is not None:
             if not (self.act and self.use_adj):
                 raise ValueError('ADJ given but the model was built without act + use_adj')
             adj_mask = self._adj_mask_from(ADJ, X.device).reshape(nb * self.seq_out, -1)
-        # the embedding is linear, its last step is kept as the residual, then the activation is applied (:198-201):
-        # two launches of the same GEMM (same per-row arithmetic), one with and one without the activation
-        if drop:      # Dense(linear) -> Dropout(0.2) -> residual slice -> activation (:198-201,206-209); masks drawn in the reference's order x, b, e, ae
-            xl = d02(self.embed_x(c(X), 'linear'))
-            b = d02(self.embed_b(c(B)))
-            el = d02(self.embed_e(c(E), 'linear'))
-            ae = d02(self.embed_ae(c(AE))) if self.act else None
-            x_lin_last, e_lin_last = c(xl[:, -1:]), c(el[:, -1:])
-            x, e = _ag.apply_activation(xl, self.activation), _ag.apply_activation(el, self.activation)
-        else:
-            x_lin_last = self.embed_x(c(X[:, -1:]), 'linear')
-            x = self.embed_x(c(X), self.activation)
-            e_lin_last = self.embed_e(c(E[:, -1:]), 'linear')
-            e = self.embed_e(c(E), self.activation)
-            b = self.embed_b(c(B))
-            ae = self.embed_ae(c(AE)) if self.act else None
+        x, e, b, ae, x_lin_last, e_lin_last = self._embed(X, B, E, AE, drop, c)
 
         def spatial(block, x, e, xb=None, eb=None, mask=None):
             T = x.shape[1]
@@ -719,102 +654,198 @@ class Emulator(nn.Module):
                 sink['block1' if block is self.block1 else 'block2'] = [bt(a) if isinstance(a, torch.Tensor) else (bt(a[0]), bt(a[1])) for a in got]
             return xs.reshape(nb, T, self.n_node, -1), es.reshape(nb, T, self.n_edge, -1)
 
-        def stack(mods, t):
-            """One side's temporal stack as ONE launch (uds_conv_stack_forward: the layers in between never reach memory), or None
-            when it is not the shape that kernel takes: two or three Conv1D(64 -> 64, kernel 3) layers with dilations 1, 2[, 4],
-            one activation, the matrix-core precision, no gradient, and enough 16-row streams to fill the device."""
-            mods = list(mods)
-            if not (self.fused_temporal and len(mods) in (2, 3) and t.shape[-1] == 64 and all(isinstance(m, Conv1D) for m in mods)):
-                return None
-            if not all(tuple(m.kernel.shape) == (3, 64, 64) and m.dilation_rate == 2 ** i and m.activation == mods[0].activation
-                       and m.precision == 'bf16x3' for i, m in enumerate(mods)):
-                return None
-            if t.shape[0] * ((t.shape[2] + 15) // 16) < self.STACK_MIN_STREAMS or _ag.grad_on(t, *[p for m in mods for p in (m.kernel, m.bias)]):
-                return None
-            return _lib.conv_stack_forward(c(t), [(_packed_kernel(m, m.kernel.reshape(192, 64)), m.bias) for m in mods], mods[0].activation)
-
-        def temporal(mods_x, mods_e, x, e):
-            """The two temporal stacks (:244-257): layer by layer; a pair of small Conv1D layers of one shape goes out as ONE launch.
-            With `fused_temporal`, a side's whole stack is one launch where `stack` takes it (same bits as its layers)."""
-            sx, se = stack(mods_x, x), stack(mods_e, e)
-            if sx is not None or se is not None:
-                self.last_temporal_path = 'stack'
-                if sx is None:
-                    for ly in mods_x:
-                        x = ly(x)
-                if se is None:
-                    for ly in mods_e:
-                        e = ly(e)
-                return (x if sx is None else sx), (e if se is None else se)
-            if len(mods_x) != len(mods_e):
-                for ly in mods_x:
-                    x = ly(x)
-                for ly in mods_e:
-                    e = ly(e)
-                return x, e
-            for lx, le in zip(mods_x, mods_e):
-                kx = lx.kernel.shape if isinstance(lx, Conv1D) else None
-                if (kx is not None and isinstance(le, Conv1D) and le.kernel.shape == kx and lx.dilation_rate == le.dilation_rate
-                        and lx.activation == le.activation and lx.precision == le.precision == 'bf16x3' and x.shape[-1] == e.shape[-1] == kx[1]
-                        and _lib.rowgemm_supported(kx[0] * kx[1], kx[1], kx[2]) and x.shape[0] * x.shape[1] * max(x.shape[2], e.shape[2]) <= 16384
-                        and kx[0] * kx[1] // 32 in (2, 6) and not _ag.grad_on(x, e, lx.kernel, le.kernel, lx.bias, le.bias)):
-                    x, e = _lib.rowgemm_forward_pair(c(x), _packed_kernel(lx, lx.kernel.reshape(kx[0] * kx[1], kx[2])), lx.bias,
-                                                     c(e), _packed_kernel(le, le.kernel.reshape(kx[0] * kx[1], kx[2])), le.bias, kx[2],
-                                                     lx.activation, taps=kx[0], dilation=lx.dilation_rate)
-                else:
-                    x, e = lx(x), le(e)
-            return x, e
-
         x, e = spatial(self.block1, x, e)
-        x, e = temporal(self.tem1_x, self.tem1_e, x, e)
+        x, e = self._temporal(self.tem1_x, self.tem1_e, x, e)
         x, e = x[:, -self.seq_out:], e[:, -self.seq_out:]             # :249,256
         # concat([x, b]) / concat([e, ae]) (:260-262) are not materialised: the first layer of block 2 reads both pieces
         x, e = spatial(self.block2, c(x), c(e), b, ae if self.act else None, adj_mask)
-        x, e = temporal(self.tem2_x, self.tem2_e, x, e)
-        def res_head(layer, t, lin_last):                             # :313-320
-            if drop:
-                y = dr(layer(t))
-                return _ag.CumsumActFn.apply(y, lin_last, self.activation) if self.resnet else y
-            if not self.resnet:
-                return layer(t)
-            if (layer.precision == 'bf16x3' and layer.units == 64 and t.shape[-1] == 64 and t.shape[0] * t.shape[2] >= 4096
-                    and not _ag.grad_on(t, lin_last, layer.kernel, layer.bias)):
-                # Dense + cumsum over time + residual + activation in one streaming kernel
-                return _lib.dense_cumsum(c(t), _packed_kernel(layer, layer.kernel), layer.bias, c(lin_last), self.activation)
-            y = layer(t)
-            if _ag.grad_on(y, lin_last):
-                return _ag.CumsumActFn.apply(y, lin_last, self.activation)
-            return _lib.cumsum_act(y, lin_last, self.activation)
-
-        def fused_heads(layer, t, lin_last, head, hidden, head_f):
-            """Dense + cumsum + residual + activation with the output heads as the epilogue of the same streaming kernel (the 64-wide
-            resnet output never reaches memory); None when the shape or mode is not the one that kernel takes."""
-            pk = lambda m: _packed_kernel(m, m.kernel)
-            ok = (self.resnet and layer.precision == 'bf16x3' and layer.units == 64 and t.shape[-1] == 64 and head.units <= 4
-                  and len(hidden) <= 5 and all(m.units == 32 for m in hidden) and (not hidden or hidden[0].kernel.shape[0] == 64)
-                  and not drop and not _ag.grad_on(t, lin_last, *self.parameters()))
-            if not ok:
-                return None
-            return _lib.dense_cumsum_heads(
-                c(t), pk(layer), layer.bias, c(lin_last), self.activation, (pk(head), head.bias, head.units, head.activation),
-                [(pk(m), m.bias) for m in hidden],
-                (pk(head_f), head_f.bias, head_f.activation, hidden[0].activation) if hidden else None)
-
-        out = fused_heads(self.res_x, x, x_lin_last, self.out, list(self.flood), self.flood_out)
-        e_out = fused_heads(self.res_e, e, e_lin_last, self.e_out_layer, [], None)
-        if out is None:
-            x = res_head(self.res_x, x, x_lin_last)
-            out = self.out(x)
-            if self.if_flood:
-                f = x
-                for ly in self.flood:
-                    f = ly(f)
-                out = torch.cat([out, self.flood_out(f)], dim=-1)     # :330-333
-        if e_out is None:
-            e_out = self.e_out_layer(res_head(self.res_e, e, e_lin_last))
-        return out, e_out
+        x, e = self._temporal(self.tem2_x, self.tem2_e, x, e)
+        pgrad = _ag.grad_on(*self.parameters())
+        return (self._output(x, x_lin_last, self.res_x, self.out, list(self.flood), self.flood_out, drop, pgrad),     # :313-333
+                self._output(e, e_lin_last, self.res_e, self.e_out_layer, [], None, drop, pgrad))                     # :317-337
 
     model = forward
+
+    def _embed(self, X, B, E, AE, drop, prep):
+        """The four embeddings (:197-212) -> x, e, b, ae and the last linear step of x and e (the resnet residual).  prep: what
+        makes a Dense input of a tensor (contiguous; the MLP model flattens a step into one row)."""
+        if drop:      # Dense(linear) -> Dropout(0.2) -> residual slice -> activation (:198-201,206-209); masks drawn in the reference's order x, b, e, ae
+            xl = self._drop02(self.embed_x(prep(X), 'linear'), True)
+            b = self._drop02(self.embed_b(prep(B)), True)
+            el = self._drop02(self.embed_e(prep(E), 'linear'), True)
+            ae = self._drop02(self.embed_ae(prep(AE)), True) if self.act else None
+            x_lin_last, e_lin_last = xl[:, -1:].contiguous(), el[:, -1:].contiguous()
+            return _ag.apply_activation(xl, self.activation), _ag.apply_activation(el, self.activation), b, ae, x_lin_last, e_lin_last
+        # the embedding is linear, its last step is kept as the residual, then the activation is applied (:198-201):
+        # two launches of the same GEMM (same per-row arithmetic), one with and one without the activation
+        x_lin_last = self.embed_x(prep(X[:, -1:]), 'linear')
+        x = self.embed_x(prep(X), self.activation)
+        e_lin_last = self.embed_e(prep(E[:, -1:]), 'linear')
+        e = self.embed_e(prep(E), self.activation)
+        return x, e, self.embed_b(prep(B)), self.embed_ae(prep(AE)) if self.act else None, x_lin_last, e_lin_last
+
+    # ------------------------------------------------------------------ the temporal stage: route, then one method per route
+    fused_temporal = False     # True: a side's Conv1D stack goes out as ONE uds_conv_stack_forward launch where `temporal_route` says 'stack'
+    STACK_MIN_STREAMS = 256    # (batch element, 16-row block) streams below which the layers stay (they leave k_conv3_stream there too)
+    last_temporal_route = None  # after a forward: [stage 1, stage 2], each what `temporal_route` returned
+    last_temporal_path = None  # ... and its summary: 'stack' (a side took the one-launch kernel) or 'layers'
+    TEMPORAL_ROUTES = {'stack': '_tem_stack', 'pair': '_tem_pair', 'layers': '_tem_layers'}
+
+    @staticmethod
+    def temporal_layer(m):
+        """What `temporal_route` reads of one temporal layer."""
+        if isinstance(m, Conv1D):
+            return TemporalLayer(True, tuple(m.kernel.shape), m.dilation_rate, m.activation, m.precision, m.filters)
+        return TemporalLayer(False, None, None, None, m.precision, m.units)
+
+    def temporal_route(self, B, T, N, E, fx, fe, layers_x, layers_e, rowgemm_supported, grad_x=(), grad_e=(), mlp=False):
+        """Which kernels the two stacks of one temporal stage (:244-257) run -> ('sides', (key of the node stack, key of the link
+        stack)) or ('pairs', (one key per layer index)), keys of TEMPORAL_ROUTES.  Plain values in, no tensor, no launch, no side
+        effect: the stacks read (B, T, N, fx) and (B, T, E, fe); layers_x / layers_e: one `TemporalLayer` per layer;
+        rowgemm_supported: `_lib.rowgemm_supported`; grad_x / grad_e: whether autograd records for the stack input ([0]) and for a
+        parameter of layer i ([i + 1]) -- "grad" at a layer is any of these up to its own.  First match wins:
+
+          0   the MLP model (conv False: one row per step)                                         sides: layers, layers
+          1   per side: fused_temporal, 2 or 3 layers, all Conv1D with kernel (3, 64, 64) on a 64-wide input, dilation 2**i at
+              layer i, one activation, all bf16x3, B * ceil(rows / 16) >= STACK_MIN_STREAMS, no grad at any layer
+                                                                                                   sides: stack there
+          2   a side of row 1 next to one that is not                                              sides: layers on the other
+          3   stacks of different lengths                                                          sides: layers, layers
+          4   per layer index: both Conv1D of one kernel shape (k0, k1, k2), dilation and activation, both bf16x3, both inputs
+              k1 wide, rowgemm_supported(k0 * k1, k1, k2), B * T * max(N, E) <= 16384, k0 * k1 // 32 in (2, 6), no grad at
+              this layer on either side                                                            pairs: pair at that index
+          5   every other layer index                                                              pairs: layers
+
+        'stack' is uds_conv_stack_forward and 'pair' uds_rowgemm_forward_pair: each gives the bits of the layers it replaces."""
+        if mlp:
+            return 'sides', ('layers', 'layers')
+
+        def stack(rows, f, layers, grad):
+            return (self.fused_temporal and len(layers) in (2, 3) and f == 64 and all(ly.conv1d for ly in layers) and
+                    all(ly.kernel == (3, 64, 64) and ly.dilation == 2 ** i and ly.activation == layers[0].activation and
+                        ly.precision == 'bf16x3' for i, ly in enumerate(layers)) and
+                    B * ((rows + 15) // 16) >= self.STACK_MIN_STREAMS and not any(grad))
+        sides = tuple('stack' if stack(*side) else 'layers' for side in ((N, fx, layers_x, grad_x), (E, fe, layers_e, grad_e)))
+        if 'stack' in sides or len(layers_x) != len(layers_e):
+            return 'sides', sides
+        keys = []
+        for i, (lx, le) in enumerate(zip(layers_x, layers_e)):
+            k = lx.kernel
+            pair = (lx.conv1d and le.conv1d and le.kernel == k and lx.dilation == le.dilation and lx.activation == le.activation and
+                    lx.precision == le.precision == 'bf16x3' and fx == fe == k[1] and rowgemm_supported(k[0] * k[1], k[1], k[2]) and
+                    B * T * max(N, E) <= 16384 and k[0] * k[1] // 32 in (2, 6) and not any(grad_x[:i + 2]) and not any(grad_e[:i + 2]))
+            keys.append('pair' if pair else 'layers')
+            fx, fe = lx.out, le.out
+        return 'pairs', tuple(keys)
+
+    def _temporal(self, mods_x, mods_e, x, e, mlp=False):
+        """One temporal stage: asks `temporal_route` once, runs what it says and records it."""
+        grads = lambda t, mods: (_ag.grad_on(t),) + tuple(_ag.grad_on(*m.parameters()) for m in mods)
+        route = form, keys = self.temporal_route(
+            x.shape[0], x.shape[1], x.shape[2], e.shape[2], x.shape[-1], e.shape[-1], [self.temporal_layer(m) for m in mods_x],
+            [self.temporal_layer(m) for m in mods_e], _lib.rowgemm_supported, grads(x, mods_x), grads(e, mods_e), mlp)
+        self.last_temporal_route.append(route)
+        self.last_temporal_path = 'stack' if any('stack' in k for _, k in self.last_temporal_route) else 'layers'
+        if form == 'sides':
+            return getattr(self, self.TEMPORAL_ROUTES[keys[0]])(mods_x, x), getattr(self, self.TEMPORAL_ROUTES[keys[1]])(mods_e, e)
+        for key, lx, le in zip(keys, mods_x, mods_e):
+            x, e = self._tem_pair(lx, le, x, e) if key == 'pair' else (self._tem_layers([lx], x), self._tem_layers([le], e))
+        return x, e
+
+    def _tem_layers(self, mods, t):
+        for ly in mods:
+            t = ly(t)
+        return t
+
+    def _tem_stack(self, mods, t):
+        """One side's stack as ONE launch: the layers in between never reach memory."""
+        return _lib.conv_stack_forward(t.contiguous(), [(_packed_kernel(m, m.kernel.reshape(192, 64)), m.bias) for m in mods], mods[0].activation)
+
+    def _tem_pair(self, lx, le, x, e):
+        """Two small Conv1D layers of one shape, one per side, as ONE launch."""
+        k0, k1, k2 = lx.kernel.shape
+        return _lib.rowgemm_forward_pair(x.contiguous(), _packed_kernel(lx, lx.kernel.reshape(k0 * k1, k2)), lx.bias,
+                                         e.contiguous(), _packed_kernel(le, le.kernel.reshape(k0 * k1, k2)), le.bias, k2,
+                                         lx.activation, taps=k0, dilation=lx.dilation_rate)
+
+    # ------------------------------------------------------------------ the output stage: route, then one method per route
+    last_head_route = None     # after a forward: [node side, link side], each a key of HEAD_ROUTES
+    HEAD_ROUTES = {'heads': '_head_fused', 'dropout': '_head_dropout', 'plain': '_head_plain', 'dense-cumsum': '_head_dense_cumsum',
+                   'cumsum': '_head_cumsum'}
+
+    def head_route(self, B, rows, res, head_units, hidden, drop=False, grad_any=False, grad_own=False, mlp=False):
+        """Which kernels one side of the output stage (:313-337) runs -> a key of HEAD_ROUTES.  Plain values in, no tensor, no
+        launch, no side effect: the side reads (B, T, rows, F); res: (precision, units, F) of its res layer; head_units: units of
+        its first head; hidden: [(units, input width)] of the layers between the res layer and its second head (the flood chain; none
+        on the link side); drop: dropout is active; grad_any: autograd records for the input, the residual or ANY parameter of the
+        model; grad_own: ... for the input, the residual or a parameter of the res layer.  First match wins:
+
+          1   resnet, res = (bf16x3, 64, 64), head_units <= 4, at most 5 hidden layers, all 32 units, the first 64 wide,
+              no dropout, no grad_any, not the MLP model                                           heads
+          2   dropout active: the layer, Dropout, CumsumActFn if resnet                           dropout
+          3   not resnet: the layer                                                                plain
+          4   res = (bf16x3, 64, 64), B * rows >= 4096, no grad_own, not the MLP model             dense-cumsum
+          5   the layer, then CumsumActFn under grad, else uds_cumsum_act                          cumsum
+
+        'heads' (uds_dense_cumsum_heads) also runs the side's heads; after every other route they are launches of their own.
+        The MLP model (one row per step, heads that emit all N or E outputs of a step) never takes 1 or 4."""
+        wide = tuple(res) == ('bf16x3', 64, 64)
+        if (not mlp and self.resnet and wide and head_units <= 4 and len(hidden) <= 5 and all(u == 32 for u, _ in hidden) and
+                (not hidden or hidden[0][1] == 64) and not drop and not grad_any):
+            return 'heads'
+        if drop:
+            return 'dropout'
+        if not self.resnet:
+            return 'plain'
+        if not mlp and wide and B * rows >= 4096 and not grad_own:
+            return 'dense-cumsum'
+        return 'cumsum'
+
+    def _output(self, t, lin_last, res, head, hidden, head_f, drop, pgrad, rows=None):
+        """One side of the output stage: asks `head_route` once, runs what it says and records it.  hidden, head_f: the flood
+        chain and its head ([] and None on the link side); pgrad: a parameter of the model needs a gradient; rows: N or E for the MLP
+        model, whose heads emit (B, T, 1, rows * c)."""
+        key = self.head_route(t.shape[0], t.shape[2], (res.precision, res.units, t.shape[-1]), head.units,
+                              [(m.units, m.kernel.shape[0]) for m in hidden], drop, pgrad or _ag.grad_on(t, lin_last),
+                              _ag.grad_on(t, lin_last, res.kernel, res.bias), rows is not None)
+        self.last_head_route.append(key)
+        run = getattr(self, self.HEAD_ROUTES[key])
+        if key == 'heads':
+            return run(res, t, lin_last, head, hidden, head_f)
+        t = run(res, t, lin_last)
+        view = (lambda o: o) if rows is None else (lambda o: o.reshape(o.shape[0], o.shape[1], rows, -1))      # :322-325
+        out = view(head(t))
+        if head_f is not None:
+            f = t
+            for ly in hidden:
+                f = ly(f)
+            out = torch.cat([out, view(head_f(f))], dim=-1)           # :330-333
+        return out
+
+    def _head_fused(self, res, t, lin_last, head, hidden, head_f):
+        """Dense + cumsum + residual + activation with the output heads as the epilogue of the same streaming kernel (the 64-wide
+        resnet output never reaches memory)."""
+        pk = lambda m: _packed_kernel(m, m.kernel)
+        return _lib.dense_cumsum_heads(
+            t.contiguous(), pk(res), res.bias, lin_last.contiguous(), self.activation, (pk(head), head.bias, head.units, head.activation),
+            [(pk(m), m.bias) for m in hidden], (pk(head_f), head_f.bias, head_f.activation, hidden[0].activation) if hidden else None)
+
+    def _head_dropout(self, res, t, lin_last):
+        y = self._drop(res(t), True)
+        return _ag.CumsumActFn.apply(y, lin_last, self.activation) if self.resnet else y
+
+    def _head_plain(self, res, t, lin_last):
+        return res(t)
+
+    def _head_dense_cumsum(self, res, t, lin_last):
+        """Dense + cumsum over time + residual + activation in one streaming kernel."""
+        return _lib.dense_cumsum(t.contiguous(), _packed_kernel(res, res.kernel), res.bias, lin_last.contiguous(), self.activation)
+
+    def _head_cumsum(self, res, t, lin_last):
+        y = res(t)
+        if _ag.grad_on(y, lin_last):
+            return _ag.CumsumActFn.apply(y, lin_last, self.activation)
+        return _lib.cumsum_act(y.contiguous(), lin_last.contiguous(), self.activation)
 
     # ------------------------------------------------------------------ normalisation (:794-810)
     def set_norm(self, norm_x, norm_b, norm_y, norm_r, norm_e):
@@ -1067,11 +1098,6 @@ class Emulator(nn.Module):
         q_w, y = self.constrain_tf(y, b[..., :1], x[:, -1:, :, 0])
         return torch.cat([y, q_w.unsqueeze(-1)], dim=-1), ey
 
-    # ------------------------------------------------------------------ a temporal stack as one launch
-    fused_temporal = False     # True: a side's Conv1D stack goes out as ONE uds_conv_stack_forward launch where `forward` finds its shape
-    STACK_MIN_STREAMS = 256    # (batch element, 16-row block) streams below which the layers stay (they leave k_conv3_stream there too)
-    last_temporal_path = None  # 'stack' (a side took the one-launch kernel) or 'layers' after a forward
-
     # ------------------------------------------------------------------ the predict tail as one HIP operator
     fused_tail = True         # False: `_predict` keeps its tensor code for everything after the forward
     last_tail_path = None      # 'hip', 'hip-train' (through autograd.PredictTailFn) or 'torch' after a predict_tf / predict call
@@ -1131,25 +1157,42 @@ class Emulator(nn.Module):
         self._norm_derived[key] = (ny, ne, (n_act, b_channels, ce), spec)
         return spec
 
+    def _tail_takes(self, device, B, T, ce, a, n_act):
+        """Do the tail kernels (uds_predict_tail, uds_fit_tail) take this model with `ce` link channels, settings `a` of
+        (B, T, n_act) and its norms on `device`?  Not a local model of `shard_emulator` (its flows cross the cut between the link
+        gates and the balance), 2 to 8 link channels, 'y' / 'e' norms of one row per node / link with the channels the kernels read,
+        and for an actuated model fp32 settings on the device of which every one drives its links (and, without edge fusion, its
+        two nodes): a fact of the model, looked up once per n_act (`_act_edge_index` walks the link list: 5 ms on 250 000 links)."""
+        if hasattr(self, '_flow_exchange') or not 2 <= ce <= 8:
+            return False
+        ny, ne = self._norm('y', device), self._norm('e', device)
+        if (tuple(ny.shape[1:]) != (self.n_node, ny.shape[-1]) or ny.shape[-1] < 3 + int(bool(self.if_flood)) or
+                tuple(ne.shape[1:]) != (self.n_edge, ne.shape[-1]) or ne.shape[-1] < max(ce, 3 if self.act else 0)):
+            return False
+        if not self.act:
+            return True
+        if a is None or tuple(a.shape) != (B, T, n_act) or a.dtype != torch.float32 or not a.is_cuda:
+            return False
+        ok = self._idx_cache.get(('tail_act', n_act))
+        if ok is None:
+            ok = self._idx_cache[('tail_act', n_act)] = (len(self._act_edge_index()) == n_act and
+                                                         (self.edge_fusion or len(self.act_edges) == n_act))
+        return ok
+
     def _predict_tail_hip(self, y, ey, a, b, nb_, x, np_form):
         """Everything of `_predict` after the forward as `uds_predict_tail` (bit-identical to the tensor code below it), or None
         where the tensor route stays: `fused_tail` off, a local model of `shard_emulator` (its flows cross the cut between the
         link gates and the balance), shapes the kernels do not take (conv='False' models with other channel counts), NumPy mode
         under autograd, and `b` or a norm that needs a gradient."""
-        if not self.fused_tail or not y.is_cuda or hasattr(self, '_flow_exchange'):
+        if not self.fused_tail or not y.is_cuda:
             return None
         B, T, C = y.shape[0], self.seq_out, 3 + int(bool(self.if_flood))
         ce, bc = ey.shape[-1], b.shape[-1]
         cy = C - 2 if self.edge_fusion else C
         n_act = a.shape[-1] if self.act else 0
-        ny, ne = self._norm('y', y.device), self._norm('e', y.device)
-        if (tuple(y.shape) != (B, T, self.n_node, cy) or tuple(ey.shape) != (B, T, self.n_edge, ce) or not 2 <= ce <= 8 or
-                tuple(b.shape) != (B, T, self.n_node, bc) or x.shape[-1] < 1 or tuple(ny.shape[1:]) != (self.n_node, ny.shape[-1]) or
-                ny.shape[-1] < C or tuple(ne.shape[1:]) != (self.n_edge, ne.shape[-1]) or ne.shape[-1] < max(ce, 3 if self.act else 0) or
-                any(t.dtype != torch.float32 for t in (y, ey, b, x))):
-            return None
-        if self.act and (a is None or tuple(a.shape) != (B, T, n_act) or a.dtype != torch.float32 or not a.is_cuda or
-                         len(self._act_edge_index()) != n_act or (not self.edge_fusion and len(self.act_edges) != n_act)):
+        if (tuple(y.shape) != (B, T, self.n_node, cy) or tuple(ey.shape) != (B, T, self.n_edge, ce) or
+                tuple(b.shape) != (B, T, self.n_node, bc) or x.shape[-1] < 1 or any(t.dtype != torch.float32 for t in (y, ey, b, x)) or
+                not self._tail_takes(y.device, B, T, ce, a, n_act)):
             return None
         if _ag.grad_on(b, nb_, *self._norms.values()):
             return None
@@ -1193,20 +1236,26 @@ class Emulator(nn.Module):
     def _roll_step(self, x, ex, a_i, b_i, fit=False):
         """One chunk of the autoregressive rollout (emulator.py:403-423): forward on the last seq_in steps, post-processing,
         then the window shifts by seq_out steps fed with the prediction (flood bit thresholded at 0.5)."""
-        ae_i = self.get_edge_action(a_i, True) if self.act else None
-        adj_i = self.get_adj_action(a_i, True) if self.act and self.use_adj else None       # :407
+        ae_i, adj_i = self._chunk_actions(a_i)                                              # :407
         y, ey = self.forward(x[:, -self.seq_in:], b_i, ex[:, -self.seq_in:], ae_i, adj_i, training=fit)
         y, ey = self.post_proc_tf((y, ey), a_i, b_i)
-        if self.if_flood:                                   # flood bit fed back as a hard 0/1 (:417)
-            x_new = torch.cat([y[..., :-1], (y[..., -1:] > 0.5).float(), b_i], dim=-1)
-        else:
-            x_new = torch.cat([y, b_i], dim=-1)
+        return (y, ey) + self._shift_window(x, ex, y, ey, b_i, ae_i)
+
+    def _chunk_actions(self, a_i):
+        """(ae_i, adj_i): the link settings and the adjacency mask the forward of one chunk takes, from its settings a_i."""
+        return (self.get_edge_action(a_i, True) if self.act else None,
+                self.get_adj_action(a_i, True) if self.act and self.use_adj else None)
+
+    def _shift_window(self, x, ex, y, ey, b_i, ae_i):
+        """The next (x, ex) of the rollout (:413-423): the windows keep their last seq_in - seq_out steps and take the chunk's
+        post-processed prediction y, ey with its boundary b_i (flood bit fed back as a hard 0/1, :417) and its link settings ae_i
+        (ones for a model without actions)."""
         keep = self.seq_in - self.seq_out
+        x_new = torch.cat([y[..., :-1], (y[..., -1:] > 0.5).float(), b_i] if self.if_flood else [y, b_i], dim=-1)
         x = torch.cat([x[:, -keep:], x_new], dim=1) if keep > 0 else x_new
-        ae_new = ae_i if self.act else torch.ones(ey.shape[:-1] + (1,), device=ey.device)
-        ex_new = torch.cat([ey, ae_new], dim=-1)
+        ex_new = torch.cat([ey, ae_i if self.act else torch.ones(ey.shape[:-1] + (1,), device=ey.device)], dim=-1)
         ex = torch.cat([ex[:, -keep:], ex_new], dim=1) if keep > 0 else ex_new
-        return y, ey, x, ex
+        return x, ex
 
     def _fused_roll_ok(self, x, b, ex):
         """The plain configuration whose post-forward part `uds_roll_update` covers: edge fusion, no control actions, no tide,
@@ -1347,30 +1396,20 @@ class Emulator(nn.Module):
         `fused_fit_tail` off, a local model of `shard_emulator` (its flows cross the cut between the link gates and the balance),
         channel counts the kernels do not take (conv='False' models with a wider state; the rule of `_predict_tail_hip`), and a
         setting, boundary, target or norm that needs a gradient (the operator is differentiable in the network outputs only)."""
-        if not self.fused_fit_tail or not x.is_cuda or hasattr(self, '_flow_exchange'):
+        if not self.fused_fit_tail or not x.is_cuda:
             return None
         if 'y' not in self._norms or 'e' not in self._norms or (self.balance and 'b' not in self._norms):
             return None                          # the kernels read the norms a plain model's tensor code never asks for
         dev, N, E = x.device, self.n_node, self.n_edge
         B, T = x.shape[0], self.seq_out * max(self.roll, 1)
-        ce, C = self.e_out, 3 + int(bool(self.if_flood))
+        ce = self.e_out
         n_act = a.shape[-1] if self.act and a is not None else 0
-        ny, ne, nb = self._norm('y', dev), self._norm('e', dev), self._norm('b', dev) if self.balance else None
-        if (self.n_out != (1 if self.edge_fusion else 3) or not 2 <= ce <= 8 or b.dim() != 4 or tuple(b.shape[:3]) != (B, T, N) or
+        ny, nb = self._norm('y', dev), self._norm('b', dev) if self.balance else None
+        if (self.n_out != (1 if self.edge_fusion else 3) or b.dim() != 4 or tuple(b.shape[:3]) != (B, T, N) or
                 y.dim() != 4 or tuple(y.shape[:3]) != (B, T, N) or y.shape[-1] < 3 or tuple(ey.shape) != (B, T, E, ce) or
-                tuple(ny.shape[1:]) != (N, ny.shape[-1]) or ny.shape[-1] < C or tuple(ne.shape[1:]) != (E, ne.shape[-1]) or
-                ne.shape[-1] < max(ce, 3 if self.act else 0) or (nb is not None and tuple(nb.shape[1:]) != (N, nb.shape[-1])) or
-                any(t.dtype != torch.float32 or not t.is_cuda for t in (x, b, y, ey))):
+                (nb is not None and tuple(nb.shape[1:]) != (N, nb.shape[-1])) or
+                any(t.dtype != torch.float32 or not t.is_cuda for t in (x, b, y, ey)) or not self._tail_takes(dev, B, T, ce, a, n_act)):
             return None
-        if self.act and (a is None or tuple(a.shape) != (B, T, n_act) or a.dtype != torch.float32 or not a.is_cuda):
-            return None
-        if self.act:            # every setting drives its links (and, without edge fusion, its two nodes): a fact of the model, looked up once
-            ok = self._idx_cache.get(('fit_tail_act', n_act))       # (`_act_edge_index` walks the link list: 5 ms on 250 000 links)
-            if ok is None:
-                ok = self._idx_cache[('fit_tail_act', n_act)] = (len(self._act_edge_index()) == n_act and
-                                                                 (self.edge_fusion or len(self.act_edges) == n_act))
-            if not ok:
-                return None
         if _ag.grad_on(a if self.act else None, b, y, ey, *self._norms.values()):
             return None
         spec = self._tail_spec(dev, n_act, b.shape[-1], ce)
@@ -1405,7 +1444,7 @@ class Emulator(nn.Module):
         self.last_fit_tail_path = 'hip'
         spec, ops = fused
         c = lambda t: None if t is None else t.detach().contiguous()
-        so, keep = self.seq_out, self.seq_in - self.seq_out
+        so = self.seq_out
         tail = lambda ny_, ney_, sl: _ag.FitTailFn.apply(ny_, ney_, c(a[:, sl]) if self.act else None, c(b[:, sl]), c(y[:, sl]), c(ey[:, sl]),
                                                          self._inc_handle, spec, ops, self.act and self._has_pump)
         if not self.roll:
@@ -1416,17 +1455,10 @@ class Emulator(nn.Module):
             for i in range(self.roll):                     # `_model` with roll > 0, `_roll_step` with the tail fused
                 sl = slice(i * so, (i + 1) * so)
                 a_i, b_i = (a[:, sl] if a is not None else None), b[:, sl]
-                ae_i = self.get_edge_action(a_i, True) if self.act else None
-                adj_i = self.get_adj_action(a_i, True) if self.act and self.use_adj else None
+                ae_i, adj_i = self._chunk_actions(a_i)
                 out_y, out_ey, s = tail(*self.forward(x[:, -self.seq_in:], b_i, ex[:, -self.seq_in:], ae_i, adj_i, training=fit), sl)
                 sums = s if sums is None else sums + s
-                if self.if_flood:
-                    x_new = torch.cat([out_y[..., :-1], (out_y[..., -1:] > 0.5).float(), b_i], dim=-1)
-                else:
-                    x_new = torch.cat([out_y, b_i], dim=-1)
-                x = torch.cat([x[:, -keep:], x_new], dim=1) if keep > 0 else x_new
-                ex_new = torch.cat([out_ey, ae_i if self.act else torch.ones(out_ey.shape[:-1] + (1,), device=out_ey.device)], dim=-1)
-                ex = torch.cat([ex[:, -keep:], ex_new], dim=1) if keep > 0 else ex_new
+                x, ex = self._shift_window(x, ex, out_y, out_ey, b_i, ae_i)
         rows = float(y.shape[0] * y.shape[1])
         node_loss, edge_loss = sums[0] / (rows * self.n_node), sums[2] / (rows * self.n_edge)
         fl_loss = sums[1] / (rows * self.n_node) if self.if_flood and not self.balance else None
@@ -1458,25 +1490,37 @@ class Emulator(nn.Module):
         if fit:
             for p in params:
                 p.requires_grad_(True)
+        return self._fit_step((x, a, b, y, ex, ey), fit, params, captured=False)
+
+    def _fit_step(self, inputs, fit, params, captured):
+        """The step itself, once for both modes of `fit_eval`: losses, total loss, gradients zeroed, backward, optimizer step, the
+        detached losses.  captured=False (the eager step): the loss is tested on the host, agreed over the data-parallel ranks,
+        before backward; the gradients are all-reduced after it; the optimizer is created on first use and a `HipKerasAdam` reports
+        after its step.  captured=True (inside a graph, one rank): nothing touches the host -- `HipKerasAdam.step(loss)` tests the
+        loss and the gradient norms on the device, and `_fit_eval_graph` reads its status after the replay."""
+        x, a, b, y, ex, ey = inputs
         with torch.set_grad_enabled(bool(fit)):
             ae = self.get_edge_action(a, True) if self.act else None
             node_loss, fl_loss, edge_loss = self._fit_losses(x, a, b, y, ex, ey, ae, fit)
             if fit:
                 loss = self._fit_total_loss(node_loss, fl_loss, edge_loss)
-                from .dist import all_ranks_finite, allreduce_gradients
-                if not all_ranks_finite(loss):       # agreed over the data-parallel ranks: all raise or none does
-                    raise FloatingPointError('Loss contains NaN or Inf values.')
+                if not captured:
+                    from .dist import all_ranks_finite, allreduce_gradients
+                    if not all_ranks_finite(loss):       # agreed over the data-parallel ranks: all raise or none does
+                        raise FloatingPointError('Loss contains NaN or Inf values.')
                 for p in params:
                     p.grad = None
                 loss.backward()
-                allreduce_gradients(params)          # data-parallel ranks: one bucketed all-reduce (no-op on one rank)
-                if self._optimizer is None:
-                    self._optimizer = (HipKerasAdam if self._graphed_fit else KerasAdam)(params, self.learning_rate, clipnorm=1.0)
-                self._optimizer.step()
-                if isinstance(self._optimizer, HipKerasAdam):
-                    self._optimizer.raise_if_not_finite()
-        out = [node_loss.detach()] + ([fl_loss.detach()] if self.if_flood and fl_loss is not None else []) + [edge_loss.detach()]
-        return out
+                if captured:
+                    self._optimizer.step(loss)
+                else:
+                    allreduce_gradients(params)          # data-parallel ranks: one bucketed all-reduce (no-op on one rank)
+                    if self._optimizer is None:
+                        self._optimizer = (HipKerasAdam if self._graphed_fit else KerasAdam)(params, self.learning_rate, clipnorm=1.0)
+                    self._optimizer.step()
+                    if isinstance(self._optimizer, HipKerasAdam):
+                        self._optimizer.raise_if_not_finite()
+        return [node_loss.detach()] + ([fl_loss.detach()] if self.if_flood and fl_loss is not None else []) + [edge_loss.detach()]
 
     # ------------------------------------------------------------------ fit_eval as one captured graph per step
     def fit_graph_refusal(self, *tensors):
@@ -1515,20 +1559,6 @@ class Emulator(nn.Module):
                 if name in m.__dict__:
                     setattr(m, name, None)
 
-    def _fit_graph_body(self, inputs, fit, params):
-        """The step itself, as the eager `fit_eval` runs it on one rank, with the finite tests left to `HipKerasAdam` on the device."""
-        x, a, b, y, ex, ey = inputs
-        with torch.set_grad_enabled(bool(fit)):
-            ae = self.get_edge_action(a, True) if self.act else None
-            node_loss, fl_loss, edge_loss = self._fit_losses(x, a, b, y, ex, ey, ae, fit)
-            if fit:
-                loss = self._fit_total_loss(node_loss, fl_loss, edge_loss)
-                for p in params:
-                    p.grad = None
-                loss.backward()
-                self._optimizer.step(loss)
-        return [node_loss.detach()] + ([fl_loss.detach()] if self.if_flood and fl_loss is not None else []) + [edge_loss.detach()]
-
     def _capture_fit_graph(self, inputs, fit, params):
         """Static input buffers, two warm-up steps on a side stream that leave the model as it was, then the capture on ONE stream
         (nothing forks inside it: the graph is a chain).  An error during warm-up or capture propagates."""
@@ -1545,7 +1575,7 @@ class Emulator(nn.Module):
                 with torch.no_grad():
                     saved = [t.detach().clone() for t in params + opt.m + opt.v + [opt.state]]
             for _ in range(2):                              # caches, handles, tile plans, kernel code objects, library workspaces
-                self._fit_graph_body(G['inputs'], fit, params)
+                self._fit_step(G['inputs'], fit, params, captured=True)
             if fit:
                 with torch.no_grad():
                     for dst, src in zip(params + opt.m + opt.v + [opt.state], saved):
@@ -1561,7 +1591,7 @@ class Emulator(nn.Module):
         G['graph'] = torch.cuda.CUDAGraph()
         try:
             with torch.cuda.graph(G['graph']):
-                G['out'] = self._fit_graph_body(G['inputs'], fit, params)
+                G['out'] = self._fit_step(G['inputs'], fit, params, captured=True)
         finally:
             self._invalidate_weight_packs()                 # a pack made while capturing holds nothing until a replay
             for m in ne_dense:
