@@ -23,6 +23,15 @@
 //   stores its outputs behind its row loads, and the compiler -- which merges its pending-operation state over the
 //   exec-masked store branches -- would wait vmcnt(0) for those fresh stores before the next P1; X's row loads are
 //   therefore inline asm and their one wait is counted by hand: vmcnt(number of stores issued since).
+// * Set-up (paid once per (tile, chunk) workgroup: 1 010 times per launch at the headline) is two vector-memory round trips
+//   behind one scalar one, where it used to be four.  Trip 0 (scalar): the tile's side and the eight-int header of its block
+//   from global memory -- the section offsets are known before anything is in LDS.  Trip 1, issued back to back: the tile block,
+//   the attention vectors, each lane's row ids straight from the global block (clamped indices stay inside the block) and the
+//   team's weights into their final registers; one wait for the block, one __syncthreads.  Trip 2: the first snapshot's rows
+//   (Y: pp / rm, X: the asm loads) and the NodeEdge gather incl. the overflow list; X's static P3 state and Y's ag_locs are
+//   computed under it.  The gathered values are read by Y's aggregate only, from behind the first lds_barrier of the
+//   pipeline (the one after P1(0)), so no second set-up barrier is needed.  Each team still drains with ONE
+//   __builtin_amdgcn_s_waitcnt(vmcnt(0)) on every path into its snapshot loop.
 #pragma once
 #include "kernels_fused.hpp"
 
@@ -108,9 +117,22 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
   const int chunk_id = w / a.n_tiles;
   const int s_begin = chunk_id * a.chunk;
   const int s_end = min(a.S, (chunk_id + 1) * a.chunk);
+#ifdef UDS_PHASE_TIMING
+  unsigned long long tm_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = clock64();      // stamp 0 runs from kernel entry to the first lds_barrier
+  const unsigned long long rt0_ = __builtin_amdgcn_s_memrealtime(), mt0_ = tl_;
+#endif
+  // ---- set-up, trip 0 (scalar): the tile's side and the header of its block, both from global memory ----
+  // The header (the same eight ints the block copy puts at smem[0..7]) gives the section offsets before anything is in LDS, so
+  // every address of trip 1 can be formed at once.
+  const int32_t *gblk = a.blocks + (int64_t)tile * a.meta_cap;
   const int sd = __builtin_amdgcn_readfirstlane(a.hdr[tile * TILE_HDR_INTS + 6]);
+  int hd_[TILE_HDR_INTS];
+#pragma unroll
+  for (int q = 0; q < TILE_HDR_INTS; ++q) hd_[q] = __builtin_amdgcn_readfirstlane(gblk[q]);
   if (!((a.side_mask >> sd) & 1)) return;
   const FusedSide &S_ = a.side[sd];
+  const int n_own = hd_[0], n_prim = hd_[1], n_sec = hd_[2], flags = hd_[3], n_ovf = hd_[4], n_adj = hd_[5], inc_width = hd_[7];
+  const EllOffsets off = ell_offsets(n_own, n_prim, n_sec, flags, n_ovf, n_adj);
 
   float *s_self = reinterpret_cast<float *>(smem + a.meta_cap);         // [2][p_cap]
   float *s_nbr = s_self + 2 * a.p_cap;                                   // [2][p_cap]
@@ -119,26 +141,7 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
   float *hx = sec + 2 * a.q_cap * SEC_STRIDE;    // [2][p_cap * 64]
   const int sec_buf = a.q_cap * SEC_STRIDE, hx_buf = a.p_cap * FUSED_D;
 
-  // ---- set-up: tile block, attention vectors (each team loads its own weights inside its branch) ----
-  {
-    const uint4 *src = reinterpret_cast<const uint4 *>(a.blocks + (int64_t)tile * a.meta_cap);
-    uint4 *dst = reinterpret_cast<uint4 *>(smem);
-    for (int i = tid; i < a.meta_cap / 4; i += NT) dst[i] = src[i];
-  }
-  if (tid < FUSED_D) {   // scaled by log2(e): scores are logits in base-2 units, P3 needs no multiply in front of its exp2
-    attn[tid] = S_.a_self[tid] * 1.44269504088896340736f;
-    attn[FUSED_D + tid] = S_.a_nbr[tid] * 1.44269504088896340736f;
-    if (tid < FUSED_H) attn[2 * FUSED_D + tid] = S_.b_small ? S_.b_small[tid] : 0.f;
-    attn[2 * FUSED_D + FUSED_H + tid] = S_.b_out ? S_.b_out[tid] : 0.f;
-  }
-  __syncthreads();
-  const int n_own = __builtin_amdgcn_readfirstlane(smem[0]), n_prim = __builtin_amdgcn_readfirstlane(smem[1]),
-            n_sec = __builtin_amdgcn_readfirstlane(smem[2]), flags = __builtin_amdgcn_readfirstlane(smem[3]),
-            n_ovf = __builtin_amdgcn_readfirstlane(smem[4]), n_adj = __builtin_amdgcn_readfirstlane(smem[5]),
-            inc_width = __builtin_amdgcn_readfirstlane(smem[7]);
-  const EllOffsets off = ell_offsets(n_own, n_prim, n_sec, flags, n_ovf, n_adj);
   const int32_t *prim_ids = smem + off.prim;
-  const int32_t *sec_ids = smem + off.sec;
   const uint32_t *inc_loc = reinterpret_cast<const uint32_t *>(smem + off.inc_loc);
   int32_t *inc_w = smem + off.inc_w;
   const f32x4 *inc_val4 = reinterpret_cast<const f32x4 *>(inc_w);
@@ -146,18 +149,63 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
   const int32_t *ovf_ptr = smem + off.ovf_ptr, *ovf_loc = smem + off.ovf_loc;
   int32_t *ovf_w = smem + off.ovf_w;
   const int32_t *adj_ptr = smem + off.adj_ptr, *adj_loc = smem + off.adj_loc;
-
-  for (int i = tid; i < ELL_INC * n_prim; i += NT) {      // NodeEdge values of the fixed-width lists (0 for padding)
-    const int k = inc_w[i];
-    reinterpret_cast<float *>(inc_w)[i] = k >= 0 ? S_.ne_val[k] : 0.f;
-  }
-  if (flags & ELL_FLAG_INC_OVF)
-    for (int i = tid; i < n_ovf; i += NT) reinterpret_cast<float *>(ovf_w)[i] = S_.ne_val[ovf_w[i]];
   const float *ovf_val = reinterpret_cast<const float *>(ovf_w);
 
+  // ---- set-up, trip 1: every load whose address is known now, issued back to back; nothing waits until all are in flight ----
+  // Common to both teams: the tile block (first 16 bytes per thread; a block longer than NT x 16 B finishes in block_to_lds) and
+  // the attention vectors.  Each team adds, in its branch, its row ids straight from the global block and its weights.
+  // (issue_block is called inside the team's branch: loaded in front of it, blk0 was spilled to scratch behind a vmcnt(0).)
+  const int n4 = a.meta_cap / 4;
+  const uint4 *blk4 = reinterpret_cast<const uint4 *>(gblk);
+  uint4 blk0;
+  float at_s = 0.f, at_n = 0.f, at_bs = 0.f, at_bo = 0.f;
+  auto issue_block = [&]() __attribute__((always_inline)) {
+    blk0 = blk4[min(tid, n4 - 1)];
+    if (wave == 0) {       // lane = tid < FUSED_D
+      at_s = S_.a_self[lane];
+      at_n = S_.a_nbr[lane];
+      if (lane < FUSED_H && S_.b_small) at_bs = S_.b_small[lane];
+      if (S_.b_out) at_bo = S_.b_out[lane];
+    }
+  };
+  // one wait, one barrier: the tile block and the attention vectors are in LDS.  The compiler barrier in front keeps the stores
+  // (and the wait they need) behind every load the caller has issued.
+  auto block_to_lds = [&]() __attribute__((always_inline)) {
+    asm volatile("" ::: "memory");
+    uint4 *dst = reinterpret_cast<uint4 *>(smem);
+    if (tid < n4) dst[tid] = blk0;
+    for (int i = tid + NT; i < n4; i += NT) dst[i] = blk4[i];
+    if (wave == 0) {   // scaled by log2(e): scores are logits in base-2 units, P3 needs no multiply in front of its exp2
+      attn[lane] = at_s * 1.44269504088896340736f;
+      attn[FUSED_D + lane] = at_n * 1.44269504088896340736f;
+      if (lane < FUSED_H) attn[2 * FUSED_D + lane] = at_bs;
+      attn[2 * FUSED_D + FUSED_H + lane] = at_bo;
+    }
+    __syncthreads();
+  };
+  // ---- set-up, trip 2 (behind that barrier, next to the team's first-snapshot rows): the NodeEdge values of the fixed-width lists
+  // (0 for padding) and of the overflow list replace their indices in the tile block.  One element per thread covers the
+  // fixed-width lists (ELL_INC * n_prim <= NT: p_cap <= 128).  gather_issue puts the loads in flight, gather_land stores what
+  // came back; only the Y team's aggregate reads the values, from behind the first lds_barrier of the pipeline.
+  static_assert(ELL_INC * 32 * NY <= NT, "one gather element per thread covers the rows the Y team multiplies");
+  const int n_inc = ELL_INC * n_prim;
+  float ne_v = 0.f, ov_v = 0.f;
+  auto gather_issue = [&]() __attribute__((always_inline)) {
+    if (tid < n_inc) {
+      const int k = inc_w[tid];
+      if (k >= 0) ne_v = S_.ne_val[k];
+    }
+    if ((flags & ELL_FLAG_INC_OVF) && tid < n_ovf) ov_v = S_.ne_val[ovf_w[tid]];
+  };
+  auto gather_land = [&]() __attribute__((always_inline)) {
+    if (tid < n_inc) reinterpret_cast<float *>(inc_w)[tid] = ne_v;
+    if (flags & ELL_FLAG_INC_OVF) {
+      if (tid < n_ovf) reinterpret_cast<float *>(ovf_w)[tid] = ov_v;
+      for (int i = tid + NT; i < n_ovf; i += NT) reinterpret_cast<float *>(ovf_w)[i] = S_.ne_val[ovf_w[i]];
+    }
+  };
+
 #ifdef UDS_PHASE_TIMING
-  unsigned long long tm_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tl_ = clock64();
-  const unsigned long long rt0_ = __builtin_amdgcn_s_memrealtime(), mt0_ = tl_;
 #define WS_STAMP(k) do { const unsigned long long n_ = clock64(); tm_[k] += n_ - tl_; tl_ = n_; } while (0)
 #define WS_DUMP() do { if (a.dbg && lane == 0) { unsigned long long *o = a.dbg + ((size_t)blockIdx.x * 8 + wave) * 16; \
     for (int q_ = 0; q_ < 7; ++q_) o[q_] = tm_[q_]; o[12] = wave; \
@@ -170,7 +218,6 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
   const int64_t sec_stride = (int64_t)S_.n_sec_glob * FS, prim_stride = (int64_t)S_.n_prim_glob * FP;      // floats per snapshot
   const int n_snap = s_end - s_begin;
 
-  __syncthreads();   // NodeEdge values are in LDS
   // The two teams run two separate loops (the same number of barriers in each): what a team keeps in registers across the
   // snapshots -- the big weights here, the small weights, rows in flight and P3 state there -- is live in its own loop only.
   if (team_y) {
@@ -184,6 +231,13 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
     constexpr int KT32 = (FP + FUSED_H) / 16, KX32 = FP / 16, MB32 = FUSED_D / 32;      // 6 k-steps (4 of x, 2 of agg), 2 feature blocks
     static_assert(NY == 4, "one 32-row block per Y wave: four waves cover p_cap = 128");
     const int n32 = lane & 31, hf = lane >> 5;
+    const int lrow = 32 * yw + n32;
+    const bool valid = lrow < n_prim;
+    const int lr = min(lrow, n_prim - 1);
+    // trip 1, Y's part: this lane's row id from the tile's block in global memory (a clamped row -- and the word in front of the
+    // section, should it be empty -- lies inside the block), then the weights into the registers they stay in
+    issue_block();
+    const int prim_id = gblk[off.prim + lr];
     bf16x8 wh[KT32][MB32], wl[KT32][MB32];       // 96 VGPRs, resident across the snapshot loop
 #pragma unroll
     for (int t = 0; t < KT32; ++t)
@@ -192,20 +246,16 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
         wh[t][m] = __builtin_bit_cast(bf16x8, S_.w_big32[((t * MB32 + m) * 2 + 0) * 64 + lane]);
         wl[t][m] = __builtin_bit_cast(bf16x8, S_.w_big32[((t * MB32 + m) * 2 + 1) * 64 + lane]);
       }
-    const int lrow = 32 * yw + n32;
-    const bool valid = lrow < n_prim;
-    const int lr = min(lrow, n_prim - 1);
-    const unsigned prow = (unsigned)prim_ids[lr] * FP + 8u * hf;      // element offset of this lane's 8-float piece of k-step 0
+    block_to_lds();
+    const unsigned prow = (unsigned)prim_id * FP + 8u * hf;      // element offset of this lane's 8-float piece of k-step 0
     f32x4 pp[2 * KX32];           // the primary row of the snapshot P2 multiplies next: piece i = floats 16 (i >> 1) + 8 hf + 4 (i & 1)
     // the dense remainder of a trained NodeEdge (FusedSide::rem, (S, n_prim_glob, 32)): this lane's 16 aggregate features of its
     // row, fetched with the row itself one interval ahead and used as the initial value of the aggregate
     const bool has_rem = S_.rem != nullptr;
-    const unsigned rrow = (unsigned)prim_ids[lr] * FUSED_H + 8u * hf;
+    const unsigned rrow = (unsigned)prim_id * FUSED_H + 8u * hf;
     f32x4 rm[4] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     const int64_t rem_stride = (int64_t)S_.n_prim_glob * FUSED_H;
-    const unsigned ag_locs = inc_loc[lr];
-    const f32x4 ag_vals = inc_val4[lr];
-    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): drain the set-up loads on every path (see the X team's note)
+    // trip 2, Y's part: the first snapshot's row (and remainder piece), then the NodeEdge gather; the LDS read of ag_locs rides under it
     if (n_snap > 0) {
       const float *base = S_.prim_in + s_begin * prim_stride;
       static_for<2 * KX32>([&](auto i_) {
@@ -220,8 +270,13 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
         rm[3] = *reinterpret_cast<const f32x4 *>(rb + 20);
       }
     }
+    gather_issue();
+    const unsigned ag_locs = inc_loc[lr];
+    gather_land();
+    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): drain the set-up loads on every path (see the X team's note)
     WS_STAMP(0);
-    lds_barrier();      // the X team has computed the secondary MLP of the first snapshot
+    lds_barrier();      // the X team has computed the secondary MLP of the first snapshot; every thread's NodeEdge values are in LDS
+    const f32x4 ag_vals = inc_val4[lr];      // the only reader of those values (with ovf_val in the loop): behind that barrier
 
     auto mfma3_32 = [&](const bf16x8 &a_h, const bf16x8 &a_l, const bf16x8 &d_h, const bf16x8 &d_l, f32x16 acc) __attribute__((always_inline)) {
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, d_l, acc, 0, 0, 0);
@@ -330,15 +385,22 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
     typedef float f32x16 __attribute__((ext_vector_type(16)));
     constexpr int KS32 = FS / 16, SJ32 = (8 + NX - 1) / NX;      // 4 k-steps; 32-row secondary blocks per X wave (q_cap <= 256)
     const int n32 = lane & 31, hf = lane >> 5;
+    // trip 1, X's part: this lane's row ids from the tile's block in global memory (a clamped row -- and the word in front of the
+    // section, should it be empty -- lies inside the block), then the weights into the registers they stay in
+    issue_block();
+    int sec_id[SJ32];
+#pragma unroll
+    for (int j = 0; j < SJ32; ++j) sec_id[j] = gblk[off.sec + min((xw + NX * j) * 32 + n32, n_sec - 1)];
     bf16x8 w1h[KS32], w1l[KS32];      // 32 VGPRs
 #pragma unroll
     for (int t = 0; t < KS32; ++t) {
       w1h[t] = __builtin_bit_cast(bf16x8, S_.w_small32[(t * 2 + 0) * 64 + lane]);
       w1l[t] = __builtin_bit_cast(bf16x8, S_.w_small32[(t * 2 + 1) * 64 + lane]);
     }
+    block_to_lds();
     unsigned srow[SJ32];              // BYTE offsets of this lane's rows
 #pragma unroll
-    for (int j = 0; j < SJ32; ++j) srow[j] = ((unsigned)sec_ids[min((xw + NX * j) * 32 + n32, n_sec - 1)] * FS + 8u * hf) * 4u;
+    for (int j = 0; j < SJ32; ++j) srow[j] = ((unsigned)sec_id[j] * FS + 8u * hf) * 4u;
     f32x4 sp[SJ32][2 * KS32];         // the secondary rows of the snapshot P1 multiplies next (asm loads: see the header)
     auto load_sec_at = [&](const float *base) __attribute__((always_inline)) {      // unconditional (rows are clamped): a fixed number of loads
       static_for<SJ32>([&](auto j_) {
@@ -364,6 +426,10 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
     // the row's lanes by two bank-masked DPP row broadcasts.  The second slot set goes through ds_bpermute instead (the
     // LDS crossbar).  Rows are degree-sorted inside the tile and dealt in octets: unit u (0..3) of wave xw -> octet NX u + xw.
     const int ro = lane >> 3, c8 = lane & 7, hf8 = ro & 1;      // hf8: which 128-B half of a row this lane takes first (see phase3o)
+    // trip 2, X's part: the first snapshot's rows, then the NodeEdge gather; the static P3 state below (LDS reads and ballots on the
+    // tile block) is computed while both are in flight
+    if (n_snap > 0) load_sec(s_begin);
+    gather_issue();
     int p3_dmax[U];
     unsigned p3_pk[U][4];      // (the row's output row is re-read from the tile block per snapshot: registers are short)
     unsigned p3_jb4 = 0;          // this lane's own slot byte of the four octets, 8 bits each: the index of the score it gathers
@@ -398,6 +464,7 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
       if (8 * (NX * u + xw) < n_own) n_st += 2;
     }
     const float *bias_l = attn + 2 * FUSED_D + FUSED_H + 4 * c8;      // + 32 hf8 / + 32 - 32 hf8 for the lane's first / second piece      // the output bias, read back per snapshot (registers are short)
+    gather_land();
     __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): drain the set-up loads on every path (see the Y team's note)
 
     // ---------------- P1: secondary MLP, registers -> MFMA (32x32x16) -> sec ----------------
@@ -444,9 +511,8 @@ __global__ __launch_bounds__(FUSED_WAVES * 64, 2) void k_fused_ws(FusedArgs a) {
       });
     };
 
-    // first snapshot: rows -> registers -> P1 -> sec[0]; the second snapshot's rows into the registers
+    // first snapshot: rows (requested in trip 2) -> registers -> P1 -> sec[0]; the second snapshot's rows into the registers
     if (n_snap > 0) {
-      load_sec(s_begin);
       ws_vmcnt(0);
       pin_rows();
       phase1(0);

@@ -49,6 +49,13 @@ ok = rt > 0
 print('in-kernel clock: median %.3f GHz (shader cycles / 100 MHz real-time ticks per workgroup), workgroup life %.1f us median'
       % (float(np.median(mt[ok] / rt[ok])) * 0.1, float(np.median(rt[ok])) * 0.01))
 print('shares:', {n: round(float(rows[:, k].sum() / tot), 3) for k, n in enumerate(names)})
+# stamp 0 of k_fused_ws (kernel entry -> first barrier of the pipeline) per team, beside the life of the wave's workgroup in cycles
+life_cyc = (rows[:, 15] & 0xffffffff).astype(np.float64)
+for team, sel in (('Y (waves 0-3)', rows[:, 12] < 4), ('X (waves 4-7)', rows[:, 12] >= 4)):
+    s0, lc = rows[sel, 0].astype(np.float64), life_cyc[sel]
+    if len(s0) and lc.min() > 0:
+        print('stamp 0, team %s: median %d  p90 %d cycles = %.3f / %.3f of the median workgroup life (%d cycles)'
+              % (team, np.median(s0), np.percentile(s0, 90), np.median(s0) / np.median(lc), np.percentile(s0, 90) / np.median(lc), np.median(lc)))
 # workgroup life by side and size (wave 0 of every workgroup): how uneven the (tile, chunk) items are
 w0 = rows[rows[:, 12] == 0]
 life = (w0[:, 15] >> 32).astype(np.float64) * 0.01
