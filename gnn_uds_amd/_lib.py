@@ -136,6 +136,7 @@ SYMBOLS = {
     'uds_tile_plan_destroy': (_c_int, [_c_ptr]),
     'uds_tile_plan_sizes': (_c_int, [_c_ptr, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _c_ptr]),
     'uds_tile_plan_copy': (_c_int, [_c_ptr, _c_ptr, _c_ptr]),
+    'uds_tile_plan_refine_counts': (_c_int, [_c_ptr, _c_ptr]),
     'uds_tile_plan_blocks': (_c_int, [_c_ptr, _c_ptr, ctypes.POINTER(_c_i64)]),
     'uds_roll_update': (_c_int, [_c_ptr] * 7 + [_c_i64, _c_ptr, _c_i64, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr, _c_ptr]),
     'uds_predict_tail': (_c_int, [_c_ptr] * 9 + [_c_i64, _c_i64, _c_ptr, _c_ptr, _c_ptr]),
@@ -409,6 +410,7 @@ def fused_chunk(S, working_tiles):
 def tile_plan(graph, t_node=48, t_link=48, p_limit=0, q_limit=0, blocks=False):
     """Host-only tile plan of a DrainageGraph (no GPU needed): returns (hdr (T,8) int32, pool int32, caps).
     hdr columns: n_own, n_prim, n_sec, n_inc, n_adj, pool_off, side, meta_len (csrc/tile_plan.hpp).
+    caps: p_cap, q_cap, meta_cap and refine = what the refinement of the tiles did (fill / move / dissolve counts).
     blocks=True adds caps['blocks']: the (T, stride) int32 tile blocks the fused d = 64 kernel fetches (fixed-width index
     lists; include/uds_hip.h: uds_tile_plan_blocks), or None when a tile exceeds the byte-wide local indices."""
     lib = load()
@@ -425,6 +427,8 @@ def tile_plan(graph, t_node=48, t_link=48, p_limit=0, q_limit=0, blocks=False):
         hdr = np.zeros((nt.value, 8), dtype=np.int32)
         pool = np.zeros(pl.value, dtype=np.int32)
         _check(lib.uds_tile_plan_copy(h, hdr.ctypes.data, pool.ctypes.data), 'uds_tile_plan_copy')
+        refine = np.zeros(3, dtype=np.int64)
+        _check(lib.uds_tile_plan_refine_counts(h, refine.ctypes.data), 'uds_tile_plan_refine_counts')
         blk = None
         if blocks:
             stride = _c_i64()
@@ -433,7 +437,8 @@ def tile_plan(graph, t_node=48, t_link=48, p_limit=0, q_limit=0, blocks=False):
                 _check(lib.uds_tile_plan_blocks(h, blk.ctypes.data, ctypes.byref(stride)), 'uds_tile_plan_blocks')
     finally:
         lib.uds_tile_plan_destroy(h)
-    out = dict(p_cap=int(caps[0]), q_cap=int(caps[1]), meta_cap=int(caps[2]))
+    out = dict(p_cap=int(caps[0]), q_cap=int(caps[1]), meta_cap=int(caps[2]),
+               refine=dict(fill=int(refine[0]), move=int(refine[1]), dissolve=int(refine[2])))
     if blocks:
         out['blocks'] = blk
     return hdr, pool, out

@@ -13,7 +13,8 @@
 //   halo rows  : ADJ-neighbours of own rows outside the cluster -- their transformed features are
 //                recomputed locally instead of exchanged            (rest of prim)
 //   sec  rows  : every secondary row incident to a prim row (their MLP output is recomputed too)
-// All lists are int32; local CSR indices point into prim / sec.  Tested in tests/test_tile_plan.py.
+// All lists are int32; local CSR indices point into prim / sec.  Tested in tests/test_tile_plan.py and
+// tests/test_tile_plan_refine.py.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -40,6 +41,7 @@ struct SidePlan {
                                            //           inc_w[n_inc] adj_ptr[n_own+1] adj_loc[n_adj]
   std::vector<int32_t> key;                // locality key per tile (median BFS index of the nodes it touches)
   std::vector<int32_t> bfs_index;          // BFS visiting index of every primary row
+  int64_t n_fill = 0, n_move = 0, n_dissolve = 0;   // what the refinement did (TileRefiner)
 };
 
 // BFS spanning forest of adj (self loops ignored) + bottom-up packing into clusters of <= t_max rows.
@@ -221,17 +223,365 @@ inline void merge_clusters(const HostCsr &adj, const HostCsr &inc, const std::ve
   members.swap(out);
 }
 
+// ---- Refinement of the agglomerated tiles -------------------------------------------------------------------------------
+// merge_clusters() never moves a row once its cluster is placed: it leaves every tile a few primary rows short of the limit
+// and the halos where the clusters happened to end.  The refinement works on single rows, with EXACT footprints kept per
+// tile (prim_n = own + halo rows, sec_n = incident secondary rows) and updated from the neighbourhood of the moved row:
+//   u is staged by tile B    <=>  B owns u or owns a row that has u in its ADJ list
+//   q is staged by tile B    <=>  some primary row staged by B has q in its INC list
+// so a move costs O(degree^3) instead of a walk over both tiles.  Three steps, all deterministic (rows and tiles are visited
+// in index order, ties go to the lower index):
+//   boundary moves : a row goes to an adjacent tile when that lowers the summed primary footprint of the two tiles ("move"),
+//                    or keeps it while the target has at least as many own rows ("fill": the fuller tile absorbs the row,
+//                    the spare rows collect in the smaller one).  The sum of footprints falls, or stays while the sum of
+//                    squared sizes rises, so it ends.
+//   dissolve       : the tile with the fewest own rows hands ALL its rows to the tiles around it.  Those are full, so the
+//                    rows ripple outwards: tiles are levelled by their distance from the victim in the tile graph, a tile
+//                    only gives rows to the next level, and a tile that is asked for more room than it has asks the level
+//                    behind it.  Committed only if the victim ends empty, otherwise every move is taken back.
+// Limits (own rows, primary and secondary footprint) are checked before every move; a tile that exceeds them on its own
+// (a hub row) is left alone.  The number of tiles never grows.
+struct RefineStats {
+  int64_t fill = 0, move = 0, dissolve = 0;
+};
+
+class TileRefiner {
+ public:
+  TileRefiner(const HostCsr &adj, const HostCsr &inc, int own_limit, int p_limit, int q_limit, std::vector<std::vector<int32_t>> &members)
+      : adj_(adj), inc_(inc), own_limit_(own_limit), p_limit_(p_limit), q_limit_(q_limit), members_(members) {
+    transpose(adj_, adjT_);
+    transpose(inc_, incT_);
+    const int nt = (int)members_.size();
+    tile_of_.assign((size_t)adj_.n_rows, -1);
+    own_n_.assign(nt, 0);
+    prim_n_.assign(nt, 0);
+    sec_n_.assign(nt, 0);
+    frozen_.assign(nt, 0);
+    std::vector<int32_t> mark_p((size_t)adj_.n_rows, 0), mark_s((size_t)inc_.n_cols, 0);
+    for (int t = 0; t < nt; ++t) {
+      for (int32_t r : members_[t]) tile_of_[r] = t;
+      int np_ = 0, nq_ = 0;
+      tile_footprint(adj_, inc_, members_[t], mark_p, mark_s, np_, nq_);
+      own_n_[t] = (int32_t)members_[t].size();
+      prim_n_[t] = np_;
+      sec_n_[t] = nq_;
+      frozen_[t] = np_ > p_limit_ || nq_ > q_limit_ || own_n_[t] > own_limit_;
+    }
+    level_.assign(nt, -1);
+    want_.assign(nt, 0);
+    stamp_.assign(nt, 0);
+    stuck_at_.assign(nt, -1);
+    stuck_on_.resize(nt);
+  }
+
+  RefineStats run() {
+    std::vector<int32_t> rows((size_t)adj_.n_rows);
+    std::iota(rows.begin(), rows.end(), 0);
+    boundary_moves(rows, 8);
+    const int nt = (int)members_.size();
+    std::vector<char> failed(nt, 0);
+    int fails = 0;
+    while (fails < 8) {
+      int victim = -1;
+      for (int t = 0; t < nt; ++t)
+        if (own_n_[t] > 0 && !frozen_[t] && !failed[t] && (victim < 0 || own_n_[t] < own_n_[victim])) victim = t;
+      if (victim < 0) break;
+      if (dissolve(victim, rows)) {
+        ++stats_.dissolve;
+        fails = 0;
+        boundary_moves(rows, 2);      // the rows of the tiles the ripple went through: tidy their halos again
+        for (int32_t r : rows) failed[tile_of_[r]] = 0;      // and give the tiles there another chance
+      } else {
+        failed[victim] = 1;
+        ++fails;
+      }
+    }
+    std::vector<std::vector<int32_t>> out;
+    for (auto &m : members_)
+      if (!m.empty()) out.push_back(std::move(m));
+    members_.swap(out);
+    return stats_;
+  }
+
+ private:
+  static void transpose(const HostCsr &a, HostCsr &t) {
+    t.n_rows = a.n_cols;
+    t.n_cols = a.n_rows;
+    t.rowptr.assign((size_t)a.n_cols + 1, 0);
+    t.col.resize(a.col.size());
+    for (int32_t c : a.col) ++t.rowptr[c + 1];
+    for (int64_t i = 0; i < a.n_cols; ++i) t.rowptr[i + 1] += t.rowptr[i];
+    std::vector<int32_t> fill(t.rowptr.begin(), t.rowptr.end() - 1);
+    for (int32_t r = 0; r < (int32_t)a.n_rows; ++r)
+      for (int32_t p = a.rowptr[r]; p < a.rowptr[r + 1]; ++p) t.col[fill[a.col[p]]++] = r;
+  }
+  bool in_prim(int32_t u, int32_t b) const {
+    if (tile_of_[u] == b) return true;
+    for (int32_t p = adjT_.rowptr[u]; p < adjT_.rowptr[u + 1]; ++p)
+      if (tile_of_[adjT_.col[p]] == b) return true;
+    return false;
+  }
+  bool in_sec(int32_t q, int32_t b) const {
+    for (int32_t p = incT_.rowptr[q]; p < incT_.rowptr[q + 1]; ++p)
+      if (in_prim(incT_.col[p], b)) return true;
+    return false;
+  }
+  static bool push_unique(std::vector<int32_t> &v, int32_t x) {
+    if (std::find(v.begin(), v.end(), x) != v.end()) return false;
+    v.push_back(x);
+    return true;
+  }
+  // rows among {r} + ADJ(r) and their incident secondary rows that tile b does NOT stage in the current state
+  void unstaged(int32_t r, int32_t b, int &dp, int &dq) {
+    lp_.clear();
+    lq_.clear();
+    if (!in_prim(r, b)) lp_.push_back(r);
+    for (int32_t p = adj_.rowptr[r]; p < adj_.rowptr[r + 1]; ++p)
+      if (!in_prim(adj_.col[p], b)) push_unique(lp_, adj_.col[p]);
+    for (int32_t u : lp_)
+      for (int32_t p = inc_.rowptr[u]; p < inc_.rowptr[u + 1]; ++p)
+        if (std::find(lq_.begin(), lq_.end(), inc_.col[p]) == lq_.end() && !in_sec(inc_.col[p], b)) lq_.push_back(inc_.col[p]);
+    dp = (int)lp_.size();
+    dq = (int)lq_.size();
+  }
+  // what tile b would newly stage if it owned r (r is not its own row)
+  void add_cost(int32_t r, int32_t b, int &dp, int &dq) { unstaged(r, b, dp, dq); }
+  // what the tile that owns r would stop staging without it
+  void remove_gain(int32_t r, int &dp, int &dq) {
+    const int32_t a = tile_of_[r];
+    tile_of_[r] = -1;
+    unstaged(r, a, dp, dq);
+    tile_of_[r] = a;
+  }
+  bool fits(int32_t b, int ap, int aq) const {
+    return !frozen_[b] && own_n_[b] + 1 <= own_limit_ && prim_n_[b] + ap <= p_limit_ && sec_n_[b] + aq <= q_limit_;
+  }
+  void apply(int32_t r, int32_t b) {
+    const int32_t a = tile_of_[r];
+    int lp, lq, ap, aq;
+    remove_gain(r, lp, lq);
+    add_cost(r, b, ap, aq);
+    prim_n_[a] -= lp;
+    sec_n_[a] -= lq;
+    prim_n_[b] += ap;
+    sec_n_[b] += aq;
+    --own_n_[a];
+    ++own_n_[b];
+    tile_of_[r] = b;
+    stamp_[a] = stamp_[b] = ++clock_;
+    std::vector<int32_t> &ma = members_[a];
+    ma.erase(std::find(ma.begin(), ma.end(), r));
+    members_[b].push_back(r);
+  }
+  // tiles other than r's own that own a row next to r (either direction of ADJ)
+  void adjacent_tiles(int32_t r, std::vector<int32_t> &out) const {
+    out.clear();
+    const int32_t a = tile_of_[r];
+    for (int32_t p = adj_.rowptr[r]; p < adj_.rowptr[r + 1]; ++p)
+      if (tile_of_[adj_.col[p]] != a) push_unique(out, tile_of_[adj_.col[p]]);
+    for (int32_t p = adjT_.rowptr[r]; p < adjT_.rowptr[r + 1]; ++p)
+      if (tile_of_[adjT_.col[p]] != a) push_unique(out, tile_of_[adjT_.col[p]]);
+  }
+
+  void boundary_moves(const std::vector<int32_t> &rows, int max_rounds) {
+    std::vector<int32_t> cand;
+    for (int round = 0; round < max_rounds; ++round) {
+      int64_t moved = 0;
+      for (int32_t r : rows) {
+        const int32_t a = tile_of_[r];
+        if (frozen_[a]) continue;
+        adjacent_tiles(r, cand);
+        if (cand.empty()) continue;
+        int lp, lq;
+        remove_gain(r, lp, lq);
+        int32_t best = -1;
+        int best_d = 1;
+        for (int32_t b : cand) {
+          int ap, aq;
+          add_cost(r, b, ap, aq);
+          if (!fits(b, ap, aq)) continue;
+          const int d = ap - lp;
+          if (d > 0 || (d == 0 && own_n_[b] < own_n_[a])) continue;
+          if (best < 0 || d < best_d || (d == best_d && (own_n_[b] > own_n_[best] || (own_n_[b] == own_n_[best] && b < best)))) {
+            best = b;
+            best_d = d;
+          }
+        }
+        if (best < 0) continue;
+        apply(r, best);
+        ++(best_d < 0 ? stats_.move : stats_.fill);
+        ++moved;
+      }
+      if (!moved) break;
+    }
+  }
+
+  // up to k rows of tile a go to tiles of the next level; tiles that were too full are asked for room (want_)
+  int push_out(int32_t a, int k) {
+    int pushed = 0;
+    std::vector<int32_t> cand;
+    std::vector<int32_t> &blocked = stuck_on_[a];
+    auto ask = [&](int need) {      // the tiles that were too full share what is still to go
+      if (blocked.empty()) return;
+      const int share = (need + (int)blocked.size() - 1) / (int)blocked.size() + 1;
+      for (int32_t b : blocked) want_[b] += share;
+    };
+    if (stuck_at_[a] >= 0) {        // nothing fitted last time: the same again unless this tile or one of those changed since
+      bool same = stamp_[a] <= stuck_at_[a];
+      for (int32_t b : blocked) same = same && stamp_[b] <= stuck_at_[a];
+      if (same) {
+        ask(k);
+        return 0;
+      }
+      stuck_at_[a] = -1;
+    }
+    struct Cand { int d; int32_t r, b; };
+    std::vector<Cand> todo;
+    while (pushed < k && own_n_[a] > 0) {
+      todo.clear();
+      blocked.clear();
+      for (int32_t r : members_[a]) {
+        adjacent_tiles(r, cand);
+        int lp = -1, lq = 0;
+        Cand best{0, -1, -1};
+        for (int32_t b : cand) {
+          if (level_[b] != level_[a] + 1 || frozen_[b]) continue;
+          if (lp < 0) remove_gain(r, lp, lq);
+          int ap, aq;
+          add_cost(r, b, ap, aq);
+          if (!fits(b, ap, aq)) {
+            push_unique(blocked, b);
+            continue;
+          }
+          const int d = ap - lp;
+          if (best.r < 0 || d < best.d || (d == best.d && b < best.b)) best = Cand{d, r, b};
+        }
+        if (best.r >= 0) todo.push_back(best);
+      }
+      if (todo.empty()) {
+        ask(k - pushed);
+        stuck_at_[a] = clock_;
+        break;
+      }
+      // cheapest first; every move is checked again in the state the earlier ones left
+      std::stable_sort(todo.begin(), todo.end(), [](const Cand &x, const Cand &y) { return x.d != y.d ? x.d < y.d : x.r < y.r; });
+      const int before = pushed;
+      for (const Cand &c : todo) {
+        if (pushed >= k || pushed - before >= BATCH) break;
+        int lp, lq, ap, aq;
+        remove_gain(c.r, lp, lq);
+        add_cost(c.r, c.b, ap, aq);
+        if (!fits(c.b, ap, aq) || ap - lp > c.d) continue;
+        log_.push_back({c.r, a});
+        apply(c.r, c.b);
+        ++pushed;
+      }
+      if (pushed == before) break;
+    }
+    return pushed;
+  }
+
+  // touched: on success, the rows of every tile of the region (ascending)
+  bool dissolve(int32_t victim, std::vector<int32_t> &touched) {
+    // levels of the tile graph around the victim
+    std::vector<int32_t> region{victim};
+    level_[victim] = 0;
+    std::vector<int32_t> cand;
+    int64_t spare = 0;
+    int radius = 0;      // levels are added until the tiles around the victim have room for it twice over
+    for (size_t head = 0; head < region.size(); ++head) {
+      const int32_t a = region[head];
+      if (level_[a] > radius) {
+        if (spare * 10 >= (int64_t)own_n_[victim] * 20 || level_[a] > RADIUS) {
+          for (size_t i = head; i < region.size(); ++i) level_[region[i]] = -1;
+          region.resize(head);
+          break;
+        }
+        radius = level_[a];
+      }
+      if (a != victim && !frozen_[a]) spare += p_limit_ - prim_n_[a];
+      for (int32_t r : members_[a]) {
+        adjacent_tiles(r, cand);
+        for (int32_t b : cand)
+          if (level_[b] < 0) {
+            level_[b] = level_[a] + 1;
+            region.push_back(b);
+          }
+      }
+    }
+    log_.clear();
+    bool ok = spare >= own_n_[victim];
+    for (int sweep = 0; ok && sweep < MAX_SWEEPS && own_n_[victim] > 0; ++sweep) {
+      for (int32_t a : region) want_[a] = 0;
+      want_[victim] = own_n_[victim];
+      int progress = 0;
+      for (int32_t a : region)      // discovery order = by level
+        if (want_[a] > 0) progress += push_out(a, want_[a]);
+      if (!progress) {
+        // a row with no neighbour outside the victim (a separate piece): anywhere in the region it fits, cheapest first
+        const int32_t r = *std::min_element(members_[victim].begin(), members_[victim].end());
+        int32_t best = -1;
+        int best_ap = 0;
+        for (int32_t b : region) {
+          if (b == victim) continue;
+          int ap, aq;
+          add_cost(r, b, ap, aq);
+          if (fits(b, ap, aq) && (best < 0 || ap < best_ap)) {
+            best = b;
+            best_ap = ap;
+          }
+        }
+        if (best < 0) break;
+        log_.push_back({r, victim});
+        apply(r, best);
+      }
+    }
+    ok = ok && own_n_[victim] == 0;
+    if (!ok)
+      for (size_t i = log_.size(); i-- > 0;) apply(log_[i].row, log_[i].from);
+    if (ok) {
+      touched.clear();
+      for (int32_t a : region) touched.insert(touched.end(), members_[a].begin(), members_[a].end());
+      std::sort(touched.begin(), touched.end());
+    }
+    for (int32_t a : region) {
+      level_[a] = -1;
+      want_[a] = 0;
+      stuck_at_[a] = -1;
+    }
+    return ok;
+  }
+
+  // bounds of one dissolve attempt (planning time grows with them; at 200 000 rows the whole refinement takes a few seconds)
+  static constexpr int RADIUS = 6;        // levels of tiles around the victim that may take part
+  static constexpr int MAX_SWEEPS = 96;   // passes over those levels
+  static constexpr int BATCH = 8;         // rows a tile gives away between two looks at its boundary
+  struct Move { int32_t row, from; };
+  const HostCsr &adj_, &inc_;
+  HostCsr adjT_, incT_;
+  int own_limit_, p_limit_, q_limit_;
+  std::vector<std::vector<int32_t>> &members_;
+  std::vector<int32_t> tile_of_, own_n_, prim_n_, sec_n_, level_, want_, lp_, lq_;
+  std::vector<int64_t> stamp_, stuck_at_;      // when a tile last changed / when push_out last found it stuck
+  std::vector<std::vector<int32_t>> stuck_on_;  // ... and on which tiles
+  int64_t clock_ = 0;
+  std::vector<char> frozen_;
+  std::vector<Move> log_;
+  RefineStats stats_;
+};
+
 // p_limit / q_limit (0 = none): footprint limits of a tile (primary rows incl. halo / secondary rows).  With limits the
-// rows are first packed into small subtree clusters (t_max / 6 rows) which merge_clusters() then agglomerates into
-// tiles of at most t_max own rows that fill the limits; a cluster that still exceeds them (a hub row) is bisected in BFS
-// order until it fits, so one outlier does not set the LDS size of every workgroup.
+// rows are first packed into small subtree clusters (t_max / 8 rows) which merge_clusters() then agglomerates into
+// tiles of at most t_max own rows that fill the limits and TileRefiner then refines row by row; a cluster that still
+// exceeds them (a hub row) is bisected in BFS order until it fits, so one outlier does not set the LDS size of every
+// workgroup.
 inline SidePlan build_side_plan(const HostCsr &adj, const HostCsr &inc, int t_max, int side,
                                 const std::vector<int32_t> *node_bfs, int p_limit = 0, int q_limit = 0) {
   SidePlan plan;
   std::vector<int32_t> cluster_of;
   int n_clusters = 0;
   const bool limits = p_limit > 0 && q_limit > 0;
-  cluster_rows(adj, limits ? std::max(4, t_max / 6) : t_max, cluster_of, n_clusters, plan.bfs_index);
+  cluster_rows(adj, limits ? std::min(t_max, std::max(4, t_max / 8)) : t_max, cluster_of, n_clusters, plan.bfs_index);
   const int32_t n = (int32_t)adj.n_rows;
   std::vector<std::vector<int32_t>> members(n_clusters);
   for (int32_t r = 0; r < n; ++r) members[cluster_of[r]].push_back(r);   // ascending ids
@@ -255,7 +605,13 @@ inline SidePlan build_side_plan(const HostCsr &adj, const HostCsr &inc, int t_ma
       work.emplace_back(c.begin(), c.begin() + half);
     }
     members.swap(fitted);
-    if (limits) merge_clusters(adj, inc, plan.bfs_index, t_max, p_limit, q_limit, members);
+    if (limits) {
+      merge_clusters(adj, inc, plan.bfs_index, t_max, p_limit, q_limit, members);
+      const RefineStats rs = TileRefiner(adj, inc, t_max, p_limit, q_limit, members).run();
+      plan.n_fill = rs.fill;
+      plan.n_move = rs.move;
+      plan.n_dissolve = rs.dissolve;
+    }
     n_clusters = (int)members.size();
     for (auto &m : members) std::sort(m.begin(), m.end());
   }

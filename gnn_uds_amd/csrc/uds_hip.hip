@@ -125,7 +125,7 @@ inline bool ws_plan_ok(const uds_plan_slot &u) {
 
 // Tile plan for the kernel variant <fp, fs> (primary / secondary input rows of fp / fs floats: they set the size of the
 // DMA stage) under the LDS budget: fix the footprint limits (primary / secondary rows staged per tile, multiples of 16)
-// first; the planner then fills them (tile_plan.hpp: merge_clusters).
+// first; the planner then fills them (tile_plan.hpp: merge_clusters, TileRefiner).
 bool plan_network(const uds::HostCsr &adj, const uds::HostCsr &eadj, const uds::HostCsr &inc_n, const uds::HostCsr &inc_e,
                   int fp, int fs, uds::NetworkPlan &out, int64_t &lds, int &blk_cap) {
   // candidate (p_limit, q_limit) pairs, largest first; meta is bounded by the limits (checked after planning)
@@ -1976,6 +1976,14 @@ int uds_tile_plan_sizes(const uds_tile_plan_t *tp, int64_t *n_tiles, int64_t *po
     caps3[1] = tp->plan.q_cap;
     caps3[2] = tp->plan.meta_cap;
   }
+  return UDS_OK;
+}
+
+int uds_tile_plan_refine_counts(const uds_tile_plan_t *tp, int64_t *counts3) {
+  UDS_REQUIRE(tp && counts3, "uds_tile_plan_refine_counts: NULL argument");
+  counts3[0] = tp->plan.side[0].n_fill + tp->plan.side[1].n_fill;
+  counts3[1] = tp->plan.side[0].n_move + tp->plan.side[1].n_move;
+  counts3[2] = tp->plan.side[0].n_dissolve + tp->plan.side[1].n_dissolve;
   return UDS_OK;
 }
 

@@ -710,6 +710,9 @@ int uds_tile_plan_create(const int32_t *adj_rowptr, const int32_t *adj_col, cons
 int uds_tile_plan_destroy(uds_tile_plan_t *plan);
 int uds_tile_plan_sizes(const uds_tile_plan_t *plan, int64_t *n_tiles, int64_t *pool_len, int32_t *caps3);
 int uds_tile_plan_copy(const uds_tile_plan_t *plan, int32_t *hdr_out, int32_t *pool_out);
+/* What the row-by-row refinement of the plan did, both sides together (tile_plan.hpp: TileRefiner): counts3 = rows a
+ * fuller tile absorbed at no cost (fill), rows moved to shrink a halo (move), tiles dissolved into their neighbours. */
+int uds_tile_plan_refine_counts(const uds_tile_plan_t *plan, int64_t *counts3);
 /* The tile blocks the fused d = 64 kernel fetches (host-only, integer bookkeeping): one block per tile of the merged
  * list at a fixed stride of *stride_out ints, [8-int header | fixed-width index lists] (layout:
  * gnn_uds_amd/csrc/tile_plan.hpp, "Tile blocks of k_fused_tile").  Pass blocks_out = NULL to query the stride.  Returns
