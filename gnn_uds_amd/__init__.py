@@ -15,6 +15,7 @@ from .emulator import GRU, LSTM, Conv1D, Emulator                     # noqa: F4
 from . import inp                                                     # noqa: F401,E402
 from .agent import ConvNet, GlobalAttnSumPool                         # noqa: F401,E402
 from . import mpc                                                     # noqa: F401,E402
+from .mpc import Problem                                              # noqa: F401,E402
 from . import mbrl                                                    # noqa: F401,E402
 from .data import WindowStore, WindowTable                            # noqa: F401,E402
 from .train import emulate_event, fit                                 # noqa: F401,E402

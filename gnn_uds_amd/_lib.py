@@ -53,6 +53,10 @@ SYMBOLS = {
     'uds_adam_step': (_c_int, [_c_ptr, _c_i64, _c_ptr] + [ctypes.c_double] * 5 + [_c_ptr, _c_ptr, _c_i64, _c_ptr]),
     'uds_window_batch': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int] + [_c_ptr] * 7),
     'uds_window_draw': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, ctypes.c_uint64, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_mpc_objective': (_c_int, [_c_ptr, _c_ptr] + [_c_i64] * 5 + [_c_ptr] * 6),
+    'uds_mpc_objective_backward': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_ptr] + [_c_i64] * 4 + [_c_ptr] * 6),
+    'uds_ce_draw': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, ctypes.c_uint64, _c_ptr, _c_ptr, _c_ptr]),
+    'uds_ce_update': (_c_int, [_c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, ctypes.c_double, ctypes.c_double] + [_c_ptr] * 6),
     'uds_recurrent_forward_train': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
     'uds_recurrent_backward': (_c_int, [_c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_ptr, _c_i64, _c_i64, _c_i64, _c_int, _c_ptr, _c_ptr, _c_ptr]),
     'uds_recurrent_bwd_packed_bytes': (_c_i64, [_c_i64, _c_int]),
@@ -1258,6 +1262,84 @@ def window_draw(table, cum, seed, count, B, out=None):
                                   int(seed) & 0xFFFFFFFFFFFFFFFF, _dev_i64(count, 'count'), _dev_i32(out, 'out'), _stream()),
            'uds_window_draw')
     return out
+
+
+CE_MAX = 1024                         # candidates and variables of a cross-entropy call (csrc/kernels_mpc.hpp)
+
+
+def _mpc_objective_operands(what, preds, q_in0, w_flood, w_out, w_smooth, gamma):
+    """Shapes of the objective operands -> (pop, T, N, C, q0_stride)."""
+    if not isinstance(preds, torch.Tensor) or preds.dim() != 4:
+        raise UdsError('%s: preds must be (pop, T, N, C)' % what)
+    pop, T, N, C = preds.shape
+    if tuple(q_in0.shape) not in ((N,), (pop, N)):
+        raise UdsError('%s: q_in0 must be (%d,) or (%d, %d), got %r' % (what, N, pop, N, tuple(q_in0.shape)))
+    for name, w in (('w_flood', w_flood), ('w_out', w_out), ('w_smooth', w_smooth)):
+        if w is not None and tuple(w.shape) != (N,):
+            raise UdsError('%s: %s must be (%d,), got %r' % (what, name, N, tuple(w.shape)))
+    if gamma is not None and tuple(gamma.shape) != (T,):
+        raise UdsError('%s: gamma must be (%d,), got %r' % (what, T, tuple(gamma.shape)))
+    return pop, T, N, C, (N if q_in0.dim() == 2 else 0)
+
+
+def mpc_objective(preds, q_in0, w_flood=None, w_out=None, w_smooth=None, gamma=None, out=None):
+    """The scenario objective (pop,) of pop predicted horizons preds (pop, T, N, C) (uds_mpc_objective; include/uds_hip.h gives
+    the definition): q_in0 (N,) shared or (pop, N), dense per-node weights (N,) or None, gamma (T,) or None."""
+    what = 'mpc_objective'
+    pop, T, N, C, q0 = _mpc_objective_operands(what, preds, q_in0, w_flood, w_out, w_smooth, gamma)
+    out = _out(out, (pop,), preds, 'out')
+    if pop == 0:
+        return _nothing_to_launch(q_in0, 'q_in0', out)
+    _check(load().uds_mpc_objective(_dev(preds, 'preds'), _dev(q_in0, 'q_in0'), q0, pop, T, N, C, _dev(w_flood, 'w_flood', True),
+                                    _dev(w_out, 'w_out', True), _dev(w_smooth, 'w_smooth', True), _dev(gamma, 'gamma', True), _dev(out, 'out'),
+                                    _stream()), 'uds_mpc_objective')
+    return out
+
+
+def mpc_objective_backward(preds, q_in0, g, w_flood=None, w_out=None, w_smooth=None, gamma=None, out=None):
+    """d_preds (pop, T, N, C) of sum_p g[p] * mpc_objective(...)[p] (uds_mpc_objective_backward): every element written."""
+    what = 'mpc_objective_backward'
+    pop, T, N, C, q0 = _mpc_objective_operands(what, preds, q_in0, w_flood, w_out, w_smooth, gamma)
+    if tuple(g.shape) != (pop,):
+        raise UdsError('%s: g must be (%d,), got %r' % (what, pop, tuple(g.shape)))
+    out = _out(out, preds.shape, preds, 'out')
+    if pop == 0:
+        return _nothing_to_launch(q_in0, 'q_in0', out)
+    _check(load().uds_mpc_objective_backward(_dev(preds, 'preds'), _dev(q_in0, 'q_in0'), q0, _dev(g, 'g'), pop, T, N, C, _dev(w_flood, 'w_flood', True),
+                                             _dev(w_out, 'w_out', True), _dev(w_smooth, 'w_smooth', True), _dev(gamma, 'gamma', True),
+                                             _dev(out, 'out'), _stream()), 'uds_mpc_objective_backward')
+    return out
+
+
+def ce_draw(mean, std, seed, count, pop, out=None):
+    """pop candidates (pop, n_var) from N(mean, std) clipped to [0, 1] (uds_ce_draw): candidate i uses the stream index count + i
+    (Philox4x32-10, key = seed, counter (index, variable)); afterwards count (one int64 device element) is count + pop.  Device
+    only; nothing is read back."""
+    if not isinstance(mean, torch.Tensor) or not isinstance(std, torch.Tensor) or mean.dim() != 1 or tuple(std.shape) != tuple(mean.shape):
+        raise UdsError('ce_draw: mean and std must be one-dimensional tensors of one length')
+    if not isinstance(count, torch.Tensor) or count.numel() != 1:
+        raise UdsError('ce_draw: count must be one int64 device element')
+    out = _out(out, (int(pop), mean.shape[0]), mean, 'out')
+    _check(load().uds_ce_draw(_dev(mean, 'mean'), _dev(std, 'std'), mean.shape[0], int(pop), int(seed) & 0xFFFFFFFFFFFFFFFF, _dev_i64(count, 'count'),
+                              _dev(out, 'out'), _stream()), 'uds_ce_draw')
+    return out
+
+
+def ce_update(y, obj, n_elite, smooth, std_min, mean, std, best_y, best_obj, status):
+    """One cross-entropy update in place on mean, std (n_var,), best_y (n_var,), best_obj (1,) and status (int32, [0] raised when
+    no candidate is finite) from the candidates y (pop, n_var) and their objectives obj (pop,) (uds_ce_update).  Device only;
+    nothing is read back."""
+    if not isinstance(y, torch.Tensor) or y.dim() != 2:
+        raise UdsError('ce_update: y must be (pop, n_var)')
+    pop, n_var = y.shape
+    for name, t, shape in (('obj', obj, (pop,)), ('mean', mean, (n_var,)), ('std', std, (n_var,)), ('best_y', best_y, (n_var,))):
+        if tuple(t.shape) != shape:
+            raise UdsError('ce_update: %s must be %r, got %r' % (name, shape, tuple(t.shape)))
+    if best_obj.numel() != 1 or status.numel() < 1:
+        raise UdsError('ce_update: best_obj must hold one element and status at least one')
+    _check(load().uds_ce_update(_dev(y, 'y'), _dev(obj, 'obj'), pop, n_var, int(n_elite), float(smooth), float(std_min), _dev(mean, 'mean'),
+                                _dev(std, 'std'), _dev(best_y, 'best_y'), _dev(best_obj, 'best_obj'), _dev_i32(status, 'status'), _stream()),
+           'uds_ce_update')
 
 
 def flow_balance(handle, sign, flow, scale_in, scale_out):

@@ -658,6 +658,24 @@ class FitTailFn(torch.autograd.Function):
         return dy, dey, None, None, None, None, None, None, None, None
 
 
+class MpcObjectiveFn(torch.autograd.Function):
+    """The MPC scenario objective of a population of predicted horizons as one HIP forward and one HIP backward (include/uds_hip.h:
+    uds_mpc_objective / uds_mpc_objective_backward).  Differentiable in preds only: q_in0 is history, the weights and gamma are
+    constants of the problem."""
+
+    @staticmethod
+    def forward(ctx, preds, q_in0, w_flood, w_out, w_smooth, gamma):
+        preds = preds.contiguous()
+        ctx.save_for_backward(preds, q_in0)
+        ctx.weights = (w_flood, w_out, w_smooth, gamma)
+        return _lib.mpc_objective(preds, q_in0, w_flood, w_out, w_smooth, gamma)
+
+    @staticmethod
+    def backward(ctx, g):
+        preds, q_in0 = ctx.saved_tensors
+        return _lib.mpc_objective_backward(preds, q_in0, g.contiguous(), *ctx.weights), None, None, None, None, None
+
+
 def grad_on(*tensors):
     """True when autograd is recording and one of the tensors needs a gradient: the modules then take the Function path."""
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)

@@ -36,6 +36,7 @@
 #include "kernels_fit_tail.hpp"
 #include "kernels_optim.hpp"
 #include "kernels_data.hpp"
+#include "kernels_mpc.hpp"
 #include "tile_plan.hpp"
 
 namespace {
@@ -1126,6 +1127,85 @@ int uds_window_draw(const int32_t *starts_table, const uint64_t *cum, int64_t W,
   hipLaunchKernelGGL(uds::k_window_draw, dim3((unsigned)((B + uds::WINDOW_THREADS - 1) / uds::WINDOW_THREADS)), dim3(uds::WINDOW_THREADS), 0, st, k);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(UDS_EHIP, "%s: draw launch -> %s", what, hipGetErrorString(e));
   hipLaunchKernelGGL(uds::k_window_bump, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned long long *>(count), (unsigned long long)B);
+  return launched(what, hipGetLastError());
+}
+
+// ---- Model-predictive control (kernels_mpc.hpp).  The scenario objective of a population of predicted horizons
+// (objective_pred_tf, envs/scenario/astlingen.py:75-99) and its reverse mode share their checks; `out` is obj or d_preds.
+static int mpc_objective(const char *what, const float *preds, const float *q_in0, int64_t q0_stride, const float *g, bool backward, int64_t pop,
+                         int64_t T, int64_t N, int64_t C, const float *w_flood, const float *w_out, const float *w_smooth, const float *gamma,
+                         float *out, uds_stream_t stream) {
+  UDS_REQUIRE(preds && q_in0 && out && (g || !backward), "%s: NULL argument", what);
+  UDS_REQUIRE(C >= 2 && C <= 8, "%s: C=%lld outside [2, 8]", what, (long long)C);
+  UDS_REQUIRE(T >= 1 && T <= 4096, "%s: T=%lld outside [1, 4096]", what, (long long)T);
+  UDS_REQUIRE(pop >= 0 && pop <= ((int64_t)1 << 20) && N >= 1 && N <= ((int64_t)1 << 24), "%s: pop=%lld (at most 2^20) N=%lld (1 to 2^24)", what,
+              (long long)pop, (long long)N);
+  UDS_REQUIRE((pop * T * N + uds::MPC_THREADS - 1) / uds::MPC_THREADS < INT32_MAX, "%s: pop * T * N = %lld too large for one launch", what,
+              (long long)(pop * T * N));
+  UDS_REQUIRE(q0_stride == 0 || q0_stride == N, "%s: q0_stride=%lld (0 = one shared row, N = %lld = one row per candidate)", what, (long long)q0_stride,
+              (long long)N);
+  UDS_REQUIRE(w_flood || w_out || w_smooth, "%s: no weight vector given", what);
+  UDS_REQUIRE(aligned16(preds) && aligned16(q_in0) && aligned16(g) && aligned16(w_flood) && aligned16(w_out) && aligned16(w_smooth) && aligned16(gamma) &&
+                  aligned16(out),
+              "%s: every pointer must be 16-byte aligned", what);
+  if (pop == 0) return UDS_OK;
+  uds::MpcObjectiveArgs a{preds, q_in0, g, w_flood, w_out, w_smooth, gamma, backward ? nullptr : out, backward ? out : nullptr, q0_stride, pop,
+                          (int)T, (int)N, (int)C};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (backward)
+    hipLaunchKernelGGL(uds::k_mpc_objective_backward, dim3((unsigned)((pop * T * N + uds::MPC_THREADS - 1) / uds::MPC_THREADS)), dim3(uds::MPC_THREADS), 0,
+                       st, a);
+  else
+    hipLaunchKernelGGL(uds::k_mpc_objective, dim3((unsigned)pop), dim3(uds::MPC_THREADS), 0, st, a);
+  return launched(what, hipGetLastError());
+}
+
+int uds_mpc_objective(const float *preds, const float *q_in0, int64_t q0_stride, int64_t pop, int64_t T, int64_t N, int64_t C, const float *w_flood,
+                      const float *w_out, const float *w_smooth, const float *gamma, float *obj, uds_stream_t stream) {
+  return mpc_objective("uds_mpc_objective", preds, q_in0, q0_stride, nullptr, false, pop, T, N, C, w_flood, w_out, w_smooth, gamma, obj, stream);
+}
+
+int uds_mpc_objective_backward(const float *preds, const float *q_in0, int64_t q0_stride, const float *g, int64_t pop, int64_t T, int64_t N, int64_t C,
+                               const float *w_flood, const float *w_out, const float *w_smooth, const float *gamma, float *d_preds,
+                               uds_stream_t stream) {
+  return mpc_objective("uds_mpc_objective_backward", preds, q_in0, q0_stride, g, true, pop, T, N, C, w_flood, w_out, w_smooth, gamma, d_preds, stream);
+}
+
+// The two steps of a cross-entropy iteration share the limits of their sizes.
+static int ce_check_sizes(const char *what, int64_t pop, int64_t n_var) {
+  UDS_REQUIRE(pop >= 2 && pop <= uds::CE_MAX, "%s: pop=%lld outside [2, %d]", what, (long long)pop, uds::CE_MAX);
+  UDS_REQUIRE(n_var >= 1 && n_var <= uds::CE_MAX, "%s: n_var=%lld outside [1, %d]", what, (long long)n_var, uds::CE_MAX);
+  return UDS_OK;
+}
+
+int uds_ce_draw(const float *mean, const float *std, int64_t n_var, int64_t pop, uint64_t seed, uint64_t *count, float *out, uds_stream_t stream) {
+  const char *what = "uds_ce_draw";
+  UDS_REQUIRE(mean && std && count && out, "%s: NULL argument", what);
+  if (int rc = ce_check_sizes(what, pop, n_var)) return rc;
+  UDS_REQUIRE(aligned16(mean) && aligned16(std) && aligned16(count) && aligned16(out), "%s: every pointer must be 16-byte aligned", what);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  uds::CeDrawArgs k{mean, std, reinterpret_cast<const unsigned long long *>(count), out, (unsigned long long)seed, (int)n_var, (int)pop};
+  hipLaunchKernelGGL(uds::k_ce_draw, dim3((unsigned)((pop * n_var + uds::MPC_THREADS - 1) / uds::MPC_THREADS)), dim3(uds::MPC_THREADS), 0, st, k);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(UDS_EHIP, "%s: draw launch -> %s", what, hipGetErrorString(e));
+  hipLaunchKernelGGL(uds::k_window_bump, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned long long *>(count), (unsigned long long)pop);
+  return launched(what, hipGetLastError());
+}
+
+int uds_ce_update(const float *y, const float *obj, int64_t pop, int64_t n_var, int64_t n_elite, double smooth, double std_min, float *mean, float *std,
+                  float *best_y, float *best_obj, int32_t *status, uds_stream_t stream) {
+  const char *what = "uds_ce_update";
+  UDS_REQUIRE(y && obj && mean && std && best_y && best_obj && status, "%s: NULL argument", what);
+  if (int rc = ce_check_sizes(what, pop, n_var)) return rc;
+  UDS_REQUIRE(n_elite >= 1 && n_elite <= pop, "%s: n_elite=%lld outside [1, pop=%lld]", what, (long long)n_elite, (long long)pop);
+  UDS_REQUIRE(smooth >= 0 && smooth <= 1 && std_min >= 0 && std_min < INFINITY, "%s: smooth=%g (0 to 1) std_min=%g (finite, not negative)", what, smooth,
+              std_min);
+  UDS_REQUIRE(aligned16(y) && aligned16(obj) && aligned16(mean) && aligned16(std) && aligned16(best_y) && aligned16(best_obj) && aligned16(status),
+              "%s: every pointer must be 16-byte aligned", what);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  uds::CeUpdateArgs k{y, obj, mean, std, best_y, best_obj, status, (float)smooth, (float)std_min, (int)pop, (int)n_var, (int)n_elite};
+  hipLaunchKernelGGL(uds::k_ce_update, dim3((unsigned)n_var), dim3(uds::MPC_THREADS), 0, st, k);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return fail(UDS_EHIP, "%s: update launch -> %s", what, hipGetErrorString(e));
+  hipLaunchKernelGGL(uds::k_ce_commit, dim3(1), dim3(uds::MPC_THREADS), 0, st, k);
   return launched(what, hipGetLastError());
 }
 

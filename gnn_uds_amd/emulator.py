@@ -64,6 +64,10 @@ class Conv1D(nn.Module):
 # (None for GRU / LSTM), precision, output width
 TemporalLayer = namedtuple('TemporalLayer', 'conv1d kernel dilation activation precision out')
 
+# what `Emulator.decode` needs of the history (`Emulator.encode_history`): x (B, seq_out, N, H), e (B, seq_out, E, H) after the first
+# temporal stage, and the last linear step of the two embeddings, (B, 1, N, d) and (B, 1, E, d) (the resnet residual)
+History = namedtuple('History', 'x e x_lin_last e_lin_last')
+
 
 class _DenseShim:
     """What DenseFn reads of its module, for a bare (kernel, bias) pair."""
@@ -625,46 +629,93 @@ class Emulator(nn.Module):
         training: keras' `training=` flag -- switches the Dropout layers on when the model was built with `dropout` > 0."""
         drop = bool(self.dropout) and training
         self.last_temporal_route, self.last_head_route = [], []
+        self.last_prefix_batch = X.shape[0]
         if not self.conv:
             return self._forward_mlp(X, B, E, AE, drop)
-        dr = (lambda t: self._drop(t, True)) if drop else None
-        nb = X.shape[0]
-        c = lambda t: t.contiguous()
-        adj_mask = None
-        if ADJ is not None:
-            if not (self.act and self.use_adj):
-                raise ValueError('ADJ given but the model was built without act + use_adj')
-            adj_mask = self._adj_mask_from(ADJ, X.device).reshape(nb * self.seq_out, -1)
-        x, e, b, ae, x_lin_last, e_lin_last = self._embed(X, B, E, AE, drop, c)
-
-        def spatial(block, x, e, xb=None, eb=None, mask=None):
-            T = x.shape[1]
-            r = lambda t, n: None if t is None else t.reshape(nb * T, n, -1)
-            kw = {} if mask is None else {'adj_mask': mask}
-            if dr is not None:
-                kw['dropout'] = dr
-                if self.conv_kind == 'GAT':      # training=True reaches the GATConv layers too: Spektral's attention dropout (rate 0.5)
-                    kw['attn_dropout'] = self.dropout_stream
-            sink = getattr(self, '_attn_sink', None)
-            if sink is not None:                 # attention_coefficients(): the layers run unfused and hand their coefficients out
-                kw['attn_out'] = got = []
-            xs, es = block(r(x, self.n_node), r(e, self.n_edge), r(xb, self.n_node), r(eb, self.n_edge), **kw)
-            if sink is not None:
-                bt = lambda t: t.reshape((nb, T) + t.shape[-2:])
-                sink['block1' if block is self.block1 else 'block2'] = [bt(a) if isinstance(a, torch.Tensor) else (bt(a[0]), bt(a[1])) for a in got]
-            return xs.reshape(nb, T, self.n_node, -1), es.reshape(nb, T, self.n_edge, -1)
-
-        x, e = spatial(self.block1, x, e)
-        x, e = self._temporal(self.tem1_x, self.tem1_e, x, e)
-        x, e = x[:, -self.seq_out:], e[:, -self.seq_out:]             # :249,256
-        # concat([x, b]) / concat([e, ae]) (:260-262) are not materialised: the first layer of block 2 reads both pieces
-        x, e = spatial(self.block2, c(x), c(e), b, ae if self.act else None, adj_mask)
-        x, e = self._temporal(self.tem2_x, self.tem2_e, x, e)
-        pgrad = _ag.grad_on(*self.parameters())
-        return (self._output(x, x_lin_last, self.res_x, self.out, list(self.flood), self.flood_out, drop, pgrad),     # :313-333
-                self._output(e, e_lin_last, self.res_e, self.e_out_layer, [], None, drop, pgrad))                     # :317-337
+        adj_mask = self._adj_mask(ADJ, X.shape[0], X.device)
+        # the four embeddings first, in the reference's order (the dropout masks are drawn in it); then the two halves
+        x, e, b, ae, x_lin_last, e_lin_last = self._embed(X, B, E, AE, drop, lambda t: t.contiguous())
+        history = self._history_stage(x, e, x_lin_last, e_lin_last, drop)
+        return self._decode_stage(history, b, ae, adj_mask, drop)
 
     model = forward
+
+    # ------------------------------------------------------------------ the two halves of the graph model's forward
+    last_prefix_batch = None   # after a forward / predict_tf_shared: the batch the history half ran at (1 when a population shared it);
+    #                            after `mpc.Problem.predict`: that of the horizon's first chunk
+
+    def _adj_mask(self, ADJ, nb, device):
+        if ADJ is None:
+            return None
+        if not (self.act and self.use_adj):
+            raise ValueError('ADJ given but the model was built without act + use_adj')
+        return self._adj_mask_from(ADJ, device).reshape(nb * self.seq_out, -1)
+
+    def _spatial(self, block, x, e, xb=None, eb=None, mask=None, drop=False):
+        """One spatial block on (nb, T, N, f) / (nb, T, E, f) rows; xb / eb: the second piece of the first layer's input."""
+        nb, T = x.shape[:2]
+        r = lambda t, n: None if t is None else t.reshape(nb * T, n, -1)
+        kw = {} if mask is None else {'adj_mask': mask}
+        if drop:
+            kw['dropout'] = lambda t: self._drop(t, True)
+            if self.conv_kind == 'GAT':      # training=True reaches the GATConv layers too: Spektral's attention dropout (rate 0.5)
+                kw['attn_dropout'] = self.dropout_stream
+        sink = getattr(self, '_attn_sink', None)
+        if sink is not None:                 # attention_coefficients(): the layers run unfused and hand their coefficients out
+            kw['attn_out'] = got = []
+        xs, es = block(r(x, self.n_node), r(e, self.n_edge), r(xb, self.n_node), r(eb, self.n_edge), **kw)
+        if sink is not None:
+            bt = lambda t: t.reshape((nb, T) + t.shape[-2:])
+            sink['block1' if block is self.block1 else 'block2'] = [bt(a) if isinstance(a, torch.Tensor) else (bt(a[0]), bt(a[1])) for a in got]
+        return xs.reshape(nb, T, self.n_node, -1), es.reshape(nb, T, self.n_edge, -1)
+
+    def _history_stage(self, x, e, x_lin_last, e_lin_last, drop):
+        """Block 1 and the first temporal stage on the embedded history (:236-257) -> `History`: all a forward keeps of X and E."""
+        x, e = self._spatial(self.block1, x, e, drop=drop)
+        x, e = self._temporal(self.tem1_x, self.tem1_e, x, e)
+        return History(x[:, -self.seq_out:], e[:, -self.seq_out:], x_lin_last, e_lin_last)             # :249,256
+
+    def _decode_stage(self, history, b, ae, adj_mask, drop):
+        """Block 2, the second temporal stage and the output stage (:260-337) on a `History` and the embedded B / AE."""
+        # concat([x, b]) / concat([e, ae]) (:260-262) are not materialised: the first layer of block 2 reads both pieces
+        x, e = self._spatial(self.block2, history.x.contiguous(), history.e.contiguous(), b, ae if self.act else None, adj_mask, drop)
+        x, e = self._temporal(self.tem2_x, self.tem2_e, x, e)
+        pgrad = _ag.grad_on(*self.parameters())
+        return (self._output(x, history.x_lin_last, self.res_x, self.out, list(self.flood), self.flood_out, drop, pgrad),     # :313-333
+                self._output(e, history.e_lin_last, self.res_e, self.e_out_layer, [], None, drop, pgrad))                     # :317-337
+
+    def encode_history(self, X, E):
+        """The half of `forward` that reads only the history: normalised X (B, seq_in, N, c), E (B, seq_in, E, c) -> `History`
+        (x, e after the first temporal stage, cut to seq_out steps, and the last linear step of both embeddings).  Inference only
+        (no dropout).  `decode` is the other half; forward(X, B, E, AE, ADJ) computes decode(encode_history(X, E), B, AE, ADJ)
+        with the same kernels."""
+        if not self.conv:
+            raise NotImplementedError('encode_history / decode split the graph model; conv=False runs `forward`')
+        self.last_temporal_route, self.last_head_route = [], []
+        self.last_prefix_batch = X.shape[0]
+        c = lambda t: t.contiguous()
+        x_lin_last = self.embed_x(c(X[:, -1:]), 'linear')           # as `_embed`: the linear last step, then the activated embedding
+        x = self.embed_x(c(X), self.activation)
+        e_lin_last = self.embed_e(c(E[:, -1:]), 'linear')
+        e = self.embed_e(c(E), self.activation)
+        return self._history_stage(x, e, x_lin_last, e_lin_last, False)
+
+    def decode(self, history, B, AE=None, ADJ=None, pop=None):
+        """The half of `forward` after the history: embed_b, embed_ae, block 2, the second temporal stage, the output stage.
+        pop: `history` and B have batch 1 and are shared by a population whose AE / ADJ have batch pop: the boundary embedding
+        runs once, and the shared tensors are expanded to pop rows just before block 2 (one copy, the bytes block 2 reads)."""
+        if not self.conv:
+            raise NotImplementedError('encode_history / decode split the graph model; conv=False runs `forward`')
+        c = lambda t: t.contiguous()
+        b = self.embed_b(c(B))
+        ae = self.embed_ae(c(AE)) if self.act else None
+        nb = history.x.shape[0]
+        if pop is not None:
+            if nb != 1 or b.shape[0] != 1 or (ae is not None and ae.shape[0] != pop):
+                raise ValueError('decode(pop=%d): the history and B must have batch 1 and AE batch pop' % pop)
+            rows = lambda t: t.expand((pop,) + tuple(t.shape[1:])).contiguous()
+            history, b, nb = History(*(rows(t) for t in history)), rows(b), pop
+        return self._decode_stage(history, b, ae, self._adj_mask(ADJ, nb, history.x.device), False)
 
     def _embed(self, X, B, E, AE, drop, prep):
         """The four embeddings (:197-212) -> x, e, b, ae and the last linear step of x and e (the resnet residual).  prep: what
@@ -1078,6 +1129,30 @@ class Emulator(nn.Module):
         adj = self.get_adj_action(a, not np_form) if self.act and self.use_adj else None
         nb_ = self.normalize(b, 'b')
         y, ey = self.forward(self.normalize(x, 'x'), nb_, self.normalize(ex, 'e'), ae, adj)
+        return self._predict_tail(y, ey, a, b, nb_, x, np_form)
+
+    def predict_tf_shared(self, state, b, a, edge_state):
+        """`predict_tf` for a population that shares its history (the MPC candidates of `mpc.Problem`): state (T_in, N, C),
+        b (seq_out, N, cb), edge_state (T_in, E, Ce) unbatched, a (pop, seq_out, n_act) -> what predict_tf returns on the inputs
+        replicated pop times, to a tolerance (the history half runs at batch 1 and may take other kernels than at batch pop).
+        One normalisation, `encode_history` at batch 1 without autograd (nothing of it depends on a), `decode(..., pop=pop)`,
+        the same tail.  Autograd flows to a as in predict_tf; with use_adj the per-candidate mask enters block 2 only."""
+        if not self.conv:
+            raise NotImplementedError('predict_tf_shared needs a graph model (encode_history / decode); conv=False runs predict_tf')
+        pop = a.shape[0]
+        assert b.shape[0] == self.seq_out
+        x, ex, b1 = state[-self.seq_in:].unsqueeze(0), edge_state[-self.seq_in:].unsqueeze(0), b.unsqueeze(0)
+        ae = self.get_edge_action(a, True) if self.act else None
+        adj = self.get_adj_action(a, True) if self.act and self.use_adj else None
+        nb1 = self.normalize(b1, 'b')
+        with torch.no_grad():
+            history = self.encode_history(self.normalize(x, 'x'), self.normalize(ex, 'e'))
+        y, ey = self.decode(history, nb1, ae, adj, pop=pop)
+        rows = lambda t: t.expand((pop,) + tuple(t.shape[1:]))
+        return self._predict_tail(y, ey, a, rows(b1), rows(nb1), rows(x), False)
+
+    def _predict_tail(self, y, ey, a, b, nb_, x, np_form):
+        """Everything of `_predict` after the forward: the HIP tail where it takes the model, else the tensor code."""
         fused = self._predict_tail_hip(y, ey, a, b, nb_, x, np_form)
         if fused is not None:
             return fused

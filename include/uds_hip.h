@@ -839,6 +839,53 @@ int uds_window_batch(const uds_window_series_t *series, const uds_window_norm_t 
 int uds_window_draw(const int32_t *starts_table, const uint64_t *cum, int64_t W, int64_t B, uint64_t seed, uint64_t *count, int32_t *out,
                     uds_stream_t stream);
 
+/* Model-predictive control on the device (gnn_uds_amd/mpc.py: Problem).
+ *
+ * uds_mpc_objective: the scenario objective (objective_pred_tf, envs/scenario/astlingen.py:75-99) of pop predicted horizons,
+ * preds (pop, T, N, C) with q_w = channel C - 1 (flooding volume) and q_in = channel 1 (inflow):
+ *   obj[p] = sum_t gamma[t] sum_n ( w_flood[n] q_w[p,t,n] + w_out[n] q_in[p,t,n] + w_smooth[n] |q_in[p,t,n] - q_in[p,t-1,n]| ),
+ *   q_in[p,-1,n] = q_in0[p * q0_stride + n]: the inflow of the last history step, q0_stride = 0 (one row (N) shared by the
+ *   population) or N (one row per candidate).
+ * w_flood / w_out / w_smooth: (N) weights, the index / weight lists of the targets scattered into dense vectors (duplicate
+ * indices summed); a NULL vector is an absent term, at least one is given.  A term whose weight is 0 is not formed and its
+ * channel not read.  gamma: (T) or NULL (= ones).  Limits: C in [2, 8], T in [1, 4096], N in [1, 2^24], pop in [0, 2^20]
+ * (pop = 0: nothing launched).  One workgroup per candidate, fp64 sums in one fixed order, no atomics: a second call gives
+ * the same bits, and |obj - exact| <= 2 * 2^-24 * sum|term| (csrc/kernels_mpc.hpp derives it).
+ *
+ * uds_mpc_objective_backward: d_preds (pop, T, N, C) = the gradient of sum_p g[p] obj[p]; EVERY element is written, 0 where no
+ * weight reaches.  The sub-gradient of |.| at 0 is 0 (torch.abs).  Each element is its contributions summed in fp64 and rounded
+ * once.  q_in0 gets no gradient (it is history).
+ *
+ * Both: every pointer 16-byte aligned; no allocation, no copy, no synchronisation (safe inside a stream capture). */
+int uds_mpc_objective(const float *preds, const float *q_in0, int64_t q0_stride, int64_t pop, int64_t T, int64_t N, int64_t C, const float *w_flood,
+                      const float *w_out, const float *w_smooth, const float *gamma, float *obj, uds_stream_t stream);
+int uds_mpc_objective_backward(const float *preds, const float *q_in0, int64_t q0_stride, const float *g, int64_t pop, int64_t T, int64_t N, int64_t C,
+                               const float *w_flood, const float *w_out, const float *w_smooth, const float *gamma, float *d_preds,
+                               uds_stream_t stream);
+
+/* The cross-entropy method over decision vectors in [0, 1]^n_var.  The sampling and update rules are this project's own (the
+ * reference's run_ce is a host loop over a TensorFlow model); pop in [2, 1024], n_var in [1, 1024], every pointer 16-byte
+ * aligned, no allocation, no copy, no synchronisation, no host read of a device value.
+ *
+ * uds_ce_draw: out (pop, n_var).  Candidate i of the call has the index j = *count + i; variable v takes Philox4x32-10 (as
+ * uds_dropout) with key = seed and counter = (j, v) -> words w0, w1;  u1 = ((w0 >> 8) + 0.5) 2^-24, u2 = ((w1 >> 8) + 0.5) 2^-24,
+ * evaluated in fp32 (the sum k + 0.5 is exact for k < 2^23 and rounds to even above, so u lies in (0, 1]);
+ *   z = sqrtf(-2 logf(u1)) cosf(2 pi u2),   out[i, v] = min(max(mean[v] + std[v] z, 0), 1).
+ * A second one-thread launch on the same stream then sets *count += pop (count: one device uint64), so no thread reads count
+ * after it moved: two calls of pop rows draw what one call of 2 pop rows draws.
+ *
+ * uds_ce_update: y (pop, n_var) the candidates, obj (pop) their objectives.  key(p) = obj[p], any NaN / Inf taken as +inf;
+ * rank(p) = #{q: key(q) < key(p) or (key(q) == key(p) and q < p)} (integer comparisons); p is elite when rank(p) < n_elite
+ * (1 <= n_elite <= pop) and obj[p] is finite.  Over the K elites, per variable: m = mean, s = population standard deviation
+ * (two passes, ddof 0), both as balanced trees of 10 levels in rank order;
+ *   mean <- smooth mean + (1 - smooth) m,   std <- max(smooth std + (1 - smooth) s, std_min)      (smooth in [0, 1]).
+ * best_y (n_var) / best_obj (1) take the rank-0 candidate when it is finite and obj < *best_obj (start best_obj at +inf).
+ * K = 0: mean, std, best_y and best_obj stay and status[0] = 1; status[0] is never cleared here (the caller zeroes it before
+ * its loop and reads it once after).  best_obj and status are written by a second launch on the same stream. */
+int uds_ce_draw(const float *mean, const float *std, int64_t n_var, int64_t pop, uint64_t seed, uint64_t *count, float *out, uds_stream_t stream);
+int uds_ce_update(const float *y, const float *obj, int64_t pop, int64_t n_var, int64_t n_elite, double smooth, double std_min, float *mean, float *std,
+                  float *best_y, float *best_obj, int32_t *status, uds_stream_t stream);
+
 /* Which launches a fused spatial layer makes (host-only bookkeeping: neither entry touches a device).
  *
  * The snapshots of a launch are cut into chunks and one workgroup handles one (tile, chunk) pair: *chunk = the chunk
