@@ -33,7 +33,7 @@ from . import _lib
 from .graph import DrainageGraph, csr_from_dense
 from . import autograd as _ag
 from .graph import csr_from_dense, edge_based_adj_csr, node_based_adj_csr
-from .layers import Dense, DiffusionConv, Dropout, DropoutStream, GATConv, GCNConv, GraphBaseBlock, NodeEdge, SpatialBlock, SpatialLayer, _glorot_uniform, _packed_kernel, _param
+from .layers import Dense, DiffusionConv, Dropout, DropoutStream, GATConv, GCNConv, GraphBaseBlock, NodeEdge, PackCache, SpatialBlock, SpatialLayer, _glorot_uniform, _packed_kernel, _param
 
 
 class Conv1D(nn.Module):
@@ -91,7 +91,7 @@ class _Recurrent(nn.Module):
 
     def __init__(self, units, return_sequences=True, in_features=None, generator=None, precision='fp32'):
         super().__init__()
-        self.precision, self._packed = precision, None
+        self.precision, self._packs = precision, PackCache()
         if not return_sequences:
             raise NotImplementedError('the emulator uses return_sequences=True (emulator.py:159,161)')
         self.units = int(units)
@@ -120,23 +120,23 @@ class _Recurrent(nn.Module):
         b_in, b_rec = (self.bias[0].contiguous(), self.bias[1].contiguous()) if self.KIND == 'GRU' else (self.bias, None)
         F = x.shape[-1]
         if self.precision == 'bf16x3' and self.units == 64 and F % 32 == 0:
-            key = (self.kernel._version, self.recurrent_kernel._version, self.bias._version, self.kernel.data_ptr(), self.recurrent_kernel.data_ptr())
             direct = _lib.recurrent_fused_supported(F, self.KIND)
-            if self._packed is None or self._packed[0] != key:
+
+            def build():
                 if direct:
-                    self._packed = (key, _lib.recurrent_pack(self.kernel, self.recurrent_kernel))
-                else:     # W + U do not fit the LDS together (LSTM at 128) or another width: the projection on the row-GEMM kernel
-                    G = self.G
-                    fold = b_in.clone()
-                    if b_rec is not None:
-                        fold[:2 * 64] += b_rec[:2 * 64]               # the z / r gates add both biases (the candidate's stays apart)
-                    self._packed = (key, _lib.recurrent_pack(None, self.recurrent_kernel),
-                                    [_lib.rowgemm_pack(self.kernel[:, 64 * g:64 * (g + 1)].contiguous()) for g in range(G)], fold)
+                    return (_lib.recurrent_pack(self.kernel, self.recurrent_kernel),)
+                # W + U do not fit the LDS together (LSTM at 128) or another width: the projection on the row-GEMM kernel
+                fold = b_in.clone()
+                if b_rec is not None:
+                    fold[:2 * 64] += b_rec[:2 * 64]               # the z / r gates add both biases (the candidate's stays apart)
+                return (_lib.recurrent_pack(None, self.recurrent_kernel),
+                        [_lib.rowgemm_pack(self.kernel[:, 64 * g:64 * (g + 1)].contiguous()) for g in range(self.G)], fold)
+            packed = self._packs.get('recurrent', (self.kernel, self.recurrent_kernel, self.bias), build)
             if direct:
                 # the whole layer in one launch on the matrix cores (input projection never written out, state fed back in registers)
-                return _lib.recurrent_fused(x, self._packed[1], b_in, b_rec, self.KIND)
+                return _lib.recurrent_fused(x, packed[0], b_in, b_rec, self.KIND)
             if _lib.rowgemm_supported(F, F, 64):
-                _, packed_u, packed_w, fold = self._packed
+                packed_u, packed_w, fold = packed
                 xp = torch.empty(x.shape[:-1] + (self.G * 64,), device=x.device, dtype=torch.float32)
                 for g, pk in enumerate(packed_w):
                     _lib.rowgemm_cat(x, None, pk, fold[64 * g:64 * (g + 1)].contiguous(), 64, 'linear', out=xp, col0=64 * g)
@@ -252,7 +252,7 @@ class HipKerasAdam(_AdamState):
         _lib.adam_step([self.params[i] for i in idx], [self.params[i].grad.contiguous() for i in idx], [self.m[i] for i in idx],
                        [self.v[i] for i in idx], self.state, self._ws, None if loss is None else loss.detach().reshape(1), self.lr, self.b1,
                        self.b2, self.eps, self.clipnorm)
-        for i in idx:           # the kernel wrote the parameters behind autograd's back: caches keyed on `_version` must see a change
+        for i in idx:           # the kernel wrote the parameters behind autograd's back: every PackCache must see a change
             torch.autograd.graph.increment_version(self.params[i])
 
     def raise_if_not_finite(self):
@@ -1627,12 +1627,12 @@ class Emulator(nn.Module):
                 self.dense_node_edge_train, self.fused_gat_backward, self.fused_temporal, self.snapshot_remainder, rest)
 
     def _invalidate_weight_packs(self):
-        """Forget every packed or derived copy of a weight that is cached per parameter version, so that the next forward rebuilds
-        it: inside a capture that makes every pack a node of the graph (a replay bumps no `_version`)."""
+        # Empty every module's PackCache, under whatever name it is held, so that the next forward rebuilds each packed or derived
+        # copy of a weight: inside a capture that makes every pack a node of the graph (a replay bumps no version).
         for m in self.modules():
-            for name in ('_packed', '_blocks', '_wide', '_val_cache', '_rest_packed', '_vals'):
-                if name in m.__dict__:
-                    setattr(m, name, None)
+            for held in vars(m).values():
+                if isinstance(held, PackCache):
+                    held.clear()
 
     def _capture_fit_graph(self, inputs, fit, params):
         """Static input buffers, two warm-up steps on a side stream that leave the model as it was, then the capture on ONE stream
@@ -1706,7 +1706,7 @@ class Emulator(nn.Module):
         G['graph'].replay()
         out = [t.clone() for t in G['out']]
         if fit:
-            for p in params:                                # no kernel: eager code that caches per `_version` re-packs from the new weights
+            for p in params:                                # no kernel: the PackCache keys change, eager code re-packs from the new weights
                 torch.autograd.graph.increment_version(p)
             self._optimizer.raise_if_not_finite()
         return out

@@ -53,13 +53,45 @@ def _flatten_snapshots(x):
     return x.reshape((-1,) + tuple(x.shape[-2:])).contiguous(), lead
 
 
+class PackCache:
+    """The packed or derived copies of a module's parameters (bf16 hi/lo fragments, column blocks, folded biases, support values,
+    polynomial tables), rebuilt exactly when a parameter they were made from changes.  One entry per slot: a new key replaces the
+    old value.  A plain object, no buffer: the contents are device memory tied to one parameter storage, so a copy or a pickle
+    of the module starts empty.  `Emulator._invalidate_weight_packs` clears it around a graph capture ("Weight packs")."""
+
+    def __init__(self):
+        self._slots = {}
+
+    def get(self, slot, tensors, build, extra=()):
+        """The value of `slot`, from build() when the slot is empty or its key differs.  The key: (_version, data_ptr()) of every
+        tensor the value depends on (None for an absent one), then `extra`."""
+        key = tuple(None if t is None else (t._version, t.data_ptr()) for t in tensors) + tuple(extra)
+        hit = self._slots.get(slot)
+        if hit is None or hit[0] != key:
+            hit = self._slots[slot] = (key, build())
+        return hit[1]
+
+    def peek(self, slot):
+        """The value of `slot` or None; never builds."""
+        hit = self._slots.get(slot)
+        return None if hit is None else hit[1]
+
+    def clear(self):
+        self._slots.clear()
+
+    def __deepcopy__(self, memo):
+        return PackCache()
+
+    def __reduce__(self):
+        return PackCache, ()
+
+
 def _packed_kernel(module, kernel2d):
     """bf16 hi/lo MFMA fragments of a (K, f_out) kernel, re-split only when the parameter changes."""
-    key = (module.kernel._version, module.kernel.data_ptr())
-    hit = getattr(module, '_packed', None)
-    if hit is None or hit[0] != key:
-        module._packed = (key, _lib.rowgemm_pack(kernel2d.contiguous()))
-    return module._packed[1]
+    packs = getattr(module, '_packs', None)
+    if packs is None:
+        packs = module._packs = PackCache()
+    return packs.get('kernel', (module.kernel,), lambda: _lib.rowgemm_pack(kernel2d.contiguous()))
 
 
 class Dense(nn.Module):
@@ -73,7 +105,7 @@ class Dense(nn.Module):
         super().__init__()
         self.units, self.activation, self.use_bias = int(units), activation or 'linear', use_bias
         self.precision = precision
-        self._gen = generator
+        self._gen, self._packs = generator, PackCache()
         self.kernel = self.bias = None
         if self.activation not in _lib.ACT:
             raise ValueError('unknown activation %r' % (activation,))
@@ -99,13 +131,11 @@ class Dense(nn.Module):
         if self.precision == 'bf16x3' and self.units > 64 and self.units % 16 == 0 and _lib.rowgemm_supported(fi, fi, 64) and \
                 xc.numel() // fi >= 4096:
             # wide outputs (d = 128): 64-column blocks of the kernel, each written into its columns of one output
-            key = (self.kernel._version, self.kernel.data_ptr(), None if self.bias is None else self.bias._version)
-            if getattr(self, '_blocks', None) is None or self._blocks[0] != key:
-                self._blocks = (key, [(c0, min(64, self.units - c0), _lib.rowgemm_pack(self.kernel[:, c0:c0 + 64].contiguous()),
-                                       None if self.bias is None else self.bias[c0:c0 + 64].contiguous())
-                                      for c0 in range(0, self.units, 64)])
+            blocks = self._packs.get('blocks', (self.kernel, self.bias), lambda: [
+                (c0, min(64, self.units - c0), _lib.rowgemm_pack(self.kernel[:, c0:c0 + 64].contiguous()),
+                 None if self.bias is None else self.bias[c0:c0 + 64].contiguous()) for c0 in range(0, self.units, 64)])
             out = torch.empty(xc.shape[:-1] + (self.units,), device=xc.device, dtype=torch.float32)
-            for c0, w, pk, bb in self._blocks[1]:
+            for c0, w, pk, bb in blocks:
                 _lib.rowgemm_cat(xc, None, pk, bb, w, act, out=out, col0=c0)
             return out
         return _lib.dense_act(xc, self.kernel, self.bias, act)
@@ -159,7 +189,7 @@ class GATConv(nn.Module):
             raise ValueError('GATConv: channels must be a multiple of 4 for attn_heads > 1 or return_attn_coef, got %d' % self.channels)
         self.dropout_rate, self.add_self_loops = dropout_rate, add_self_loops
         self.activation, self.use_bias = activation or 'linear', use_bias
-        self._gen = generator
+        self._gen, self._packs = generator, PackCache()
         self._graphs = _GraphArg()
         self.precision = 'fp32'      # numerics of the backward row GEMMs (the forward linear part is the exact kernel)
         # True: the single-head layer's backward is one uds_gat_backward_act call (activation, attention / aggregation, bias and
@@ -244,14 +274,14 @@ class GATConv(nn.Module):
             # wide layers (d = 128, the reference's default): the linear part on the matrix cores (split-bf16 row GEMM, 64
             # columns per launch), the attention projections as two matrix-vector products, then the CSR aggregation kernel
             w2 = self.kernel.reshape(fin, self.channels)
-            key = (self.kernel._version, self.attn_kernel_self._version, self.attn_kernel_neighs._version, self.kernel.data_ptr())
-            if getattr(self, '_wide', None) is None or self._wide[0] != key:
+
+            def build():
                 # per parameter version: the kernel's 64-column blocks and the two attention projections W a_self, W a_nbr
                 # (s = hx a = z (W a): one more narrow row GEMM instead of a 600k-row matrix-vector product)
                 cols = [_lib.rowgemm_pack(w2[:, c0:c0 + 64].contiguous()) for c0 in range(0, self.channels, 64)]
                 wa = torch.stack([w2 @ self.attn_kernel_self.reshape(-1), w2 @ self.attn_kernel_neighs.reshape(-1)], dim=1)
-                self._wide = (key, cols, _lib.rowgemm_pack(wa.contiguous()))
-            _, cols, wa_packed = self._wide
+                return cols, _lib.rowgemm_pack(wa.contiguous())
+            cols, wa_packed = self._packs.get('wide', (self.kernel, self.attn_kernel_self, self.attn_kernel_neighs), build)
             if not all(_lib.rowgemm_supported(fin, 32, min(64, self.channels - 64 * i)) for i in range(len(cols))):
                 raise _lib.UdsError('GATConv: %d -> %d does not fit the matrix-core row GEMM' % (fin, self.channels))
             hx = torch.empty(xs.shape[:-1] + (self.channels,), device=xs.device, dtype=torch.float32)
@@ -374,7 +404,7 @@ class DiffusionConv(nn.Module):
             raise ValueError('DiffusionConv: channels must be a multiple of 4, got %d' % self.channels)
         lim = math.sqrt(6.0 / (2 * self.K))         # glorot_uniform on shape (K + 1,): fan_in = fan_out = K + 1
         self.kernel = _param((torch.rand((self.channels, self.K), generator=generator) * 2 - 1) * lim)
-        self._cache, self._vals = {}, None
+        self._cache, self._packs = {}, PackCache()
         self.moments = bool(moments)
 
     @staticmethod
@@ -407,18 +437,18 @@ class DiffusionConv(nn.Module):
                 dense = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
                 csr = csr_from_dense(dense, keep_values=True)
             hit = self._cache[id(a)] = (a, _lib.CsrHandle(csr), torch.as_tensor(csr.val, dtype=torch.float32, device=device))
-            self._vals = None
         if self.moments:
             return hit[1], None, None, hit[2]
-        key = (self.kernel._version, self.kernel.data_ptr(), id(a))
-        if self._vals is None or self._vals[0] != key:
+
+        def build():
             av = hit[2].double()[:, None]
             th = self.kernel.detach().double()
             v = th[:, 0].expand(av.shape[0], -1)
             for k in range(1, self.K):                       # Horner, as tf.math.polyval
                 v = v * av + th[:, k]
-            self._vals = (key, (v - th[:, -1]).float().contiguous(), th[:, -1].float().contiguous())
-        return hit[1], self._vals[1], self._vals[2], hit[2]
+            return (v - th[:, -1]).float().contiguous(), th[:, -1].float().contiguous()
+        vals, c0 = self._packs.get('table', (self.kernel,), build, extra=(id(a),))
+        return hit[1], vals, c0, hit[2]
 
     def forward(self, inputs):
         x, a = inputs
@@ -472,33 +502,32 @@ class NodeEdge(nn.Module):
         w = torch.randn(shape, generator=generator, dtype=torch.float32) * 0.05      # 'random_normal'
         self.weight = _param(w.to(device))
         self.bias = _param(torch.zeros(shape, device=device))
-        self._handle = None
-        self._val_cache = None
-        self._rest_packed = None
+        self._handle, self._packs = None, PackCache()
         self.precision = 'bf16x3'      # of the dense remainder GEMM; SpatialLayer sets it to its own
         self.last_train_path = None    # 'dense' or 'support+remainder': what the last forward under autograd ran
 
     def support_values(self):
         """weight*inci + bias on the support (nnz,), plus the off-support remainder of bias or None."""
-        key = (self.weight._version, self.bias._version, self.weight.data_ptr(), self.bias.data_ptr())
-        if self._val_cache is not None and self._val_cache[0] == key:
-            return self._val_cache[1], self._val_cache[2]
-        flat, ival = self._flat.to(self.weight.device), self._ival.to(self.weight.device)
-        if self.sparse:
-            val, rest = self.weight * ival + self.bias, None
-        else:
-            val = self.weight.reshape(-1)[flat] * ival + self.bias.reshape(-1)[flat]
-            rest = self.bias.clone()
-            rest.reshape(-1).index_fill_(0, flat, 0.0)      # (an indexed store of a Python scalar uploads it: not capturable)
-            if self.weight.is_cuda and torch.cuda.is_current_stream_capturing():
-                # a capture cannot ask the device: Emulator._capture_fit_graph asked before it began (None: keep the remainder)
-                if getattr(self, '_capture_rest_none', None):
+        def build():
+            flat, ival = self._flat.to(self.weight.device), self._ival.to(self.weight.device)
+            if self.sparse:
+                val, rest = self.weight * ival + self.bias, None
+            else:
+                val = self.weight.reshape(-1)[flat] * ival + self.bias.reshape(-1)[flat]
+                rest = self.bias.clone()
+                rest.reshape(-1).index_fill_(0, flat, 0.0)      # (an indexed store of a Python scalar uploads it: not capturable)
+                if self.weight.is_cuda and torch.cuda.is_current_stream_capturing():
+                    # a capture cannot ask the device: Emulator._capture_fit_graph asked before it began (None: keep the remainder)
+                    if getattr(self, '_capture_rest_none', None):
+                        rest = None
+                elif not bool((rest != 0).any()):
                     rest = None
-            elif not bool((rest != 0).any()):
-                rest = None
-        self._val_cache = (key, val.contiguous(), rest)
-        self._rest_packed = None
-        return self._val_cache[1], rest
+            return val.contiguous(), rest
+        return self._packs.get('values', (self.weight, self.bias), build)
+
+    def _rest_pack(self):
+        """bf16 hi/lo planes of the off-support remainder (callers have checked that there is one), split once per update."""
+        return self._packs.get('rest', (self.weight, self.bias), lambda: _lib.remainder_pack(self.support_values()[1]))
 
     def remainder(self, xs, precision='bf16x3'):
         """`rest @ xs`, rest = the trained bias off the incidence support (emulator.py:36-39,44): the dense GEMM on the
@@ -509,9 +538,7 @@ class NodeEdge(nn.Module):
             return None
         if precision != 'bf16x3' or xs.shape[-1] % 4 or xs.shape[-1] > 64:
             return torch.matmul(rest, xs)
-        if self._rest_packed is None:
-            self._rest_packed = _lib.remainder_pack(rest)
-        return _lib.remainder_forward(self._rest_packed, tuple(rest.shape), xs)
+        return _lib.remainder_forward(self._rest_pack(), tuple(rest.shape), xs)
 
     def remainder_of_dense(self, es, dense):
         """`rest @ dense(es)` with the Dense layer's output written straight into the GEMM's operand planes (uds_remainder_forward_dense);
@@ -520,9 +547,7 @@ class NodeEdge(nn.Module):
         if rest is None or dense.precision != 'bf16x3' or es.shape[-1] not in (64, 128) or dense.units not in (32, 64) or not es.is_cuda \
                 or rest.shape[1] < 64:      # (a 30-row network fills half of that kernel's 64-row blocks: the flattened row GEMM is the better Dense there)
             return None
-        if self._rest_packed is None:
-            self._rest_packed = _lib.remainder_pack(rest)
-        return _lib.remainder_forward_dense(self._rest_packed, tuple(rest.shape), es.contiguous(), _packed_kernel(dense, dense.kernel), dense.bias,
+        return _lib.remainder_forward_dense(self._rest_pack(), tuple(rest.shape), es.contiguous(), _packed_kernel(dense, dense.kernel), dense.bias,
                                             dense.activation, dense.units)
 
     def handle(self):
@@ -646,8 +671,7 @@ class SpatialLayer(nn.Module):
             # emulator.py:229-230 with net = DiffusionConv; CSR filters (a model built from args.graph): the table-free form
             self.gcn_x = DiffusionConv(self.d, activation=activation, generator=g, moments=isinstance(filters[0], CSR))
             self.gcn_e = DiffusionConv(self.d, activation=activation, generator=g, moments=isinstance(filters[1], CSR))
-        self._net = net
-        self._packed = None       # (parameter versions, packed bf16 hi/lo fragments) of the four GEMM kernels
+        self._net, self._packs = net, PackCache()
         self.last_path = None     # which kernels the last forward ran: 'fused', 'fused+remainder', 'unfused' (tests, bench)
         self.last_route = None    # ... and the row of the route table (`route`) it took
         self.last_remainder = None   # per side what computed the dense remainder: 'snapshot', 'gemm' or None (no remainder); None before
@@ -655,22 +679,20 @@ class SpatialLayer(nn.Module):
         self._ws_rem_ok = None    # override for tests: False sends a d = 64 remainder to 'rem-split96' whatever the plan says
 
     def _packed_weights(self, p, fx, fe, remainder=False):
-        ks = (self.dense_xe.kernel, self.dense_ex.kernel, self.gat_x.kernel, self.gat_e.kernel)
-        key = tuple((k._version, k.data_ptr()) for k in ks) + (fx, fe, remainder)
-        if self._packed is None or self._packed[0] != key:
-            if remainder:
-                # a trained dense NodeEdge bias through the fused kernel's 96-wide split-input variant: the dense remainder
-                # `rest @ x_e` (S, R, 32) rides in as the 32 extra input columns, multiplied by the SAME rows of the GAT kernel
-                # as the CSR aggregate ([x | rem | agg] @ [Wx; Wagg; Wagg] = [x | agg + rem] @ [Wx; Wagg]); the in-kernel
-                # secondary MLP must not see those columns: zero rows under its kernel
-                z = torch.zeros((self.h, self.h), device=p['xe_k'].device)
-                aug = dict(xe_k=torch.cat([p['xe_k'], z]), ex_k=torch.cat([p['ex_k'], z]),
-                           gx_k=torch.cat([p['gx_k'], p['gx_k'][-self.h:]]), ge_k=torch.cat([p['ge_k'], p['ge_k'][-self.h:]]))
-                p = dict(p, **aug)
-            else:
-                aug = {}
-            self._packed = (key, _lib.spatial_pack_weights(p, fx, fe, self.h, self.d), aug)
-        return self._packed[1], self._packed[2]
+        """(packed bf16 hi/lo fragments of the four GEMM kernels, the augmented kernels of the remainder variant or {})."""
+        def build():
+            if not remainder:
+                return _lib.spatial_pack_weights(p, fx, fe, self.h, self.d), {}
+            # a trained dense NodeEdge bias through the fused kernel's 96-wide split-input variant: the dense remainder
+            # `rest @ x_e` (S, R, 32) rides in as the 32 extra input columns, multiplied by the SAME rows of the GAT kernel
+            # as the CSR aggregate ([x | rem | agg] @ [Wx; Wagg; Wagg] = [x | agg + rem] @ [Wx; Wagg]); the in-kernel
+            # secondary MLP must not see those columns: zero rows under its kernel
+            z = torch.zeros((self.h, self.h), device=p['xe_k'].device)
+            aug = dict(xe_k=torch.cat([p['xe_k'], z]), ex_k=torch.cat([p['ex_k'], z]),
+                       gx_k=torch.cat([p['gx_k'], p['gx_k'][-self.h:]]), ge_k=torch.cat([p['ge_k'], p['ge_k'][-self.h:]]))
+            return _lib.spatial_pack_weights(dict(p, **aug), fx, fe, self.h, self.d), aug
+        return self._packs.get('weights', (self.dense_xe.kernel, self.dense_ex.kernel, self.gat_x.kernel, self.gat_e.kernel), build,
+                               extra=(fx, fe, remainder))
 
     def network(self):
         if self._net is None:
@@ -901,9 +923,7 @@ class SpatialLayer(nn.Module):
             if dense.precision != 'bf16x3' or F not in (64, 128) or h not in (32, 64) or not src.is_cuda \
                     or not _lib.remainder_snapshot_plan(rest.shape[0], rest.shape[1], F, h)['G']:
                 return None
-            if layer._rest_packed is None:
-                layer._rest_packed = _lib.remainder_pack(rest)
-            args.append((layer._rest_packed, tuple(rest.shape), src.contiguous(), _packed_kernel(dense, dense.kernel), dense.bias,
+            args.append((layer._rest_pack(), tuple(rest.shape), src.contiguous(), _packed_kernel(dense, dense.kernel), dense.bias,
                          dense.activation, h))
         live = [a for a in args if a is not None]
         if len(live) == 2 and (live[0][2].shape[-1] != live[1][2].shape[-1] or live[0][5] != live[1][5]):

@@ -211,7 +211,7 @@ def test_moment_layer_under_autograd(dev, networks, which, C):
         with torch.no_grad():
             y0 = layer([xd.detach(), filt])
         out = layer([xd, filt])
-        assert torch.equal(out.detach(), y0) and layer._vals is None           # no table was built
+        assert torch.equal(out.detach(), y0) and layer._packs.peek('table') is None          # no table was built
         close(out, ref.detach(), 5e-6)
         (out * gy.float().to(dev)).sum().backward()
         close(xd.grad, xr.grad, 5e-6)
@@ -294,7 +294,7 @@ def test_emulator_forward_and_predict_tf(dev, networks, name, conv, precision, l
     assert tuple(py.shape) == tuple(qy.shape)
     assert _outliers(py, qy, tol) <= OUTLIERS_ALLOWED and _outliers(pey, qey, tol) <= OUTLIERS_ALLOWED
     if conv == 'Diffusion':
-        assert all(m.moments and m._vals is None for m in emul.modules() if isinstance(m, U.DiffusionConv))
+        assert all(m.moments and m._packs.peek('table') is None for m in emul.modules() if isinstance(m, U.DiffusionConv))
 
 
 def reference_moves_by(args, params, norms, cpu_in, tol, rel=1e-6, probes=2):
@@ -534,7 +534,7 @@ def test_moment_layer_at_size(dev, big):
         torch.cuda.synchronize()
     grew = torch.cuda.max_memory_allocated() - before
     print('inference forward at S = 1: %d bytes, the table alone %d' % (grew, ah.nnz * C * 4))
-    assert y1.shape == (1, big.n_node, C) and grew < ah.nnz * C * 4 and layer._vals is None
+    assert y1.shape == (1, big.n_node, C) and grew < ah.nnz * C * 4 and layer._packs.peek('table') is None
 
 
 def test_gcn_spatial_layer_at_size(dev, big):

@@ -267,8 +267,8 @@ def test_node_edge_cache_follows_parameter_updates(dev):
         ref = torch.matmul(ne.weight.detach().double().cpu() * inci64 + ne.bias.detach().double().cpu(), x.double())
         report('cache', what, out, ref, TOL_GEMM)
         close(out, ref, TOL_GEMM)
-        assert ne._rest_packed is not None
-        return ref, ne._rest_packed
+        assert ne._packs.peek('rest') is not None
+        return ref, ne._packs.peek('rest')
 
     ne.bias.data = (rn(R, M) * 0.05).to(dev)
     ref0, pk0 = check('first forward')
